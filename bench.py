@@ -7,6 +7,17 @@ DDIM schedule [153, 424, 926, 690] through the ADM-G ImageNet-64 UNet (classifie
 ~ U{0..999}, random-init weights of the real architecture (no checkpoint is reachable offline).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload guided|unguided|adm128|adm256|sd|candidate]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps, writes the last timed step's outputs if --dump-outputs is given, and
+prints the result line, and does nothing else.  Everything measured or checked beyond the headline
+-- the roofline and its per-launch HIP events, the untimed output-check batch, the pooled-FID stage's own timing, the CPU
+baseline and the secondary workloads -- runs only with --full.
+
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32; float64 for FIDs), at
+most 60 MiB in all (a larger output is replaced by a fixed, seeded sample of its elements, flattened in index order).  The
+inputs depend on the arguments only (seeded weights, labels, x_T and noise), so two builds can be compared output for
+output.  Rank 0 writes its own shard.
 
 --workload adm256 = the 256x256 line of the north star: ADM LSUN-256 dynamic UNet (search_lsun_cat.sh:1; 552.8 M, 2242.9
 GFLOP per image and evaluation), unconditional, uniform 5-step DDIM (the search's `--time_step 5` start candidate);
@@ -17,8 +28,8 @@ GFLOP per image and evaluation), unconditional, uniform 5-step DDIM (the search'
 (search_imagenet64_classifier_guidance.sh:1-20: batch 100, 5000 images): sampling (hipGraph replay) + HIP Inception pool3 +
 float64 Gram + Frechet distance on the device; reports candidates/hour and the reference's reset / sample / fid_time split.
 
-After the timed region every workload produces one more, untimed batch and checks it (finite float sample, uint8 batch
-that is not constant; `output_check` in the JSON line): a non-finite batch makes bench.py exit non-zero.
+With --full, after the timed region every workload produces one more, untimed batch and checks it (finite float sample,
+uint8 batch that is not constant; `output_check` in the JSON line): a non-finite batch makes bench.py exit non-zero.
 
 N > 1: either launch form works.  `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank per
 GPU, RCCL) runs the ranks directly; a bare `python bench.py --gpus N ...` (WORLD_SIZE unset) LAUNCHES ITSELF: the parent starts
@@ -26,11 +37,11 @@ that same torchrun command as a child process before anything touches the GPU, r
 child's code.  The batch shards by image with no data-path collective
 (weak scaling); timing is barrier + synchronize bracketed, MAX over ranks.  `--force-dist` builds a process group even at N = 1
 (a world-size-1 nccl group: every collective of the timing protocol and of the pooled-FID stage then runs through RCCL on a
-one-GPU box).  With the default workload (`auto`) the same process then runs the other BASELINE workloads as short secondary
-lines (`secondary`: adm256, sd, adm128, population; `--secondary none` to skip).  Rank 0 prints ONE JSON
-line with the metric, the dominant kernel's roofline (HIP events on the launch stream; with classifier guidance
-the gradient network runs concurrently on a second stream, so `roofline.isolated` adds the kernel's launch time from
-one untimed batch with the two networks in sequence) and the CPU oracle baseline timed on the host cores.
+one-GPU box).  With --full and the default workload (`auto`) the same process then runs the other BASELINE workloads as
+short secondary lines (`secondary`: adm256, sd, adm128, population; `--secondary none` to skip).  Rank 0 prints ONE JSON
+line with the metric; with --full also the dominant kernel's roofline (HIP events on the launch stream; with classifier
+guidance the gradient network runs concurrently on a second stream, so `roofline.isolated` adds the kernel's launch time
+from one untimed batch with the two networks in sequence) and the CPU oracle baseline timed on the host cores.
 """
 import argparse
 import json
@@ -114,6 +125,33 @@ def check_output(sample, u8):
         print(json.dumps({"error": "bench.py: the produced batch is non-finite or constant", "output_check": res}), flush=True)
         raise SystemExit(3)
     return res
+
+
+DUMP_BYTES = 60 << 20     # --dump-outputs: at most this many bytes of .npy data in all
+
+
+def write_outputs(path, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every array (device tensor or numpy) as `path/<name>.npy`, float64 data as float64 and everything else as
+    float32.  When the arrays together exceed `budget` bytes, each keeps its share of the budget as a sample of its elements
+    drawn by a generator seeded with 0 (the same elements for the same shapes in every run), flattened, in index order.
+    -> {name: {"shape", "dtype", "sampled_elements"}} for the JSON line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    desc = {}
+    for name, a in host.items():
+        shape, sampled = list(a.shape), None
+        if total > budget:
+            keep = max(1, budget * a.nbytes // total // a.itemsize)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+            sampled = int(keep)
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        desc[name] = {"shape": shape, "dtype": str(a.dtype), "sampled_elements": sampled}
+    return desc
 
 
 def _cpulist(text):
@@ -470,19 +508,22 @@ def run_sd(args, ctx):
     assert torch.isfinite(last["out"]).all()
     elapsed_local, elapsed = timed(ctx, one_step, args.steps)
     out = last["out"]
+    dumped = write_outputs(args.dump_outputs, {"latents": out}) if args.dump_outputs and rank == 0 else None
     rankinfo = gather_ranks(ctx, elapsed_local)
-    # the latents of the last timed step (outside the timed region): finite and not constant
-    lat_ok = bool(torch.isfinite(out).all().item())
-    lat_std = float(out.float().std().item())
-    chk = {"finite": lat_ok, "latent_shape": list(out.shape), "latent_mean": round(float(out.float().mean().item()), 5),
-           "latent_std": round(lat_std, 5), "how": "the last timed step's latents, checked after the timed region"}
-    if not lat_ok or not lat_std > 0.0:
-        print(json.dumps({"error": "bench.py --workload sd: non-finite or constant latents", "output_check": chk}), flush=True)
-        raise SystemExit(3)
+    chk = None
+    if args.full:
+        # the latents of the last timed step (outside the timed region): finite and not constant
+        lat_ok = bool(torch.isfinite(out).all().item())
+        lat_std = float(out.float().std().item())
+        chk = {"finite": lat_ok, "latent_shape": list(out.shape), "latent_mean": round(float(out.float().mean().item()), 5),
+               "latent_std": round(lat_std, 5), "how": "the last timed step's latents, checked after the timed region"}
+        if not lat_ok or not lat_std > 0.0:
+            print(json.dumps({"error": "bench.py --workload sd: non-finite or constant latents", "output_check": chk}), flush=True)
+            raise SystemExit(3)
     value = world * n * args.steps / elapsed
     model_tflops = value * 2 * len(SD_CAND) * SD_GFLOP_LATENT / 1e3
     roof = None
-    if not args.no_kernel_events:  # per-launch HIP events need the eager path: one untimed evaluation outside the graph
+    if args.full and not args.no_kernel_events:  # per-launch HIP events need the eager path: one untimed evaluation outside the graph
         unet.enable_graph(False)
         ops.CONV_PROFILE, ops.CONV_PROFILE_KEY = [], None
         x = torch.randn(2 * n, 4, 64, 64, device=dev)
@@ -509,7 +550,7 @@ def run_sd(args, ctx):
     if rank != 0:
         return None
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         del unet, sampler
         torch.cuda.empty_cache()
         cpu = cpu_baseline(workload="sd")
@@ -525,6 +566,8 @@ def run_sd(args, ctx):
                    "parallelism": f"dp{world} (latent-sharded, no data-path collective)"},
         "model_tflops": round(model_tflops, 1),
         "roofline": roof, "output_check": chk, "parity": parity_block("sd", args.torso), "hbm_peak_gb": hbm_peak_gb(dev), "cpu_baseline": cpu}
+    if dumped:
+        line["outputs"] = dumped
     if rankinfo:
         line.update(rankinfo)
     return line
@@ -603,28 +646,30 @@ def run_candidate(args, ctx):
     if not all(np.isfinite(fids)):
         print(json.dumps({"error": "bench.py --workload candidate: non-finite FID", "fids": [float(f) for f in fids]}), flush=True)
         raise SystemExit(3)
+    dumped = write_outputs(args.dump_outputs, {"fid": np.array(fids[-1:], dtype=np.float64)}) if args.dump_outputs and rank == 0 else None
     rankinfo = gather_ranks(ctx, elapsed_local)
-    # output check + roofline of the dominant kernel at this batch: one eager batch after the timed region
-    ev = searcher._ev
-    model.enable_graph(False)
-    classifier.enable_graph(False)
-    ev.set_candidate(CAND_LIST[0])
-    roof = None
-    if not args.no_kernel_events:
-        ops.CONV_PROFILE, ops.CONV_PROFILE_KEY = [], (5, 9, True, 2)
-    t0e = time.perf_counter()
-    u8, sample = ev.sample_batch(bs, seed=12345 + rank, return_float=True)
-    torch.cuda.synchronize()
-    eager_s = time.perf_counter() - t0e
-    if ops.CONV_PROFILE is not None:
-        prof, ops.CONV_PROFILE, ops.CONV_PROFILE_KEY = ops.CONV_PROFILE, None, None
-        if prof:
-            tr, src = pmc_traffic("guided")
-            roof, _ = roof_from(prof, CONV_SYMBOLS[(5, 9, True, 2)], None if tr is None else round(tr * bs / 256.0),
-                                None if tr is None else src + f"; measured at batch 256 and scaled by {bs}/256 (the kernel's traffic is linear in the batch)")
-            roof["how"] = (f"one eager batch of {bs} after the timed region (the timed candidates replay hipGraphs, which carry no events), "
-                           f"{eager_s * 1e3:.0f} ms with per-launch events")
-    chk = check_output(sample, u8)
+    roof = chk = None
+    if args.full:
+        # output check + roofline of the dominant kernel at this batch: one eager batch after the timed region
+        ev = searcher._ev
+        model.enable_graph(False)
+        classifier.enable_graph(False)
+        ev.set_candidate(CAND_LIST[0])
+        if not args.no_kernel_events:
+            ops.CONV_PROFILE, ops.CONV_PROFILE_KEY = [], (5, 9, True, 2)
+        t0e = time.perf_counter()
+        u8, sample = ev.sample_batch(bs, seed=12345 + rank, return_float=True)
+        torch.cuda.synchronize()
+        eager_s = time.perf_counter() - t0e
+        if ops.CONV_PROFILE is not None:
+            prof, ops.CONV_PROFILE, ops.CONV_PROFILE_KEY = ops.CONV_PROFILE, None, None
+            if prof:
+                tr, src = pmc_traffic("guided")
+                roof, _ = roof_from(prof, CONV_SYMBOLS[(5, 9, True, 2)], None if tr is None else round(tr * bs / 256.0),
+                                    None if tr is None else src + f"; measured at batch 256 and scaled by {bs}/256 (the kernel's traffic is linear in the batch)")
+                roof["how"] = (f"one eager batch of {bs} after the timed region (the timed candidates replay hipGraphs, which carry no events), "
+                               f"{eager_s * 1e3:.0f} ms with per-launch events")
+        chk = check_output(sample, u8)
     logger.log = _log
     if rank != 0:
         return None
@@ -658,9 +703,11 @@ def run_candidate(args, ctx):
         "fid_values": [round(float(f), 4) for f in fids],
         "roofline": roof, "output_check": chk, "parity": parity_block("adm64", args.torso), "hbm_peak_gb": hbm_peak_gb(dev),
     }
+    if dumped:
+        out["outputs"] = dumped
     if rankinfo:
         out.update(rankinfo)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline()
         v = out["cpu_baseline"]["value"]
         out["cpu_baseline"]["note"] = (f"sampling only, unguided, BASELINE config 1 (images/sec); a {nimg}-image guided candidate at that rate "
@@ -726,6 +773,7 @@ def run_population(args, ctx):
     if not all(np.isfinite(f["fids"]).all() for f in flushes):
         print(json.dumps({"error": "bench.py --workload population: non-finite FID"}), flush=True)
         raise SystemExit(3)
+    dumped = write_outputs(args.dump_outputs, {"fids": np.array(fl["fids"], dtype=np.float64)}) if args.dump_outputs and rank == 0 else None
     mine = {"assigned": int(np.mean([f["assigned"] for f in flushes])), "assigned_cost": int(np.mean([f["assigned_cost"] for f in flushes])),
             "evaluate_s": round(float(np.mean([f["evaluate_s"] for f in flushes])), 3)}
     rankinfo = gather_ranks(ctx, elapsed_local, extra=mine)
@@ -757,6 +805,8 @@ def run_population(args, ctx):
     }
     if not ctx.dist_on:
         out["per_rank"] = [mine]
+    if dumped:
+        out["outputs"] = dumped
     if rankinfo:
         out.update(rankinfo)
     return out
@@ -824,6 +874,7 @@ def run_images(args, ctx):
         fid_acc = ActivationAccumulator(2048, dev)
 
     MB = max(1, args.merge_batches)   # reference batches per pass over the networks (bitwise the same images: sample_batches)
+    last = {}                         # what the latest step returned: --dump-outputs writes the last timed step's
 
     def one_step(step_idx, return_float=False):
         # deterministic, layout-independent seeding per (step, rank)
@@ -832,17 +883,18 @@ def run_images(args, ctx):
             if fid_net is not None:
                 for u8 in u8s:
                     fid_acc.add_from(fid_net.features, u8)
+            last["images"] = u8s
             return u8s[0]
-        res = ev.sample_batch(B, seed=(1000003 * step_idx + rank), return_float=return_float)
-        u8 = res[0] if return_float else res
+        u8, sample = ev.sample_batch(B, seed=(1000003 * step_idx + rank), return_float=True)
         if fid_net is not None:
             fid_acc.add_from(fid_net.features, u8)
-        return res
+        last["images"], last["sample"] = [u8], sample
+        return (u8, sample) if return_float else u8
 
     for w in range(args.warmup):
         one_step(-1 - w)
     torch.cuda.synchronize()
-    events_live = not args.no_kernel_events and not args.graph
+    events_live = args.full and not args.no_kernel_events and not args.graph
     if events_live:
         ops.CONV_PROFILE = []
         # HIP events only around the dominant kernel's launches (all conv launches with --conv-breakdown): a pair of
@@ -850,8 +902,14 @@ def run_images(args, ctx):
         ops.CONV_PROFILE_KEY = None if args.conv_breakdown else dom_key
     elapsed_local, elapsed = timed(ctx, one_step, args.steps)
     prof_timed, ops.CONV_PROFILE = ops.CONV_PROFILE, None
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before anything else runs: graph replays reuse their output buffers
+        arrays = {"images": torch.cat(last["images"], 0)}
+        if "sample" in last:
+            arrays["sample"] = last["sample"]
+        dumped = write_outputs(args.dump_outputs, arrays)
     fid_pooled = None
-    if fid_acc is not None and w256:
+    if args.full and fid_acc is not None and w256:
         # BASELINE config 5's pooled-FID stage: ONE all-gather of the packed float64 (n, sum a, sum a a^T) over the ranks (RCCL over
         # xGMI; skipped without a process group) + the Frechet distance on the device; timed on its own, outside the sampling steps
         ref = synthetic_ref_stats(2048)
@@ -867,7 +925,7 @@ def run_images(args, ctx):
     roof = None
     eager_s = None
     prof = prof_timed
-    if args.graph and not args.no_kernel_events:   # the replayed launches carry no events: one eager batch for the roofline
+    if args.full and args.graph and not args.no_kernel_events:   # the replayed launches carry no events: one eager batch for the roofline
         model.enable_graph(False)
         if classifier is not None:
             classifier.enable_graph(False)
@@ -930,10 +988,12 @@ def run_images(args, ctx):
                                     "avg_launch_us": round(ims * 1e3 / len(iso), 2), "launches": len(iso),
                                     "how": "one untimed batch after the timed region, networks in sequence on one stream"}
     ops.CONV_PROFILE = None
-    # what the timed loop produces, verified on one more batch outside the timed region
-    u8c, samplec = one_step(args.steps + 2, return_float=True)
-    torch.cuda.synchronize()
-    chk = check_output(samplec, u8c)
+    chk = None
+    if args.full:
+        # what the timed loop produces, verified on one more batch outside the timed region
+        u8c, samplec = one_step(args.steps + 2, return_float=True)
+        torch.cuda.synchronize()
+        chk = check_output(samplec, u8c)
     if rank != 0:
         return None
     imgs = world * B * MB * args.steps
@@ -981,9 +1041,11 @@ def run_images(args, ctx):
         out["graphs"] = model.graph_report() if hasattr(model, "graph_report") else None
     if fid_pooled:
         out["fid_pooled"] = fid_pooled
+    if dumped:
+        out["outputs"] = dumped
     if rankinfo:
         out.update(rankinfo)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline()
         if w256 or w128:
             out["cpu_baseline"]["note"] = (f"timed on BASELINE config 1 (64x64): one {size}x{size} evaluation is {gflop_unet:.1f} GFLOP, "
@@ -1050,9 +1112,16 @@ def main():
                          "star's 256x256 line; + --skip-layers / --with-fid / --class-cond = configs[4]); sd = configs[3] (Stable-Diffusion v1 latent "
                          "UNet, 6 searched DDIM steps, classifier-free guidance 7.5); candidate = one whole get_cand_fid per step; "
                          "population = configs[2]: one EA epoch of 64 ADM-G-128 10-step candidates, LPT-sharded over the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the roofline (per-launch HIP events), the untimed "
+                         "output-check batch, the pooled-FID stage's timing, the CPU baseline and, with --workload auto, the secondary "
+                         "workloads; off by default, so that a plain run only sets up, warms up and times its steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32, FIDs float64; at most "
+                         "60 MiB in all, a larger output as a fixed seeded sample of its elements); rank 0's shard")
     ap.add_argument("--secondary", default=None,
                     help=f"comma list of workloads run after the headline in the same process and attached to its line as `secondary` "
-                         f"(default with --workload auto: {SECONDARY_DEFAULT}; 'none' to skip)")
+                         f"(default with --workload auto and --full: {SECONDARY_DEFAULT}; 'none' to skip)")
     ap.add_argument("--skip-layers", default=None,
                     help="dynamic-UNet workloads (adm256): one layer-skip list per step, as JSON ('[[1,5],[],...]'), or 'auto' = "
                          "10 %% of the layers per step, seeded (the shape `--max_prun 0.1` candidates have)")
@@ -1087,7 +1156,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--conv-breakdown", action="store_true",
-                    help="print per-shape conv time / TFLOP/s (HIP events) to stderr")
+                    help="with --full: print per-shape conv time / TFLOP/s (HIP events) to stderr")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1102,6 +1171,8 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
     if args.steps is None:
         args.steps = 1 if args.workload == "population" else 3
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     ndev = torch.cuda.device_count()
     if args.dist_backend == "nccl" and world > 1 and ndev < local_world:
         raise SystemExit(f"bench.py: {local_world} ranks on this node but {ndev} visible GPU(s): RCCL takes one rank per device "
@@ -1133,7 +1204,7 @@ def main():
         return RUNNERS.get(a.workload, run_images)(a, ctx)
 
     line = run(args)
-    names = args.secondary if args.secondary is not None else (SECONDARY_DEFAULT if args.workload == "auto" else "none")
+    names = args.secondary if args.secondary is not None else (SECONDARY_DEFAULT if args.workload == "auto" and args.full else "none")
     names = [] if names in ("none", "") else [n_ for n_ in names.split(",") if n_]
     if names:
         import gc
@@ -1145,6 +1216,7 @@ def main():
             sub.workload, sub.batch, sub.images, sub.merge_batches, sub.graph, sub.with_fid = name, None, None, 0, False, False
             sub.skip_layers, sub.sampler_steps, sub.class_cond, sub.conv_breakdown, sub.no_cpu_baseline = None, 0, False, False, True
             sub.steps, sub.warmup = SECONDARY_STEPS.get(name, (2, 1))
+            sub.dump_outputs = None   # the files hold the headline's outputs
             if name == "adm128":
                 # what a search on this model launches: get_cand_fid merges the reference's memory-driven batches of 32 up to the
                 # 128-image pass cap (evaluate.merge_policy; bitwise the same images) -- the line's workload string says so;

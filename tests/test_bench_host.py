@@ -34,6 +34,27 @@ def test_check_output_passes_images_and_rejects_nan_or_constant_batches(capsys):
         bench.check_output(torch.zeros(4, 3, 8, 8), torch.full((4, 8, 8, 3), 127, dtype=torch.uint8))
 
 
+def test_write_outputs_keeps_float_types_and_samples_within_the_budget(tmp_path):
+    """--dump-outputs: uint8 / fp32 arrays as float32, float64 as float64; over the byte budget every array keeps its share as a
+    seeded sample of its elements -- the same elements in every run."""
+    import numpy as np
+    g = torch.Generator().manual_seed(0)
+    u8 = torch.randint(0, 256, (4, 8, 8, 3), generator=g, dtype=torch.uint8)
+    x = torch.randn(4, 3, 8, 8, generator=g)
+    d = bench.write_outputs(str(tmp_path / "a"), {"images": u8, "sample": x, "fid": np.array([1.25])})
+    assert d["images"] == {"shape": [4, 8, 8, 3], "dtype": "float32", "sampled_elements": None}
+    assert np.array_equal(np.load(tmp_path / "a" / "images.npy"), u8.numpy().astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "sample.npy"), x.numpy())
+    assert np.load(tmp_path / "a" / "fid.npy").dtype == np.float64 and d["fid"]["dtype"] == "float64"
+    for tag in ("b", "c"):
+        d = bench.write_outputs(str(tmp_path / tag), {"images": u8, "sample": x}, budget=1024)
+        assert d["images"]["sampled_elements"] == d["sample"]["sampled_elements"] == 128
+    got = {n: [np.load(tmp_path / t / f"{n}.npy") for t in ("b", "c")] for n in ("images", "sample")}
+    assert sum(a[0].nbytes for a in got.values()) <= 1024
+    assert all(np.array_equal(a, b) and a.shape == (128,) for a, b in got.values())
+    assert np.isin(got["sample"][0], x.numpy().reshape(-1)).all()
+
+
 def test_pin_rank_gives_each_local_rank_its_own_cpu_slice():
     assert bench.pin_rank(0, 1) is None      # one rank: the process is left alone
     if not hasattr(os, "sched_getaffinity") or len(os.sched_getaffinity(0)) < 2:

@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -18,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _two_rank_cmd(form, workload, extra):
     """The two launch forms the contract allows: the ranks started by torchrun, or a bare `python bench.py --gpus 2` that
     starts them itself (WORLD_SIZE unset: the driver's own command shape)."""
-    tail = ["--gpus", "2", "--dist-backend", "gloo", "--workload", workload, "--no-cpu-baseline", "--no-kernel-events"] + extra
+    tail = ["--gpus", "2", "--dist-backend", "gloo", "--workload", workload, "--full", "--no-cpu-baseline", "--no-kernel-events"] + extra
     if form == "self":
         return [sys.executable, os.path.join(ROOT, "bench.py")] + tail
     sock = socket.socket(); sock.bind(("127.0.0.1", 0)); port = sock.getsockname()[1]; sock.close()
@@ -91,7 +92,7 @@ def test_bench_single_rank_line_with_the_fid_stage_and_roofline():
     Inception + Gram stage inside the step (config.fid_stage_in_step)."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline",
            "--with-fid", "--secondary", "adm256"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, OMP_NUM_THREADS="4"), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -118,13 +119,43 @@ def test_bench_single_rank_line_with_the_fid_stage_and_roofline():
     assert chk["finite"] is True and chk["u8_shape"] == [8, 64, 64, 3] and chk["u8_std"] > 0
 
 
+def test_plain_line_times_only_its_steps_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain run (no --full): exactly --steps timed steps and the headline keys, none of the extra measurements; --dump-outputs
+    writes the last timed step's uint8 images and fp32 sample, bitwise the same in two runs with the same arguments."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    outs = []
+    for tag in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+               "--dump-outputs", str(tmp_path / tag)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, OMP_NUM_THREADS="4"), cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "images/sec" and out["higher_is_better"] is True
+    assert out["dtype"] == "bf16" and "guided" in out["config"]["workload"] and "UNGUIDED" not in out["config"]["workload"]
+    assert abs(out["value"] - 8 / (out["ms_per_step"] * 1e-3)) <= 0.02 * out["value"]
+    assert out["roofline"] is None and out["output_check"] is None and "cpu_baseline" not in out and "secondary" not in out
+    assert out["outputs"]["images"] == {"shape": [8, 64, 64, 3], "dtype": "float32", "sampled_elements": None}
+    assert out["outputs"]["sample"] == {"shape": [8, 3, 64, 64], "dtype": "float32", "sampled_elements": None}
+    for name in ("images", "sample"):
+        a, b = (np.load(tmp_path / t / f"{name}.npy") for t in ("a", "b"))
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+    imgs, s = np.load(tmp_path / "a" / "images.npy"), np.load(tmp_path / "a" / "sample.npy")
+    assert np.isfinite(s).all() and imgs.std() > 0 and np.array_equal(imgs, np.round(imgs))
+    # both arrays come from the same step: the images are the sample's uint8 pack
+    assert np.abs(imgs - ((s.transpose(0, 2, 3, 1) + 1) * 127.5).clip(0, 255)).max() <= 1.0
+
+
 def test_bench_candidate_workload_line():
     """--workload candidate: one whole get_cand_fid per step (here 24 images in batches of 8) -> candidates/hour with the
     reference's reset / sample / fid_time split, finite FIDs, the output check and the roofline of one eager batch."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "candidate", "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--images", "24", "--no-cpu-baseline"]
+           "--images", "24", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, OMP_NUM_THREADS="4"), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -147,7 +178,7 @@ def test_bench_merged_batches_line():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "unguided", "--steps", "2", "--warmup", "1", "--batch", "4",
-           "--merge-batches", "3", "--no-cpu-baseline", "--no-kernel-events"]
+           "--merge-batches", "3", "--full", "--no-cpu-baseline", "--no-kernel-events"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, OMP_NUM_THREADS="4"), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

@@ -27,7 +27,7 @@ def _env(**kw):
 
 
 def _bench(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--dist-backend", "nccl", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--dist-backend", "nccl", "--full", "--no-cpu-baseline",
            "--no-kernel-events"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

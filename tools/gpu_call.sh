@@ -6,7 +6,7 @@
 #
 # steps (every step writes under gpurun_out/<tag>/):
 #   tests [pytest args...]              python -m pytest -x -q -m gpu <args>            -> pytest_<n>.log
-#   bench <name> [bench.py args...]     one bench.py line                                -> bench_<name>.json(.err)
+#   bench <name> [bench.py args...]     one `bench.py --full` line                       -> bench_<name>.json(.err)
 #   ab <ENVVAR> <v1,v2,...> <rounds> [bench.py args...]
 #                                       same-box A/B of an environment switch: `rounds` interleaved passes over the values
 #                                       ("-" = unset)                                    -> ab_<ENVVAR>_<value>_<round>.json
@@ -30,7 +30,7 @@ run_step() {
       tail -2 "$OUT/pytest_$n.log" ;;
     bench)
       local name=$1; shift
-      python bench.py "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || { tail -20 "$OUT/bench_$name.err"; return 1; }
+      python bench.py --full "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" || { tail -20 "$OUT/bench_$name.err"; return 1; }
       python - "$OUT/bench_$name.json" <<'PY'
 import json, sys
 l = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
