@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("ADM_HIP_LIB") or os.path.join(_HERE, "libadm_hip.so")
 # the same kernels built with IEEE half as the 16-bit element type (csrc/adm_common.h, -DADM_ACT_F16): the reference's own
 # torso precision (use_fp16=True); selected per tensor dtype by ops.py, per model by `torso="fp16"` / ADM_TORSO=fp16
 LIB_PATH_F16 = os.environ.get("ADM_HIP_LIB_F16") or os.path.join(_HERE, "libadm_hip_f16.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class AdmError(RuntimeError):
@@ -117,6 +117,8 @@ SIGNATURES = {
     "adm_vec_act": (_I, [_P, _P, _P, C.c_int64, _I, _P]),
     "adm_vec_gn": (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _P]),
     "adm_vec_gn_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
+    "adm_knn_smallest": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _I, _P]),
+    "adm_knn_cover": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
 }
 
 _libs = {}

@@ -105,6 +105,7 @@ class InceptionV3:
             else:
                 self._params[k] = torch.zeros(shp)
         self._packed: Dict[str, tuple] = {}
+        self.fc_weight = None   # [classes, 2048] fp32 of a full checkpoint: the Inception Score's softmax head (evaluator.py)
 
     # --- nn.Module-like surface -------------------------------------------------
     def eval(self):
@@ -119,6 +120,8 @@ class InceptionV3:
     def to(self, device):
         for k in self._params:
             self._params[k] = self._params[k].to(device)
+        if self.fc_weight is not None:
+            self.fc_weight = self.fc_weight.to(device)
         self._packed = {}
         return self
 
@@ -132,7 +135,9 @@ class InceptionV3:
     def load_state_dict(self, sd, strict: bool = True):
         """Takes torchvision / pt_inception names (``Mixed_5b.branch1x1.conv.weight``) or pytorch_fid's own
         (``blocks.2.0.branch1x1.conv.weight``); the classifier head (``fc.*``), ``AuxLogits.*`` and
-        ``num_batches_tracked`` entries of a full checkpoint are not part of the extractor and are skipped."""
+        ``num_batches_tracked`` entries of a full checkpoint are not part of the extractor and are skipped -- except
+        ``fc.weight`` [classes, 2048], kept as ``fc_weight`` for the Inception Score: the reference's softmax graph multiplies
+        pool3 by ``softmax/logits/MatMul``'s weight with no bias (evaluations/evaluator.py:674-685)."""
         renamed = {}
         for k, v in sd.items():
             if k.startswith("blocks."):
@@ -140,6 +145,9 @@ class InceptionV3:
                 if int(j) >= len(_FID_BLOCKS[int(i)]):
                     continue
                 k = _FID_BLOCKS[int(i)][int(j)] + "." + rest
+            if k == "fc.weight" and tuple(v.shape)[1:] == (2048,):
+                self.fc_weight = torch.as_tensor(v).detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
+                continue
             if k.startswith(("fc.", "AuxLogits.")) or k.endswith("num_batches_tracked"):
                 continue
             renamed[k] = v
@@ -239,8 +247,9 @@ class InceptionV3:
         self._bc(n + ".branch_pool", ops.pool2d(x, 3, 1, 1, pool_mode), out=y[..., 1856:2048])
         return y
 
-    def _body(self, x, upto: int):
-        """x: prepared [N,299,299,32] 16-bit NHWC -> block outputs 0..upto (NHWC 16-bit; block 3: fp32 [N, 2048])."""
+    def _body(self, x, upto: int, spatial: List[torch.Tensor] = None):
+        """x: prepared [N,299,299,32] 16-bit NHWC -> block outputs 0..upto (NHWC 16-bit; block 3: fp32 [N, 2048]).
+        `spatial` (a list): receives the sFID tap, channels 0..6 of Mixed_6d as fp32 [N, 17 * 17 * 7] in (h, w, c) order."""
         outs = []
         x = self._bc("Conv2d_1a_3x3", x, stride=2)
         x = self._bc("Conv2d_2a_3x3", x)
@@ -259,6 +268,8 @@ class InceptionV3:
             x = self._mixed_b("Mixed_6a", x)
             for n in ("Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e"):
                 x = self._mixed_c(n, x)
+                if n == "Mixed_6d" and spatial is not None:
+                    spatial.append(x[..., :SPATIAL_CHANNELS].float().reshape(x.shape[0], -1))
             outs.append(x)
         if upto >= 3:
             x = self._mixed_d("Mixed_7a", x)
@@ -306,6 +317,29 @@ class InceptionV3:
             x = ops.resize_bilinear(u8_nhwc[i:i + self.CHUNK], 299, 299, 32, "u8_nhwc", half, scale, shift, self.compute_dtype)
             outs.append(self._body(x, 3)[3])
         return torch.cat(outs, 0)
+
+    def features_all(self, u8_nhwc: torch.Tensor, mode: str = "tf1") -> Tuple[torch.Tensor, torch.Tensor]:
+        """(pool3 fp32 [B, 2048], spatial fp32 [B, 2023]) of one pass: the two tensors the ADM evaluator reads from the frozen
+        graph (evaluations/evaluator.py:26, 665-671: ``pool_3:0`` and ``mixed_6/conv:0[..., :7]``).  ``mixed_6`` is Mixed_6d
+        and its ``conv`` node is the block's branch1x1 after BatchNorm + ReLU, i.e. channels 0..6 of Mixed_6d's output
+        (17 x 17, flattened (h, w, c) like the graph's NHWC reshape) -- documented, not pinned.
+        pool3 is bitwise ``features()``: the same launches in the same order."""
+        self._prepare()
+        if u8_nhwc.dtype != torch.uint8 or u8_nhwc.dim() != 4 or u8_nhwc.shape[3] != 3:
+            raise AdmError(f"InceptionV3.features_all: expected uint8 [N, H, W, 3], got {u8_nhwc.dtype} {tuple(u8_nhwc.shape)}")
+        if mode not in ("tf1", "pt"):
+            raise ValueError(f"mode must be 'tf1' or 'pt', got {mode!r}")
+        u8_nhwc = u8_nhwc.to(self.device).contiguous()
+        half, scale, shift = (False, 1.0 / 128.0, -1.0) if mode == "tf1" else (True, 2.0 / 255.0, -1.0)
+        pools, spatial = [], []
+        for i in range(0, u8_nhwc.shape[0], self.CHUNK):
+            x = ops.resize_bilinear(u8_nhwc[i:i + self.CHUNK], 299, 299, 32, "u8_nhwc", half, scale, shift, self.compute_dtype)
+            pools.append(self._body(x, 3, spatial)[3])
+        return torch.cat(pools, 0), torch.cat(spatial, 0)
+
+
+SPATIAL_CHANNELS = 7     # evaluator.py:670 spatial[..., :7]
+SPATIAL_DIM = 17 * 17 * SPATIAL_CHANNELS   # 2023
 
 
 class Evaluator_v1:

@@ -29,10 +29,11 @@
 extern "C" {
 #endif
 
-#define ADM_ABI_VERSION 9   /* 2: adm_conv_args gained in_up / res_up; 3: ksplit / ws; 4: the Inception layer entry points; 5: up_phase; 6: geglu;
+#define ADM_ABI_VERSION 10  /* 2: adm_conv_args gained in_up / res_up; 3: ksplit / ws; 4: the Inception layer entry points; 5: up_phase; 6: geglu;
                                7: adm_gn_finalize_add gained stats, adm_gn_bwd_finalize gained add / add_stride; the classifier's other heads;
                                8: adm_conv_args gained fold0 / fold1 / fc0 / fc1;
-                               9: adm_conv_args gained out_scale; CU-partitioned streams (adm_stream_create_cumask / _set_cus / _destroy) */
+                               9: adm_conv_args gained out_scale; CU-partitioned streams (adm_stream_create_cumask / _set_cus / _destroy);
+                               10: the evaluation suite's k-NN entry points (adm_knn_smallest / adm_knn_cover) */
 
 #define ADM_E_ARG      (-1)  /* bad pointer / size / flag combination          */
 #define ADM_E_SHAPE    (-2)  /* shape not supported by the gfx950 tiling       */
@@ -393,6 +394,22 @@ int adm_bcast_add(const float* v, int v_stride, float scale, const adm_bf16* add
 int adm_vec_act(const float* x, const float* dy, float* out, int64_t items, int mode, void* stream);
 int adm_vec_gn(const float* x, const float* gamma, const float* beta, float* y, float* stats, int n, int c, float eps, void* stream);
 int adm_vec_gn_bwd(const float* x, const float* gamma, const float* stats, const float* dz, float* dx, int n, int c, void* stream);
+
+/* ---------------------------------------------------------------- k-NN precision / recall (K13, the ADM evaluation suite)
+ * ManifoldEstimator of evaluations/evaluator.py (:319-352 manifold_radii, :396-430 evaluate_pr, :458-500 DistanceBlock) as one
+ * fp16 GEMM per call with the selection / comparison in its epilogue (no distance matrix in memory).  Features are IEEE half
+ * rows [n][d] (the reference's tf.float16 cast, in both builds of the library), d % 64 == 0, 16-byte aligned; norms are fp32
+ * [n] squared norms of the SAME half rows; dist(i, j) = max(|p_i|^2 + |x_j|^2 - 2 p_i . x_j, 0) with an fp32 dot product.
+ *   adm_knn_smallest  out[c][0..kk) = the kk smallest dist(q_c, x_j) over all j < nx, ascending (x may be q itself: then the
+ *                     point's own ~0 distance is one of them, as in the reference); 1 <= kk <= 8, nx >= kk.  The rows of x
+ *                     are split over `splits` blocks per 128 queries (1 <= splits <= ceil(nx / 128)); splits > 1 needs the
+ *                     caller's workspace ws fp32 [splits][nq][kk].  Bitwise independent of `splits`.
+ *   adm_knn_cover     a_in[i][k] = 1 if dist(a_i, b_j) <= rb[j][k] for some j; b_in[j][k] = 1 if dist(a_i, b_j) <= ra[i][k] for
+ *                     some i; radii fp32 [n][K], 1 <= K <= 8; flags uint8 [n][K], ZEROED BY THE CALLER (only 1s are stored). */
+int adm_knn_smallest(const void* q, int nq, const float* qnorm, const void* x, int nx, const float* xnorm, int d, int kk,
+                     float* out, float* ws, int splits, void* stream);
+int adm_knn_cover(const void* a, int na, const float* anorm, const float* ra, const void* b, int nb, const float* bnorm,
+                  const float* rb, int d, int K, uint8_t* a_in, uint8_t* b_in, void* stream);
 
 #ifdef __cplusplus
 }
