@@ -1710,6 +1710,7 @@ extern "C" int adm_conv(const adm_conv_args* a, void* stream) {
                                    a->ksplit <= 1 && !a->up_phase && a->h >= 16 && a->w >= 16 && (a->h * a->w) % 256 == 0 && a->cout % 8 == 0),
               ADM_E_ARG, "adm_conv: prologue 3 (GroupNorm-backward epilogue) needs res (= x), out_stats, a 3x3 conv with bf16 output on a map >= 16x16");
   ADM_REQUIRE(a->out_mode == 0 || a->out_mode == 1, ADM_E_ARG, "adm_conv: out_mode must be 0 or 1");
+  ADM_REQUIRE(a->out_scale == 0.f || a->out_mode == 1, ADM_E_ARG, "adm_conv: out_scale needs the fp32 NCHW output (out_mode 1)");
   ADM_REQUIRE((a->prologue == 0) || (a->aff_a && a->aff_b), ADM_E_ARG, "adm_conv: prologue needs aff_a/aff_b");
   ADM_REQUIRE(a->out_mode == 0 || !a->res, ADM_E_ARG, "adm_conv: residual only with bf16 NHWC output");
   ADM_REQUIRE(a->out_mode == 1 || a->cout % 8 == 0, ADM_E_SHAPE, "adm_conv: bf16 NHWC output needs cout %% 8 == 0");

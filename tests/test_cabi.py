@@ -52,6 +52,22 @@ def test_argument_errors_surface_as_exceptions_without_a_gpu():
     assert lib.adm_stream_create_cumask(empty, 8, C.byref(out)) == -1 and b"empty mask" in lib.adm_last_error()
 
 
+@pytest.mark.parametrize("kind", ["bf16", "f16"])
+def test_conv_rejects_out_scale_without_the_fp32_output(kind):
+    """out_scale is applied by the fp32 NCHW epilogue only: the library refuses it with a 16-bit output instead of ignoring it
+    (argument checks run before any pointer is read, so host placeholders stand in for the device buffers).  The shape is invalid
+    on purpose (n = 0, c0 = 31): should the out_scale check ever move or go, a later shape check still refuses the call before
+    anything launches."""
+    import ctypes as C
+    lib = _lib.load(kind)
+    a = _lib.ConvArgs()
+    a.in0 = a.w_packed = a.bias = a.out = 0x1000
+    a.n, a.h, a.w, a.c0, a.cout, a.taps = 0, 16, 16, 31, 32, 9
+    a.out_mode, a.out_scale = 0, 2.0 ** -10
+    assert lib.adm_conv(C.byref(a), None) == -1   # ADM_E_ARG
+    assert b"out_scale" in lib.adm_last_error() and b"out_mode" in lib.adm_last_error()
+
+
 def test_header_is_plain_c_and_links_from_a_c_client(tmp_path):
     """include/adm_hip.h compiles as C99 (-pedantic: no C++isms, no torch types) and a C program links against the library."""
     import shutil

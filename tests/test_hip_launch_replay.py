@@ -1,0 +1,521 @@
+"""Every (kernel, shape, flags) launch the shipped models make, replayed against float64 in both torsos.
+
+The models (built as tests/test_hip_fullsize.py builds them; the weights' values do not matter, only the launch list does) run
+eagerly at the batches bench.py uses and at batch 1-2, in the bf16 and the fp16 torso, under tests/launch_replay.Recorder.  Each
+distinct record is then launched again through the same C entry point with fresh seeded operands and compared element by element
+with the float64 restatement of tests/launch_replay.py, within the per-element bounds derived there (and tested on the host by
+tests/test_launch_replay_host.py).  Large maps are compared at the corners of every 16x16 (8x8) output tile of every image plus
+seeded random pixels, all channels.  A coverage guard fails if a family of launches the models are known to reach is missing.
+
+Also here: GroupNorm statistics at a large |mean| / std (fused conv statistics, the `add` form, adm_gn_partial).
+"""
+import ctypes as C
+import time
+
+import pytest
+import torch
+
+import launch_replay as lr
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module")
+def ops():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from autodiffusion_amd import ops as _ops
+    return _ops
+
+
+def _inputs(size, n, classes, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(n, 3, size, size, generator=g).to(DEV)
+    t = torch.randint(0, 1000, (n,), generator=g).to(DEV)
+    y = torch.randint(0, 1000, (n,), generator=g).to(DEV) if classes else None
+    return x, t, y
+
+
+def _run_models(torso):
+    """Every shipped model at bench.py's batch and at batch 1-2, in one torso."""
+    from test_hip_fullsize import adm64, clf, load_filled
+    from bench import adm128_flags, adm256_flags
+    from autodiffusion_amd.script_util import create_model_and_diffusion
+    with torch.no_grad():
+        m, _ = adm64()
+        m.set_torso(torso)
+        for n in (256, 2):
+            m(*_inputs(64, n, True, 1))
+        del m
+    c = clf(64, 4).set_torso(torso)
+    for n in (256, 2):
+        c.log_prob_grad(*_inputs(64, n, True, 2), 1.0)
+    del c
+    with torch.no_grad():
+        m, _ = create_model_and_diffusion(**adm128_flags())
+        load_filled(m).set_torso(torso)
+        for n in (32, 2):
+            m(*_inputs(128, n, True, 3))
+        del m
+    c = clf(128, 2).set_torso(torso)
+    for n in (32, 2):
+        c.log_prob_grad(*_inputs(128, n, True, 4), 1.0)
+    del c
+    with torch.no_grad():
+        for cc in (True, False):
+            flags = adm256_flags()
+            flags["class_cond"] = cc     # class-conditional ADM-256 (BASELINE configs[4] as written) and LSUN-256
+            m, _ = create_model_and_diffusion(**flags)
+            load_filled(m).set_torso(torso)
+            skip = list(range(1, m.layer_num, 3))
+            for n in (64, 1):
+                x, t, y = _inputs(256, n, cc, 5)
+                for sk in ([], skip):
+                    m(x, t, y, skip_layer=sk)
+            del m
+            torch.cuda.empty_cache()
+        from autodiffusion_amd.sd_arch import SD_V1, sd_unet_plan
+        from oracle.fill import fill_state_dict
+        from test_hip_sd import _model
+        plan = sd_unet_plan(**SD_V1)
+        m = _model(plan, {k: torch.from_numpy(v) for k, v in fill_state_dict(plan.param_shapes()).items()})
+        m.set_torso(torso)
+        for splitk in (False, True):
+            m.enable_splitk(splitk)
+            for n in (6, 1):
+                g = torch.Generator().manual_seed(6)
+                m(torch.randn(n, 4, 64, 64, generator=g).to(DEV), torch.randint(0, 1000, (n,), generator=g).to(DEV),
+                  torch.randn(n, 77, 768, generator=g).to(DEV))
+        del m
+    torch.cuda.empty_cache()
+
+
+@pytest.fixture(scope="module")
+def recorded(ops):
+    t0 = time.time()
+    with pytest.MonkeyPatch.context() as mp:
+        rec = lr.Recorder(mp)
+        for torso in ("bf16", "fp16"):
+            _run_models(torso)
+    torch.cuda.synchronize()
+    print(f"\nrecorded {sum(rec.counts.values())} calls ({rec.counts}), {len(rec.records)} distinct, in {time.time() - t0:.0f} s")
+    return rec
+
+
+# ------------------------------------------------------------------ coverage guard
+def test_recorded_launches_cover_every_known_family(recorded):
+    fams = set()
+    for r in recorded.records:
+        fams |= lr.families(r)
+    for kind in ("bf16", "f16"):
+        have = sorted(f for k, f in fams if k == kind)
+        print(f"{kind}: {len([r for r in recorded.records if r[1] == kind])} distinct launches; families {have}")
+    missing = [(k, f) for k in ("bf16", "f16") for f in lr.REQUIRED_FAMILIES if (k, f) not in fams
+               and not (k == "bf16" and f == "out_mode 1 + out_scale")]   # the 2^10 gradient scale is the fp16 classifier's only
+    assert not missing, f"the models no longer reach (or the recorder missed) {missing}"
+    # every kind of record is replayed below: a new kind must get a restatement, not be dropped
+    assert {r[0] for r in recorded.records} <= REPLAYED, {r[0] for r in recorded.records} - REPLAYED
+
+
+REPLAYED = {"conv", "attention", "attention_cross", "attention_bwd", "gn_bwd", "gn_affine"}
+
+
+# ------------------------------------------------------------------ conv replay
+def _conv_operands(ops, d, T, seed):
+    torch.manual_seed(seed)
+    n, h, w, c0, c1, cout, taps = d["n"], d["h"], d["w"], d["c0"], d["c1"], d["cout"], d["taps"]
+    up = d["up_phase"]
+    if up not in (0, 5) or d["prologue"] not in (0, 1, 2, 3):
+        raise NotImplementedError(f"the restatement does not express up_phase {up} / prologue {d['prologue']}")
+    hi, wi = (h // 2, w // 2) if d["in_up"] else (h, w)
+    ho, wo = (2 * h, 2 * w) if up else (h, w)
+    cin, k = c0 + c1, (3 if taps == 9 else 1)
+    t = {"x0": torch.randn(n, hi, wi, c0, device=DEV).to(T), "x1": torch.randn(n, hi, wi, c1, device=DEV).to(T) if d["has_in1"] else None}
+    w32 = torch.randn(cout, cin, k, k, device=DEV) * (cin * taps) ** -0.5
+    bias = 0.1 * torch.randn(cout, device=DEV) if d["prologue"] != 3 else torch.zeros(cout, device=DEV)  # backward-data convs: no bias
+    w32p = None
+    if up:
+        packed, t["w"] = ops.pack_conv_weight_up(w32, T), lr.round_t(ops.up_phase_weights(w32), T)
+    elif d["geglu"]:
+        wi_, bias = ops.geglu_interleave(w32[:, :, 0, 0], bias)
+        packed, t["w"] = ops.pack_conv_weight(wi_[:, :, None, None], T), lr.round_t(wi_[:, :, None, None], T)
+    else:
+        packed, t["w"] = ops.pack_conv_weight(w32, T), lr.round_t(w32, T)
+        if d["has_w_packed32"]:
+            w32p = ops.pack_conv_weight32(w32, T)
+    if d["has_fold0"]:
+        fc = d["fc0"] + d["fc1"]
+        w1 = torch.randn(cout, fc, device=DEV) * fc ** -0.5
+        packed = ops.fold_weights(packed, ops.pack_conv_weight(w1, T))
+        t["w1"] = lr.round_t(w1, T)
+        t["f0"] = torch.randn(n, h, w, d["fc0"], device=DEV).to(T)
+        t["f1"] = torch.randn(n, h, w, d["fc1"], device=DEV).to(T) if d["has_fold1"] else None
+    t["bias"] = bias
+    if d["prologue"] in (1, 2):
+        t["a"], t["b"] = 1 + 0.2 * torch.randn(n, cin, device=DEV), 0.2 * torch.randn(n, cin, device=DEV)
+    if d["prologue"] == 3:
+        t["gnb_a"], t["gnb_b"] = 1 + 0.2 * torch.randn(n, cout, device=DEV), 0.2 * torch.randn(n, cout, device=DEV)
+    if d["has_res"]:
+        t["res"] = torch.randn(n, h // 2 if d["res_up"] else ho, w // 2 if d["res_up"] else wo, cout, device=DEV).to(T)
+    if d["out_mode"] == 1:
+        out = torch.empty(n, cout, h, w, device=DEV)
+    else:
+        out = torch.empty(n, ho, wo, cout // 2 if d["geglu"] else cout, device=DEV, dtype=T)
+    return t, packed, w32p, out
+
+
+def _launch_conv(lib, orig, d, t, packed, w32p, out):
+    from autodiffusion_amd._lib import ConvArgs, check
+    a = ConvArgs()
+    for name, _ in ConvArgs._fields_:
+        if name in d:
+            setattr(a, name, d[name])
+    keep = [packed, w32p]
+    a.in0, a.in1 = t["x0"].data_ptr(), (t["x1"].data_ptr() if t["x1"] is not None else None)
+    a.w_packed, a.bias, a.out = packed.data_ptr(), t["bias"].data_ptr(), out.data_ptr()
+    a.w_packed32 = w32p.data_ptr() if w32p is not None else None
+    if "a" in t:
+        a.aff_a, a.aff_b = t["a"].data_ptr(), t["b"].data_ptr()
+    if "gnb_a" in t:
+        a.aff_a, a.aff_b = t["gnb_a"].data_ptr(), t["gnb_b"].data_ptr()
+    a.res = t["res"].data_ptr() if "res" in t else None
+    if d["has_fold0"]:
+        a.fold0, a.fold1 = t["f0"].data_ptr(), (t["f1"].data_ptr() if t["f1"] is not None else None)
+    stats = None
+    if d["has_out_stats"]:
+        slabs = lib.adm_conv_stat_slabs(C.byref(a))
+        assert slabs > 0, d
+        stats = torch.empty(d["n"], slabs, d["cout"], 2, device=DEV)
+        a.out_stats = stats.data_ptr()
+    if d["ksplit"] > 1:
+        ws = torch.empty(d["ksplit"], d["n"] * d["h"] * d["w"], d["cout"], device=DEV)
+        keep.append(ws)
+        a.ws = ws.data_ptr()
+    check(orig(C.byref(a), torch.cuda.current_stream().cuda_stream), "adm_conv (replay)")
+    torch.cuda.synchronize()
+    return stats
+
+
+def _replay_conv(ops, orig, rec, seed):
+    from autodiffusion_amd import _lib
+    d = lr.record_dict(rec)
+    T = lr.KIND_DTYPE[rec[1]]
+    lib = _lib.load(rec[1])
+    t, packed, w32p, out = _conv_operands(ops, d, T, seed)
+    stats = _launch_conv(lib, orig, d, t, packed, w32p, out)
+    n = d["n"]
+    ho, wo = (out.shape[2], out.shape[3]) if d["out_mode"] == 1 else (out.shape[1], out.shape[2])
+    img, oy, ox = lr.sample_pixels(n, ho, wo, seed)
+    cin = d["c0"] + d["c1"]
+    per = max(1, (1 << 25) // max(1, (ho * wo * cin)))   # images per reference chunk
+    worst, num, den = 0.0, 0.0, 0.0
+    outv = out.permute(0, 2, 3, 1) if d["out_mode"] == 1 else out
+    for i0 in range(0, n, per):
+        sel = (img >= i0) & (img < i0 + per)
+        ref, bound = lr.conv_restate(d, T, t, img[sel], oy[sel], ox[sel])
+        got = outv[img[sel].to(DEV), oy[sel].to(DEV), ox[sel].to(DEV)].double()
+        assert torch.isfinite(got).all(), f"non-finite output {rec}"
+        err = (got - ref).abs()
+        r = err / bound
+        if r.max().item() > 1.0:   # the worst element, for the failure report
+            j = int(r.argmax())
+            p, c = j // r.shape[1], j % r.shape[1]
+            print(f"  worst element img {int(img[sel][p])} y {int(oy[sel][p])} x {int(ox[sel][p])} ch {c}: got {got[p, c].item():.8g} "
+                  f"ref {ref[p, c].item():.8g} bound {bound[p, c].item():.4g} ulp_T(ref) {lr.ulp_t(ref[p, c], T).item():.4g}")
+        worst = max(worst, r.max().item())
+        num += (err ** 2).sum().item()
+        den += (ref ** 2).sum().item()
+    fro = (num / max(den, 1e-300)) ** 0.5
+    if stats is not None:   # fused output statistics: per (image, channel) sums over the stored tensor
+        y = outv.double()
+        if d["prologue"] == 3:
+            s1, s2 = y.sum((1, 2)), (y * t["res"].double()).sum((1, 2))
+            a1, a2 = y.abs().sum((1, 2)), (y * t["res"].double()).abs().sum((1, 2))
+        else:
+            s1, s2 = y.sum((1, 2)), (y * y).sum((1, 2))
+            a1, a2 = y.abs().sum((1, 2)), s2
+        tot = stats.double().sum(1)
+        tol = (256 + stats.shape[1] + 8) * 2.0 ** -24
+        se = max(((tot[..., 0] - s1).abs() / (tol * a1 + 1e-30)).max().item(), ((tot[..., 1] - s2).abs() / (tol * a2 + 1e-30)).max().item())
+        worst = max(worst, se)
+    return worst, fro
+
+
+def _label(rec):
+    d = lr.record_dict(rec)
+    flags = [f for f in ("in1", "res", "aff_a", "fold0", "out_stats", "w_packed32") if d["has_" + f]]
+    return (f"{rec[1]} v{d['variant']} n{d['n']} {d['h']}x{d['w']} {d['c0']}+{d['c1']}->{d['cout']} taps{d['taps']} pro{d['prologue']} "
+            f"om{d['out_mode']} sc{d['out_scale']:g} ks{d['ksplit']} up{d['up_phase']} iu{d['in_up']} ru{d['res_up']} gg{d['geglu']} "
+            + ",".join(flags))
+
+
+def test_conv_launches_match_float64(ops, recorded):
+    t0 = time.time()
+    convs = sorted(r for r in recorded.records if r[0] == "conv")
+    assert convs, "the recorder captured no adm_conv launch"
+    fam_worst, fails = {}, []
+    for i, rec in enumerate(convs):
+        worst, fro = _replay_conv(ops, recorded.orig[rec[1]], rec, 1000 + i)
+        u = lr.U[lr.KIND_DTYPE[rec[1]]]
+        ok = worst <= 1.0 and fro <= lr.fro_bound(lr.conv_roundings(lr.record_dict(rec)), u)
+        print(f"conv {_label(rec)}: worst err/bound {worst:.3f}, fro/u {fro / u:.3f}{'' if ok else '  FAIL'}")
+        for f in lr.families(rec):
+            fam_worst[f] = max(fam_worst.get(f, 0.0), worst)
+        if not ok:
+            fails.append((_label(rec), worst, fro / u))
+    for k in ("bf16", "f16"):
+        print(f"{k}: {sum(1 for r in convs if r[1] == k)} distinct conv launches replayed")
+    for f in sorted(fam_worst):
+        print(f"worst err/bound {f}: {fam_worst[f]:.3f}")
+    print(f"conv replay: {time.time() - t0:.0f} s")
+    assert not fails, fails
+
+
+# ------------------------------------------------------------------ attention replay
+def test_attention_launches_match_float64(ops, recorded):
+    t0 = time.time()
+    recs = sorted(r for r in recorded.records if r[0] in ("attention", "attention_cross"))
+    assert recs
+    fam_worst, fails = {}, []
+    for i, rec in enumerate(recs):
+        kind = rec[1]
+        T = lr.KIND_DTYPE[kind]
+        torch.manual_seed(2000 + i)
+        if rec[0] == "attention":
+            _, _, n, t, c3, heads, new_order, want_lse = rec
+            qkv = torch.randn(n, t, c3, device=DEV).to(T)
+            out = ops.attention(qkv, heads, new_order, want_lse)
+            out, lse = out if want_lse else (out, None)
+            d, scale = c3 // 3 // heads, (c3 // 3 // heads) ** -0.5
+        else:
+            _, _, n, tq, qs, rows, kvs, tk, heads, d, scale = rec
+            hd = heads * d
+            if qs == kvs and rows == tq:    # self-attention over a fused [q | k | v] projection: kv aliases q's storage
+                buf = torch.randn(n, tq, qs, device=DEV).to(T)
+                q, kv = buf, buf[:, :, hd:]
+            else:
+                q, kv = torch.randn(n, tq, qs, device=DEV).to(T), torch.randn(n, rows, kvs, device=DEV).to(T)
+            out = ops.attention_cross(q, kv, heads, d, tk, scale)
+        torch.cuda.synchronize()
+        sel = sorted({0, n - 1, int(torch.randint(0, n, (1,)).item())})
+        worst, num, den = 0.0, 0.0, 0.0
+        for j in sel:
+            if rec[0] == "attention":
+                qh, kh, vh = lr.split_qkv(qkv[j:j + 1], heads, new_order)
+            else:
+                qh = q[j, :, :hd].reshape(tq, heads, d).permute(1, 0, 2)
+                kh = kv[j, :tk, :hd].reshape(tk, heads, d).permute(1, 0, 2)
+                vh = kv[j, :tk, hd:2 * hd].reshape(tk, heads, d).permute(1, 0, 2)
+            ref, bound = lr.attention_restate(qh, kh, vh, scale, T)
+            if rec[0] == "attention" and want_lse:   # the log-sum-exp the backward reads
+                lref, lb = lr.lse_restate(qh, kh, scale, T)
+                worst = max(worst, ((lse[j].double() - lref).abs() / lb).max().item())
+            got = out[j].reshape(-1, heads, d).permute(1, 0, 2)
+            assert torch.isfinite(got).all(), rec
+            err = (got.double() - ref).abs()
+            worst = max(worst, (err / bound).max().item())
+            num += (err ** 2).sum().item()
+            den += (ref ** 2).sum().item()
+        fro = (num / den) ** 0.5
+        u = lr.U[T]
+        ok = worst <= 1.0 and fro <= lr.fro_bound(2, u)
+        print(f"{rec}: worst err/bound {worst:.3f}, fro/u {fro / u:.3f}{'' if ok else '  FAIL'}")
+        for f in lr.families(rec):
+            fam_worst[f] = max(fam_worst.get(f, 0.0), worst)
+        if not ok:
+            fails.append((rec, worst, fro / u))
+    for f in sorted(fam_worst):
+        print(f"worst err/bound {f}: {fam_worst[f]:.3f}")
+    print(f"attention replay: {len(recs)} launches, {time.time() - t0:.0f} s")
+    assert not fails, fails
+
+
+# ------------------------------------------------------------------ classifier backward and GroupNorm replay
+def _report(name, recs, results, fam_worst=None):
+    fails = [(r, w) for r, w in zip(recs, results) if not w <= 1.0]
+    for r, w in zip(recs, results):
+        print(f"{r}: worst err/bound {w:.3f}{'' if w <= 1.0 else '  FAIL'}")
+    for k in ("bf16", "f16"):
+        ws = [w for r, w in zip(recs, results) if r[1] == k]
+        print(f"worst err/bound ('{k}', '{name}'): {max(ws) if ws else float('nan'):.3f} over {len(ws)} launches")
+    assert not fails, fails
+
+
+def test_attention_backward_launches_match_float64(ops, recorded):
+    recs = sorted(r for r in recorded.records if r[0] == "attention_bwd")
+    assert recs
+    results = []
+    for i, rec in enumerate(recs):
+        _, kind, n, t, c3, heads, new_order = rec
+        T = lr.KIND_DTYPE[kind]
+        d = c3 // 3 // heads
+        scale = d ** -0.5
+        torch.manual_seed(3000 + i)
+        qkv = torch.randn(n, t, c3, device=DEV).to(T)
+        out, lse = ops.attention(qkv, heads, new_order, want_lse=True)
+        dout = torch.randn(n, t, c3 // 3, device=DEV).to(T)
+        dqkv = ops.attention_bwd(qkv, out, dout, lse, heads, new_order)
+        torch.cuda.synchronize()
+        worst = 0.0
+        for j in sorted({0, n - 1, int(torch.randint(0, n, (1,)).item())}):
+            qh, kh, vh = lr.split_qkv(qkv[j:j + 1], heads, new_order)
+            oh = out[j].reshape(t, heads, d).permute(1, 0, 2)
+            doh = dout[j].reshape(t, heads, d).permute(1, 0, 2)
+            refs, bounds = lr.attention_bwd_restate(qh, kh, vh, oh, doh, scale, T)
+            gots = lr.split_qkv(dqkv[j:j + 1], heads, new_order)
+            for g, r, b in zip(gots, refs, bounds):
+                assert torch.isfinite(g).all(), rec
+                worst = max(worst, ((g.double() - r).abs() / b).max().item())
+        results.append(worst)
+    _report("attention_bwd", recs, results)
+
+
+def test_groupnorm_backward_launches_match_float64(ops, recorded):
+    recs = sorted(r for r in recorded.records if r[0] == "gn_bwd")
+    assert recs
+    results = []
+    for i, rec in enumerate(recs):
+        _, kind, n, h, w, c, silu, dy_half, has_add, add_half, has_partial, has_norm_add = rec
+        T = lr.KIND_DTYPE[kind]
+        torch.manual_seed(4000 + i)
+        x = torch.randn(n, h, w, c, device=DEV).to(T)
+        e = 0.3 * torch.randn(n, c, device=DEV) if has_norm_add else None
+        _, mean, rstd = lr.gn_affine_restate(x, torch.ones(c, device=DEV), torch.zeros(c, device=DEV), 1e-5, add=e)
+        stats = torch.stack([mean, rstd], -1).float()
+        a, b = 1 + 0.2 * torch.randn(n, c, device=DEV), 0.2 * torch.randn(n, c, device=DEV)
+        hs, ws_ = (h // 2, w // 2)
+        dy = torch.randn(n, hs if dy_half else h, ws_ if dy_half else w, c, device=DEV).to(T)
+        add = torch.randn(n, hs if add_half else h, ws_ if add_half else w, c, device=DEV).to(T) if has_add else None
+        partial = None
+        if has_partial:   # dy is the producing conv's dz, with its (sum dz, sum dz x) slab sums: one slab, summed in float64
+            dzd = dy.double()
+            partial = torch.stack([dzd.sum((1, 2)), (dzd * x.double()).sum((1, 2))], -1)[:, None].float().contiguous()
+        got = ops.gn_bwd(x, dy, (a, b), stats, silu, dy_half=dy_half, add=add, add_half=add_half, partial=partial, norm_add=e)
+        torch.cuda.synchronize()
+        ref, bound = lr.gn_bwd_restate(x, dy, a, b, stats, silu and not has_partial, dy_half, add, add_half, e, T)
+        assert torch.isfinite(got).all(), rec
+        results.append(((got.double() - ref).abs() / bound).max().item())
+    _report("gn_bwd", recs, results)
+
+
+def test_groupnorm_affine_launches_match_float64(ops, recorded):
+    recs = sorted(r for r in recorded.records if r[0] == "gn_affine")
+    assert recs
+    results = []
+    for i, rec in enumerate(recs):
+        _, kind, n, h, w, c0, c1, has_film, has_add, fused, want_stats, eps = rec
+        T = lr.KIND_DTYPE[kind]
+        c = c0 + c1
+        torch.manual_seed(5000 + i)
+
+        def src(ch):
+            if fused:   # a tensor that carries its producing conv's fused statistics (1x1 or 3x3: whichever offers them here)
+                xin = torch.randn(n, h, w, 32, device=DEV).to(T)
+                for taps in (1, 9):
+                    wt = torch.randn(ch, 32, *((3, 3) if taps == 9 else ()), device=DEV) * (32 * taps) ** -0.5
+                    y = ops.conv(xin, ops.pack_conv_weight(wt, T), 0.3 * torch.randn(ch, device=DEV), ch, taps, want_stats=True)
+                    if getattr(y, "_adm_stats", None) is not None:
+                        return y
+                raise AssertionError(f"no conv offers fused statistics for {rec}")
+            return (0.3 + torch.randn(n, h, w, ch, device=DEV)).to(T)
+        x0 = src(c0)
+        x1 = src(c1) if c1 else None
+        gamma, beta = 1 + 0.2 * torch.randn(c, device=DEV), 0.2 * torch.randn(c, device=DEV)
+        film = 0.3 * torch.randn(n, 2 * c, device=DEV) if has_film else None
+        add = 0.3 * torch.randn(n, c, device=DEV) if has_add else None
+        res = ops.gn_affine(x0, gamma, beta, x1, film=film, film_stride=2 * c if has_film else 0, want_stats=want_stats, eps=eps,
+                            add=add)
+        torch.cuda.synchronize()
+        x = x0 if x1 is None else torch.cat([x0, x1], 3)
+        y, mean, rstd = lr.gn_affine_restate(x, gamma, beta, eps, film=film, add=add)
+        got = res[0].double()[:, None, None, :] * x.double() + res[1].double()[:, None, None, :]
+        worst = ((got - y).abs() / (lr.U[T] / 8 * (1 + y.abs()))).max().item()
+        if want_stats:   # (mean, rstd) kept for the backward: fp32 values of the float64 statistics
+            st = res[2].double()
+            worst = max(worst, ((st[..., 0] - mean).abs() / (2.0 ** -20 * (mean.abs() + 1 / rstd))).max().item(),
+                        ((st[..., 1] - rstd).abs() / (2.0 ** -20 * rstd)).max().item())
+        results.append(worst)
+    _report("gn_affine", recs, results)
+
+
+# ------------------------------------------------------------------ fp16 range
+@pytest.mark.parametrize("case", ["one pass 3x3", "split-K 3x3", "resident 1x1", "fp32 NCHW head"])
+def test_fp16_conv_outputs_beyond_the_range_become_signed_inf(ops, case):
+    """Weights scaled so that some outputs pass 65504: an element whose float64 reference (minus its bound) is beyond 65520 (where
+    round-to-nearest overflows) must be +-inf with the reference's sign; one whose reference (plus its bound) is below 65504 must be
+    finite and within its bound; none may be NaN (the reference's fp16-torso behaviour).  The fp32 NCHW head has no 16-bit output:
+    every element must be finite and within its bound."""
+    T = torch.float16
+    n, hw, cin, cout, taps, ks, om = {"one pass 3x3": (2, 16, 128, 192, 9, 1, 0), "split-K 3x3": (2, 16, 256, 128, 9, 2, 0),
+                                      "resident 1x1": (2, 16, 256, 384, 1, 1, 0), "fp32 NCHW head": (2, 32, 128, 6, 9, 1, 1)}[case]
+    torch.manual_seed(11)
+    k = 3 if taps == 9 else 1
+    x = torch.randn(n, hw, hw, cin, device=DEV).to(T)
+    w32 = torch.randn(cout, cin, k, k, device=DEV) * (cin * taps) ** -0.5 * 40000.0
+    bias = 0.1 * torch.randn(cout, device=DEV)
+    out = ops.conv(x, ops.pack_conv_weight(w32, T), bias, cout, taps, out_f32_nchw=bool(om), ksplit=ks, variant=10 if taps == 1 else 0)
+    torch.cuda.synchronize()
+    d = dict(taps=taps, prologue=0, out_mode=om, ksplit=ks, up_phase=0, in_up=0, res_up=0, geglu=0, out_scale=0.0, has_fold0=False,
+             has_res=False)
+    img, oy, ox = lr.sample_pixels(n, hw, hw, 3)
+    ref, bound = lr.conv_restate(d, T, {"x0": x, "x1": None, "w": lr.round_t(w32, T), "bias": bias}, img, oy, ox)
+    got = (out.permute(0, 2, 3, 1) if om else out)[img.to(DEV), oy.to(DEV), ox.to(DEV)].double()
+    assert not torch.isnan(got).any()
+    over = (ref.abs() - bound) > 65520.0
+    inside = (ref.abs() + bound) < 65504.0
+    n_over = int(over.sum())
+    print(f"fp16 range {case}: {n_over} of {ref.numel()} sampled outputs beyond the range, max |ref| {ref.abs().max().item():.4g}")
+    if om:
+        assert torch.isfinite(got).all() and ((got - ref).abs() <= bound).all()
+        assert ref.abs().max().item() > 65504.0
+        return
+    assert n_over > 0
+    assert torch.isinf(got[over]).all() and torch.equal(torch.sign(got[over]), torch.sign(ref[over]))
+    assert torch.isfinite(got[inside]).all() and ((got[inside] - ref[inside]).abs() <= bound[inside]).all()
+
+
+# ------------------------------------------------------------------ GroupNorm at a large mean
+RATIOS = (0, 4, 16, 64, 256)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_groupnorm_statistics_at_a_large_mean(ops, dtype):
+    """gn_affine against a float64 GroupNorm of the same 16-bit tensor at |mean| / std in RATIOS, from conv-fused statistics (plain and
+    `add` = x + embedding) and from adm_gn_partial.  Bound on the normalised output y = (x - mean) rstd: u / 8 (1 + |y|) -- well below
+    the rounding to T that the consuming conv's prologue applies next.  Must hold up to a ratio of 16; the largest passing ratio is
+    printed."""
+    n, hw, cin, c = 2, 32, 64, 128
+    u = lr.U[dtype]
+    torch.manual_seed(7)
+    x_in = torch.randn(n, hw, hw, cin, device=DEV).to(dtype)
+    wp = ops.pack_conv_weight(torch.randn(c, cin, device=DEV) * cin ** -0.5, dtype)
+    gamma, beta = torch.ones(c, device=DEV), torch.zeros(c, device=DEV)
+    passing = {}
+    for form in ("fused", "fused_add", "partial"):
+        best = None
+        for r in RATIOS:
+            if form == "fused_add":
+                x = ops.conv(x_in, wp, torch.zeros(c, device=DEV), c, 1, want_stats=True)
+                e = r + 0.1 * torch.randn(n, c, device=DEV)
+                a, b = ops.gn_affine(x, gamma, beta, add=e)
+                xe = x.double() + e.double()[:, None, None, :]
+            else:
+                x = ops.conv(x_in, wp, torch.full((c,), float(r), device=DEV), c, 1, want_stats=True)
+                if form == "partial":
+                    x = x.clone()           # no fused statistics: the adm_gn_partial pass
+                assert (getattr(x, "_adm_stats", None) is not None) == (form == "fused")
+                a, b = ops.gn_affine(x, gamma, beta)
+                xe = x.double()
+            g = xe.reshape(n, hw * hw, 32, c // 32)
+            mean = g.mean((1, 3), keepdim=True)
+            var = ((g - mean) ** 2).mean((1, 3), keepdim=True)
+            y = ((g - mean) / torch.sqrt(var + 1e-5)).reshape(n, hw, hw, c)
+            got = a.double()[:, None, None, :] * x.double() + b.double()[:, None, None, :]
+            ratio = (((got - y).abs()) / (u / 8 * (1 + y.abs()))).max().item()
+            print(f"GroupNorm {dtype} {form} |mean|/std {r}: worst err/bound {ratio:.3f}")
+            if ratio <= 1.0 and (best is None or best == RATIOS[RATIOS.index(r) - 1]):
+                best = r
+        passing[form] = best
+    print(f"GroupNorm {dtype}: largest |mean|/std within the bound: {passing}")
+    assert all(v is not None and v >= 16 for v in passing.values()), passing
