@@ -10,11 +10,13 @@ how batches are sharded over ranks.
 """
 from __future__ import annotations
 
+import ast
 import copy
-from typing import Optional, Sequence, Union
+from typing import Callable, Optional, Sequence, Union
 
 import torch
 
+from . import logger
 from .schedule import apply_candidate
 
 NUM_CLASSES = 1000
@@ -48,6 +50,77 @@ def graph_auto(image_size: int, images_per_pass: int) -> bool:
     return images_per_pass * (image_size / 64.0) ** 2 <= 256
 
 
+# the sampling CLIs' wording of the merge line; the search passes its own (search.MERGE_LOG)
+MERGE_LOG = "evaluating {merge} batches of {batch_size} per pass ({per_pass} images per pass; bitwise the images of separate passes)"
+
+
+def batch_plan(num_samples: int, batch_size: int, world: int = 1, rank: int = 0, image_size: int = 64, merge_batches: int = 0):
+    """How `num_samples` images are produced in rounds: -> the passes over the networks that `rank` runs, each a list of
+    (global batch index, images kept) -- the one statement of this policy; no torch, no GPU.
+
+    Every round, each of the `world` ranks samples one reference batch of `batch_size` images; the batch of round i on rank r has
+    the global index g = i * world + r, which is also its place in the rank-major concatenation of which the reference keeps
+    `arr[:num_samples]`: it contributes its first max(0, min(batch_size, num_samples - g * batch_size)) images.  A batch that
+    contributes none is still sampled, so that the ranks stay in step (barrier, all_gather).  merge_policy decides how many
+    of a rank's batches ride in one pass (`merge_batches` > 0 is taken as given); the first pass is never the smaller one."""
+    rounds = -(-num_samples // (batch_size * world))
+    merge = merge_policy(image_size, batch_size, int(merge_batches or 0), rounds)[0]
+    plan = [(i * world + rank, max(0, min(batch_size, num_samples - (i * world + rank) * batch_size))) for i in range(rounds)]
+    return [plan[i:i + merge] for i in range(0, rounds, merge)]
+
+
+def _literal(text: str, flag: str):
+    try:
+        return ast.literal_eval(text)
+    except (ValueError, SyntaxError, TypeError, MemoryError, RecursionError):
+        raise ValueError(f"{flag}: expected a literal (numbers, lists, dicts; expressions and calls are not evaluated), got {text!r}") from None
+
+
+def _is_ints(v) -> bool:
+    return isinstance(v, (list, tuple)) and all(isinstance(i, int) and not isinstance(i, bool) for i in v)
+
+
+def _is_int_lists(v) -> bool:
+    return isinstance(v, (list, tuple)) and all(_is_ints(s_) for s_ in v)
+
+
+def parse_int_list(text: str, flag: str, *, nested: bool = False, use_mean: bool = False):
+    """A list flag (--use_timestep, --search_space; nested: --skip_layers, one list per step) -> list of ints (of lists of ints).
+    `use_mean`: the space-separated averaged schedule '[153.2 424.7 ...]', parsed as numbers and rounded before the check."""
+    v = _literal(text.replace(" ", ",") if use_mean else text, flag)
+    if use_mean and isinstance(v, (list, tuple)) and all(isinstance(t, (int, float)) and not isinstance(t, bool) for t in v):
+        v = [round(t) for t in v]
+    if nested and _is_int_lists(v):
+        return [list(s_) for s_ in v]
+    if not nested and _is_ints(v):
+        return list(v)
+    raise ValueError(f"{flag}: expected a list of {'lists of ints' if nested else 'ints'}, got {text!r}")
+
+
+def parse_candidate(text: str, flag: str = "candidate"):
+    """A candidate as the search writes it (str(cand)) or as a flag gives it: a list of ints, or a dict with `timesteps` and
+    one `skip_layers` list per timestep.  ast.literal_eval plus a shape check: command-line text is input from outside."""
+    v = _literal(text, flag)
+    if isinstance(v, dict):
+        ts, sk = v.get("timesteps"), v.get("skip_layers")
+        if not (_is_ints(ts) and _is_int_lists(sk) and len(ts) == len(sk)):
+            raise ValueError(f"{flag}: a dict candidate needs 'timesteps' (ints) and 'skip_layers' (one list of ints per timestep), got {text!r}")
+        return v
+    if not _is_ints(v):
+        raise ValueError(f"{flag}: expected a list of ints or a {{'timesteps', 'skip_layers'}} dict, got {text!r}")
+    return list(v)
+
+
+def parse_index_step(value, flag: str = "--index_step"):
+    """--index_step: a number, or a numeric string.  Arithmetic ('4*58': pass the product) is refused, as any expression."""
+    if not isinstance(value, str):
+        return int(value)
+    v = _literal(value, flag)
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError(f"{flag}: expected a number, got {value!r}")
+    return v
+
+
 class CandidateEvaluator:
     def __init__(self, model, base_diffusion, classifier=None, *, image_size: int, use_ddim: bool = True,
                  clip_denoised: bool = True, class_cond: bool = True, classifier_scale: float = 1.0,
@@ -63,6 +136,7 @@ class CandidateEvaluator:
         self.classifier_scale = classifier_scale
         self.device = device if device is not None else model.device
         self.skip_layers = None
+        self._merge_logged = False   # sample_plan's merge line: once per evaluator
         if use_graph:  # hipGraph replay of the UNet evaluation and of the guidance gradient (batches <= ~100: the host's
             model.enable_graph(True)   # ~60 ms of launch work per guided step is otherwise the floor)
             if classifier is not None and hasattr(classifier, "enable_graph"):
@@ -95,6 +169,32 @@ class CandidateEvaluator:
         assert y is not None
         return self.classifier.log_prob_grad(x, t, y, self.classifier_scale)
 
+    def _sample(self, batch_size: int, seeds: Sequence[Optional[int]]):
+        """One pass over the networks for len(seeds) reference batches of `batch_size` images, each drawing its labels, x_T and
+        per-step noise from its own generator (a seed of None: the global RNG) -> (uint8 NHWC of the whole pass, fp32 sample)."""
+        dev = self.device
+        gens = [None if s_ is None else torch.Generator(device=dev).manual_seed(int(s_) & 0x7FFFFFFFFFFFFFFF) for s_ in seeds]
+        shape1 = (batch_size, 3, self.image_size, self.image_size)
+        classes, noise = [], []
+        for g_ in gens:
+            classes.append(torch.randint(low=0, high=NUM_CLASSES, size=(batch_size,), device=dev, generator=g_))
+            noise.append(torch.randn(*shape1, device=dev, generator=g_))
+        one = len(gens) == 1
+        classes, x_T = (classes[0], noise[0]) if one else (torch.cat(classes, 0), torch.cat(noise, 0))
+        d = self.active_diffusion
+        d.generator = gens[0] if one else [(g_, batch_size) for g_ in gens]
+        kwargs = {"y": classes}
+        if self.skip_layers is not None:
+            kwargs["skip_layers"] = self.skip_layers
+        fn = d.ddim_sample_loop if self.use_ddim else d.p_sample_loop
+        try:
+            sample = fn(self._model_fn, tuple(x_T.shape), noise=x_T, clip_denoised=self.clip_denoised, model_kwargs=kwargs,
+                        cond_fn=self._cond_fn if self.classifier is not None else None, device=dev)
+        finally:
+            d.generator = None    # a later direct call of the diffusion object must not draw from this pass's generators
+        self.last_classes = classes
+        return d.last_uint8_nhwc, sample
+
     def sample_batches(self, batch_size: int, seeds: Sequence[int]):
         """len(seeds) reference batches of `batch_size` images in ONE pass over the networks -> [uint8 NHWC [B, H, W, 3]] per seed.
 
@@ -102,47 +202,28 @@ class CandidateEvaluator:
         from its own generator, and an image's result does not depend on how many images ride along (tests/test_hip_bigbatch.py).
         The reference's search batch (100, a memory-driven flag) leaves the 16x16 / 8x8 levels with 200-300 tiles on 256 CUs; two
         batches per pass fill the chip like the headline's 256."""
-        dev = self.device
-        gens = [torch.Generator(device=dev).manual_seed(int(s_) & 0x7FFFFFFFFFFFFFFF) for s_ in seeds]
-        shape1 = (batch_size, 3, self.image_size, self.image_size)
-        classes, noise = [], []
-        for g_ in gens:   # the draw order of sample_batch, per generator
-            classes.append(torch.randint(low=0, high=NUM_CLASSES, size=(batch_size,), device=dev, generator=g_))
-            noise.append(torch.randn(*shape1, device=dev, generator=g_))
-        classes, x_T = torch.cat(classes, 0), torch.cat(noise, 0)
-        d = self.active_diffusion
-        d.generator = [(g_, batch_size) for g_ in gens]
-        kwargs = {"y": classes}
-        if self.skip_layers is not None:
-            kwargs["skip_layers"] = self.skip_layers
-        fn = d.ddim_sample_loop if self.use_ddim else d.p_sample_loop
-        try:
-            fn(self._model_fn, tuple(x_T.shape), noise=x_T, clip_denoised=self.clip_denoised, model_kwargs=kwargs,
-               cond_fn=self._cond_fn if self.classifier is not None else None, device=dev)
-        finally:
-            d.generator = None
-        self.last_classes = classes
-        return list(d.last_uint8_nhwc.split(batch_size, 0))
+        return list(self._sample(batch_size, seeds)[0].split(batch_size, 0))
 
     def sample_batch(self, batch_size: int, seed: Optional[int] = None, return_float: bool = False):
         """-> uint8 NHWC [B, H, W, 3] on the device (and the fp32 sample if return_float)."""
-        dev = self.device
-        gen = None
-        if seed is not None:
-            gen = torch.Generator(device=dev).manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
-        classes = torch.randint(low=0, high=NUM_CLASSES, size=(batch_size,), device=dev, generator=gen)
-        shape = (batch_size, 3, self.image_size, self.image_size)
-        x_T = torch.randn(*shape, device=dev, generator=gen)
-        d = self.active_diffusion
-        d.generator = gen
-        kwargs = {"y": classes}
-        if self.skip_layers is not None:
-            kwargs["skip_layers"] = self.skip_layers
-        fn = d.ddim_sample_loop if self.use_ddim else d.p_sample_loop
-        sample = fn(self._model_fn, shape, noise=x_T, clip_denoised=self.clip_denoised, model_kwargs=kwargs,
-                    cond_fn=self._cond_fn if self.classifier is not None else None, device=dev)
-        u8 = d.last_uint8_nhwc
-        self.last_classes = classes
-        if return_float:
-            return u8, sample
-        return u8
+        u8, sample = self._sample(batch_size, [seed])
+        return (u8, sample) if return_float else u8
+
+    def sample_plan(self, num_samples: int, batch_size: int, seed_of: Callable[[int], int], *, world: int = 1, rank: int = 0,
+                    merge_batches: int = 0, merge_log: str = MERGE_LOG):
+        """Walk batch_plan(...) for this rank: one sampling call per pass, yielding per reference batch
+        (uint8 NHWC batch, its classes, how many of its images count towards `num_samples`).  `seed_of(g)` is the seed of the
+        batch with global index g.  `merge_log` is the wording of the line that tells log.txt about merged passes; it is written
+        at most once per evaluator (one search, one CLI run)."""
+        passes = batch_plan(num_samples, batch_size, world, rank, self.image_size, merge_batches)
+        merge = len(passes[0]) if passes else 1
+        if merge > 1 and not self._merge_logged:
+            logger.log(merge_log.format(merge=merge, batch_size=batch_size, per_pass=merge * batch_size))
+            self._merge_logged = True
+        done = 0
+        for batches in passes:
+            u8s = self.sample_batches(batch_size, [seed_of(g) for g, _ in batches])
+            for u8, classes, (_, keep) in zip(u8s, self.last_classes.split(batch_size, 0), batches):
+                yield u8, classes, keep
+                done += 1    # logged once the caller has consumed the batch (the CLIs: after its all_gather)
+                logger.log('created ' + str(done * batch_size * world) + ' samples')

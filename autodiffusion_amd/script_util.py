@@ -12,7 +12,9 @@ from __future__ import annotations
 
 import argparse
 
+from . import dist_util, logger
 from . import schedule as gd
+from .evaluate import parse_int_list
 from .arch import build_unet_plan
 from .sampler import SpacedDiffusion
 from .schedule import space_timesteps
@@ -145,6 +147,72 @@ def create_classifier(image_size, classifier_use_fp16, classifier_width, classif
         from .unet import warn_compute_dtype
         warn_compute_dtype("create_classifier", "classifier_use_fp16")
     return EncoderUNetModel(plan, use_fp16=classifier_use_fp16)
+
+
+def load_model_and_diffusion(args, log_source=False):
+    """What every script does with its parsed flags: build the UNet and the diffusion, place the model, load --model_path
+    (synthetic weights without one: benchmarks, tests), fp16, eval."""
+    logger.log("creating model and diffusion...")
+    model, diffusion = create_model_and_diffusion(**args_to_dict(args, model_and_diffusion_defaults().keys()))
+    model.to(dist_util.dev())
+    if args.model_path:
+        model.load_state_dict(dist_util.load_state_dict(args.model_path, map_location="cpu"))
+        if log_source:
+            logger.log('load from: ' + args.model_path)
+    else:
+        model.randomize_(1234)
+    if args.use_fp16:
+        model.convert_to_fp16()
+    model.eval()
+    return model, diffusion
+
+
+def load_classifier(args, log_loading=False):
+    """The guidance classifier from the parsed flags, as load_model_and_diffusion; None with --without_classifier."""
+    if args.without_classifier:
+        return None
+    if log_loading:
+        logger.log("loading classifier...")
+    classifier = create_classifier(**args_to_dict(args, classifier_defaults().keys()))
+    classifier.to(dist_util.dev())
+    if args.classifier_path:
+        classifier.load_state_dict(dist_util.load_state_dict(args.classifier_path, map_location="cpu"))
+    else:
+        classifier.randomize_(4321)
+    classifier.eval()
+    return classifier
+
+
+def candidate_from_flags(args, diffusion):
+    """The sampling CLIs' candidate: --use_timestep (default: the diffusion's own steps), sorted; with --skip_layers, a dict
+    candidate with one skip list per step."""
+    steps = sorted(diffusion.use_timesteps if args.use_timestep is None else parse_int_list(args.use_timestep, "--use_timestep"))
+    if args.skip_layers is None:
+        return steps
+    return {"timesteps": steps, "skip_layers": parse_int_list(args.skip_layers, "--skip_layers", nested=True)}
+
+
+def gather_batches(ev, args):
+    """The sampling CLIs' use of CandidateEvaluator.sample_plan: every reference batch (seeded by --seed and its global index)
+    all-gathered over the ranks, rank-major as the reference concatenates them -> (host image batches, host label batches);
+    the caller keeps the first num_samples of their concatenation."""
+    import torch as th
+    import torch.distributed as dist
+    world = dist_util.get_world_size()
+    all_images, all_labels = [], []
+    for sample, classes, _ in ev.sample_plan(args.num_samples, args.batch_size, lambda g: args.seed * 1000003 + g, world=world,
+                                             rank=dist_util.get_rank(), merge_batches=int(getattr(args, "merge_batches", 0) or 0)):
+        sample, classes = sample.contiguous(), classes.contiguous()
+        if world > 1:
+            gathered = [th.zeros_like(sample) for _ in range(world)]
+            gathered_labels = [th.zeros_like(classes) for _ in range(world)]
+            dist.all_gather(gathered, sample)
+            dist.all_gather(gathered_labels, classes)
+        else:
+            gathered, gathered_labels = [sample], [classes]
+        all_images.extend([s.cpu().numpy() for s in gathered])
+        all_labels.extend([lab.cpu().numpy() for lab in gathered_labels])
+    return all_images, all_labels
 
 
 def add_dict_to_argparser(parser, default_dict):

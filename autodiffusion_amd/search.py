@@ -27,9 +27,13 @@ import numpy as np
 import torch
 
 from . import dist_util, logger
-from .evaluate import CandidateEvaluator, merge_policy
+from .evaluate import CandidateEvaluator, parse_candidate, parse_index_step
 from .fid import ActivationAccumulator, FIDStatistics, cal_fid
 from .schedule import space_timesteps
+
+# the search's wording of evaluate.MERGE_LOG: log.txt shows the deviation from the reference's launch unit
+MERGE_LOG = ("evaluating {merge} batches of {batch_size} per pass over the networks ({per_pass} images per pass; "
+             "bitwise the images of separate passes; --merge_batches 1 restores the reference's launch unit)")
 
 choice = lambda x: x[np.random.randint(len(x))] if isinstance(x, tuple) else choice(tuple(x))  # noqa: E731
 
@@ -118,37 +122,20 @@ class EvolutionSearcher(object):
         seed0 = (int(getattr(args, "seed", 0)) * 1000003 + zlib.crc32(str(cand).encode())) & 0x7FFFFFFF
         # fewer samples than feature dimensions (the search's regime, `num_samples <= 1000` against 2048): the on-device Frechet
         # distance can work from the rows (an n x n eigenproblem instead of two 2048 x 2048 ones)
-        keep = int(args.num_samples) if (getattr(args, "fid_on_device", False) and args.num_samples < self.feature_dim) else 0
-        acc = ActivationAccumulator(self.feature_dim, self._ev.device, keep_rows=keep) if self.features is not None else None
+        rows = int(args.num_samples) if (getattr(args, "fid_on_device", False) and args.num_samples < self.feature_dim) else 0
+        acc = ActivationAccumulator(self.feature_dim, self._ev.device, keep_rows=rows) if self.features is not None else None
         if acc is not None and self._ref_dev is not None and self._ref_dev[0] is self.ref_stats:
             acc._ref_dev = self._ref_dev       # the reference statistics stay on the device across candidates
         host_images = []
-        produced = 0
-        batch_idx = 0
-        # rounds still to run (this rank takes one batch per round), and how many of them ride in one pass over the networks:
-        # images are bitwise those of separate passes (CandidateEvaluator.sample_batches), the chip is filled like the headline batch
-        rounds = -(-args.num_samples // (args.batch_size * world))
-        merge, per_pass = merge_policy(int(getattr(args, "image_size", 64)), args.batch_size, int(getattr(args, "merge_batches", 0) or 0), rounds)
-        if merge > 1 and not getattr(self, "_merge_logged", False):   # once per search: log.txt shows the deviation from the reference's launch unit
-            logger.log(f"evaluating {merge} batches of {args.batch_size} per pass over the networks ({per_pass} images per pass; "
-                       "bitwise the images of separate passes; --merge_batches 1 restores the reference's launch unit)")
-            self._merge_logged = True
-        while produced < args.num_samples:
-            k = min(merge, rounds - batch_idx)
-            seeds = [seed0 + 7919 * ((batch_idx + j) * world + rank) for j in range(k)]
-            u8s = [self._ev.sample_batch(args.batch_size, seed=seeds[0])] if k == 1 else self._ev.sample_batches(args.batch_size, seeds)
-            for u8 in u8s:
-                # the reference keeps arr[:num_samples] of the rank-major concatenation of every round
-                start = produced + rank * args.batch_size
-                keep = max(0, min(args.batch_size, args.num_samples - start))
-                if acc is not None:
-                    if keep > 0:
-                        acc.add_from(self.features, u8[:keep])   # on a side stream, next to the next pass's sampling
-                else:
-                    host_images.append(u8[:keep].cpu().numpy())
-                produced += args.batch_size * world
-                batch_idx += 1
-                logger.log('created ' + str(min(produced, batch_idx * args.batch_size * world)) + ' samples')
+        batches = 0
+        # rounds, merged passes, sharding over ranks: evaluate.batch_plan; the merge line is logged once per search
+        for u8, _, keep in self._ev.sample_plan(args.num_samples, args.batch_size, lambda g: seed0 + 7919 * g, world=world, rank=rank,
+                                                merge_batches=int(getattr(args, "merge_batches", 0) or 0), merge_log=MERGE_LOG):
+            if acc is None:
+                host_images.append(u8[:keep].cpu().numpy())
+            elif keep > 0:
+                acc.add_from(self.features, u8[:keep])   # on a side stream, next to the next pass's sampling
+            batches += 1
         if world > 1 or (not local and dist_util.collectives_on()):
             import torch.distributed as dist
             dist.barrier()
@@ -175,7 +162,7 @@ class EvolutionSearcher(object):
             self._coll_logged = True
         logger.log('reset_time: ' + str(reset_time) + ', sample_time: ' + str(sample_time) + ', fid_time: ' + str(fid_time))
         self.last_times = {"reset_time": reset_time, "sample_time": sample_time, "fid_time": fid_time,
-                           "images": int(args.num_samples), "batches_this_rank": batch_idx}
+                           "images": int(args.num_samples), "batches_this_rank": batches}
         return fid
 
     # ------------------------------------------------------------------ EA bookkeeping (reference order of RNG draws)
@@ -205,7 +192,7 @@ class EvolutionSearcher(object):
         if self.population_parallel:
             self._pending.append(cand)  # evaluated by flush_pending(), sharded over ranks
         else:
-            info['fid'] = self.get_cand_fid(args=self.args, cand=eval(cand))
+            info['fid'] = self.get_cand_fid(args=self.args, cand=parse_candidate(cand))
             logger.log('cand: {}, fid: {}'.format(cand, info['fid']) + self.fid_note)
         info['visited'] = True
         return True
@@ -240,7 +227,7 @@ class EvolutionSearcher(object):
         world = dist.get_world_size() if multi else 1
         rank = dist.get_rank() if multi else 0
         pending, self._pending = self._pending, []
-        cands = [eval(c) for c in pending]
+        cands = [parse_candidate(c) for c in pending]
         costs = [self.candidate_cost(c) for c in cands]
         owner = self.assign_candidates(costs, world)
         fids = np.zeros(len(pending), dtype=np.float64)
@@ -290,23 +277,32 @@ class EvolutionSearcher(object):
     def get_random(self, num):
         self._fill_random(num, self.is_legal)
 
-    def get_cross(self, k, cross_num):
-        assert k in self.keep_top_k
-        logger.log('cross ......')
+    def _collect(self, what, num, make, legal):
+        """The retry loop of every operator: up to 10 * num tries of `make()`, keeping the candidates that are `legal`."""
+        logger.log(what + ' ......')
         res = []
-        max_iters = cross_num * 10
-        while len(res) < cross_num and max_iters > 0:
+        max_iters = num * 10
+        while len(res) < num and max_iters > 0:
             max_iters -= 1
-            cand1 = eval(choice(self.keep_top_k[k]))
-            cand2 = eval(choice(self.keep_top_k[k]))
-            new_cand = [cand1[i] if np.random.random_sample() < 0.5 else cand2[i] for i in range(len(cand1))]
-            cand = str(new_cand)
-            if not self.is_legal(cand):
+            cand = str(make())
+            if not legal(cand):
                 continue
             res.append(cand)
-            logger.log('cross {}/{}'.format(len(res), cross_num))
-        logger.log('cross_num = {}'.format(len(res)))
+            logger.log('{} {}/{}'.format(what, len(res), num))
+        logger.log('{}_num = {}'.format(what.split()[0], len(res)))   # 'mutation x0' counts as mutation_num, as in the reference
         return res
+
+    def _cross(self, cand1, cand2):
+        return [cand1[i] if np.random.random_sample() < 0.5 else cand2[i] for i in range(len(cand1))]
+
+    def get_cross(self, k, cross_num):
+        assert k in self.keep_top_k
+
+        def make():
+            cand1 = parse_candidate(choice(self.keep_top_k[k]))
+            cand2 = parse_candidate(choice(self.keep_top_k[k]))
+            return self._cross(cand1, cand2)
+        return self._collect('cross', cross_num, make, self.is_legal)
 
     def _mutate(self, cand, m_prob):
         if self.search_space is not None:
@@ -325,32 +321,18 @@ class EvolutionSearcher(object):
 
     def get_mutation(self, k, mutation_num, m_prob):
         assert k in self.keep_top_k
-        logger.log('mutation ......')
-        res = []
-        max_iters = mutation_num * 10
-        while len(res) < mutation_num and max_iters > 0:
-            max_iters -= 1
-            cand = str(self._mutate(eval(choice(self.keep_top_k[k])), m_prob))
-            if not self.is_legal(cand):
-                continue
-            res.append(cand)
-            logger.log('mutation {}/{}'.format(len(res), mutation_num))
-        logger.log('mutation_num = {}'.format(len(res)))
-        return res
+        return self._collect('mutation', mutation_num, lambda: self._mutate(parse_candidate(choice(self.keep_top_k[k])), m_prob),
+                             self.is_legal)
 
     def mutate_init_x(self, x0, mutation_num, m_prob):
-        logger.log('mutation x0 ......')
-        res = []
-        max_iters = mutation_num * 10
-        while len(res) < mutation_num and max_iters > 0:
-            max_iters -= 1
-            cand = str(self._mutate(eval(x0), m_prob))
-            if not self.is_legal_before_search(cand):
-                continue
-            res.append(cand)
-            logger.log('mutation x0 {}/{}'.format(len(res), mutation_num))
-        logger.log('mutation_num = {}'.format(len(res)))
-        return res
+        return self._collect('mutation x0', mutation_num, lambda: self._mutate(parse_candidate(x0), m_prob), self.is_legal_before_search)
+
+    def _initial_candidate(self, steps):
+        """The candidate of the evenly spaced schedule that --use_ddim_init_x seeds the population with."""
+        return steps
+
+    def _after_selection(self):
+        """Hook between an epoch's top list and its offspring (the dynamic search opens its skip range here)."""
 
     def search(self):
         args = self.args
@@ -366,11 +348,11 @@ class EvolutionSearcher(object):
         else:
             steps = self.base_diffusion.original_num_steps
             timestep_respacing = ('ddim' if args.use_ddim else '') + str(args.time_step)
-            init_x = str(list(space_timesteps(steps, timestep_respacing)))
+            init_x = str(self._initial_candidate(list(space_timesteps(steps, timestep_respacing))))
             self.is_legal_before_search(init_x)
             self.candidates.append(init_x)
             # the guided script seeds pop//2 + 1 random candidates, the unconditional one pop//2
-            extra = 0 if self.break_at_last_epoch else 1
+            extra = 0 if self.variant == "unconditional" else 1
             self.get_random_before_search(self.population_num // 2 + extra)
             self.candidates += self.mutate_init_x(x0=init_x, mutation_num=self.population_num - self.population_num // 2 - 1,
                                                   m_prob=0.1)
@@ -382,6 +364,7 @@ class EvolutionSearcher(object):
             logger.log('epoch = {} : top {} result'.format(self.epoch, len(self.keep_top_k[50])))
             for i, cand in enumerate(self.keep_top_k[50]):
                 logger.log('No.{} {} fid = {}'.format(i + 1, cand, self.vis_dict[cand]['fid']) + self.fid_note)
+            self._after_selection()
             if self.break_at_last_epoch and self.epoch + 1 == self.max_epochs:
                 break
             self.candidates = self.get_mutation(self.select_num, self.mutation_num, self.m_prob)
@@ -406,17 +389,19 @@ class DynamicEvolutionSearcher(EvolutionSearcher):
     """
 
     def __init__(self, args, model, base_diffusion, time_step, classifier=None, index_step=None, **kw):
-        kw.setdefault("variant", "guided")
+        kw["variant"] = "guided"            # the dynamic script is the guided one: pop//2 + 1 random candidates next to init_x
         super().__init__(args, model, base_diffusion, time_step, classifier=classifier, **kw)
         self.init_time_step = time_step
         self.model_layers = model.layer_num if model is not None else int(getattr(args, "layer_num"))
         self.max_index_number = time_step * self.model_layers
         if index_step is not None:
-            self.max_index_number = eval(index_step) if isinstance(index_step, str) else int(index_step)
+            self.max_index_number = parse_index_step(index_step)
         self.max_prun = args.max_prun
         self.min_prun = args.min_prun
         self.skip_layer_range = [0, 0]
         self.last_best_cand = None
+        self.x0 = ''                       # search(): the dynamic script has no --init_x branch,
+        self.break_at_last_epoch = True    # and always stops before the last epoch's offspring (:701)
 
     def cand2gen(self, cand):
         """Flat index encoding (layer + layer_num * timestep of every evaluated layer), zero-padded (:207-217)."""
@@ -492,83 +477,33 @@ class DynamicEvolutionSearcher(EvolutionSearcher):
                 self._touch_skips(cand['skip_layers'][i], m_prob)
         return cand
 
-    def get_cross(self, k, cross_num):
-        assert k in self.keep_top_k
-        logger.log('cross ......')
-        res = []
-        max_iters = cross_num * 10
-        while len(res) < cross_num and max_iters > 0:
-            max_iters -= 1
-            cand1 = eval(choice(self.keep_top_k[k]))
-            cand2 = eval(choice(self.keep_top_k[k]))
-            child = {'timesteps': [], 'skip_layers': []}
-            for i in range(min(len(cand1['timesteps']), len(cand2['timesteps']))):
-                src = cand1 if np.random.random_sample() < 0.5 else cand2
-                child['timesteps'].append(src['timesteps'][i])
-                child['skip_layers'].append(src['skip_layers'][i])
-            for parent in (cand1, cand2):                          # list (lexicographic) comparison, as in the reference
-                if child['timesteps'] < parent['timesteps']:
-                    child['timesteps'] += parent['timesteps'][len(child['timesteps']):]
-                    child['skip_layers'] += parent['skip_layers'][len(child['skip_layers']):]
-            cand = str(child)
-            if not self.is_legal(cand):
-                continue
-            res.append(cand)
-            logger.log('cross {}/{}'.format(len(res), cross_num))
-        logger.log('cross_num = {}'.format(len(res)))
-        return res
+    def _cross(self, cand1, cand2):
+        child = {'timesteps': [], 'skip_layers': []}
+        for i in range(min(len(cand1['timesteps']), len(cand2['timesteps']))):
+            src = cand1 if np.random.random_sample() < 0.5 else cand2
+            child['timesteps'].append(src['timesteps'][i])
+            child['skip_layers'].append(src['skip_layers'][i])
+        for parent in (cand1, cand2):                          # list (lexicographic) comparison, as in the reference
+            if child['timesteps'] < parent['timesteps']:
+                child['timesteps'] += parent['timesteps'][len(child['timesteps']):]
+                child['skip_layers'] += parent['skip_layers'][len(child['skip_layers']):]
+        return child
 
     def mutate_init_x(self, x0, mutation_num, m_prob):
-        logger.log('mutation x0 ......')
-        res = []
-        max_iters = mutation_num * 10
-        while len(res) < mutation_num and max_iters > 0:
-            max_iters -= 1
-            cand = str(self._mutate(eval(x0), m_prob, fill_empty=False))
-            if not self.is_legal_before_search(cand):
-                continue
-            res.append(cand)
-            logger.log('mutation x0 {}/{}'.format(len(res), mutation_num))
-        logger.log('mutation_num = {}'.format(len(res)))
-        return res
+        return self._collect('mutation x0', mutation_num, lambda: self._mutate(parse_candidate(x0), m_prob, fill_empty=False),
+                             self.is_legal_before_search)
 
-    def search(self):
-        args = self.args
-        logger.log('population_num = {} select_num = {} mutation_num = {} crossover_num = {} random_num = {} max_epochs = {}'.format(
-            self.population_num, self.select_num, self.mutation_num, self.crossover_num,
-            self.population_num - self.mutation_num - self.crossover_num, self.max_epochs))
-        if getattr(args, "use_ddim_init_x", False) is False:
-            self.get_random_before_search(self.population_num)
-        else:
-            steps = self.base_diffusion.original_num_steps
-            init_x = list(space_timesteps(steps, ('ddim' if args.use_ddim else '') + str(args.time_step)))
-            init_cand = str({'timesteps': init_x, 'skip_layers': [[] for _ in init_x]})
-            self.is_legal_before_search(init_cand)
-            self.candidates.append(init_cand)
-            self.get_random_before_search(self.population_num // 2 + 1)
-            self.candidates += self.mutate_init_x(x0=init_cand, mutation_num=self.population_num - self.population_num // 2 - 1,
-                                                  m_prob=0.1)
-        while self.epoch < self.max_epochs:
-            logger.log('epoch = {}'.format(self.epoch))
-            self.flush_pending()
-            self.update_top_k(self.candidates, k=self.select_num, key=lambda x: self.vis_dict[x]['fid'])
-            self.update_top_k(self.candidates, k=50, key=lambda x: self.vis_dict[x]['fid'])
-            logger.log('epoch = {} : top {} result'.format(self.epoch, len(self.keep_top_k[50])))
-            for i, cand in enumerate(self.keep_top_k[50]):
-                logger.log('No.{} {} fid = {}'.format(i + 1, cand, self.vis_dict[cand]['fid']) + self.fid_note)
-            best = self.keep_top_k[50][0]
-            if self.skip_layer_range[1] == 0 and (self.last_best_cand == best or self.epoch > 4):
-                self.skip_layer_range[1] = self.max_prun / 5
-            elif 0 < self.skip_layer_range[1] < self.max_prun:
-                self.skip_layer_range[1] += self.max_prun / 5
-            if self.skip_layer_range[0] == 0 and self.epoch > 5:
-                self.skip_layer_range[0] = self.min_prun
-            self.last_best_cand = best
-            logger.log('skip_layer_range_left = {} , skip_layer_range_right {}'.format(*self.skip_layer_range))
-            if self.epoch + 1 == self.max_epochs:
-                break
-            self.candidates = self.get_mutation(self.select_num, self.mutation_num, self.m_prob)
-            self.candidates += self.get_cross(self.select_num, self.crossover_num)
-            self.get_random(self.population_num)
-            self.epoch += 1
-        self.flush_pending()
+    def _initial_candidate(self, steps):
+        return {'timesteps': steps, 'skip_layers': [[] for _ in steps]}
+
+    def _after_selection(self):
+        """The progressive skip-layer range (:684-692), from this epoch's best candidate."""
+        best = self.keep_top_k[50][0]
+        if self.skip_layer_range[1] == 0 and (self.last_best_cand == best or self.epoch > 4):
+            self.skip_layer_range[1] = self.max_prun / 5
+        elif 0 < self.skip_layer_range[1] < self.max_prun:
+            self.skip_layer_range[1] += self.max_prun / 5
+        if self.skip_layer_range[0] == 0 and self.epoch > 5:
+            self.skip_layer_range[0] = self.min_prun
+        self.last_best_cand = best
+        logger.log('skip_layer_range_left = {} , skip_layer_range_right {}'.format(*self.skip_layer_range))

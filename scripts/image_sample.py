@@ -16,15 +16,14 @@ import sys
 import time
 
 import numpy as np
-import torch as th
 import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import dist_util, logger  # noqa: E402
-from autodiffusion_amd.evaluate import CandidateEvaluator, merge_policy  # noqa: E402
-from autodiffusion_amd.script_util import (add_dict_to_argparser, args_to_dict, create_model_and_diffusion,  # noqa: E402
-                                           model_and_diffusion_defaults)
+from autodiffusion_amd.evaluate import CandidateEvaluator  # noqa: E402
+from autodiffusion_amd.script_util import (add_dict_to_argparser, candidate_from_flags, gather_batches,  # noqa: E402
+                                           load_model_and_diffusion, model_and_diffusion_defaults)
 
 
 def create_argparser():
@@ -42,58 +41,18 @@ def main(argv=None):
     dist_util.setup_dist()
     logger.configure(args.save_dir or None)
 
-    logger.log("creating model and diffusion...")
-    model, diffusion = create_model_and_diffusion(**args_to_dict(args, model_and_diffusion_defaults().keys()))
-    model.to(dist_util.dev())
-    if args.model_path:
-        model.load_state_dict(dist_util.load_state_dict(args.model_path, map_location="cpu"))
-        logger.log('load from: ' + args.model_path)
-    else:
-        model.randomize_(1234)
-    if args.use_fp16:
-        model.convert_to_fp16()
-    model.eval()
+    model, diffusion = load_model_and_diffusion(args, log_source=True)
 
     ev = CandidateEvaluator(model, diffusion, None, image_size=args.image_size, use_ddim=args.use_ddim,
                             clip_denoised=args.clip_denoised, class_cond=args.class_cond, device=dist_util.dev())
-    steps = sorted(eval(args.use_timestep)) if args.use_timestep is not None else sorted(diffusion.use_timesteps)
-    if args.skip_layers is not None:
-        ev.set_candidate({"timesteps": steps, "skip_layers": eval(args.skip_layers)})
-    else:
-        ev.set_candidate(steps)
+    ev.set_candidate(candidate_from_flags(args, diffusion))
 
     logger.log("sampling...")
     world, rank = dist_util.get_world_size(), dist_util.get_rank()
-    all_images, all_labels = [], []
-    batch_idx = 0
     t1 = time.time()
     # --merge_batches K (0 = auto: evaluate.merge_policy): K of the reference's batches per
     # pass over the network, bitwise the same images (scripts/classifier_sample.py)
-    rounds = -(-args.num_samples // (args.batch_size * world))
-    merge, per_pass = merge_policy(args.image_size, args.batch_size, int(getattr(args, "merge_batches", 0) or 0), rounds)
-    if merge > 1:
-        logger.log(f"evaluating {merge} batches of {args.batch_size} per pass ({per_pass} images per pass; bitwise the images of separate passes)")
-    while len(all_images) * args.batch_size < args.num_samples:
-        k = max(1, min(merge, rounds - batch_idx))
-        seeds = [args.seed * 1000003 + (batch_idx + j) * world + rank for j in range(k)]
-        if k == 1:
-            samples, labels = [ev.sample_batch(args.batch_size, seed=seeds[0])], [ev.last_classes]
-        else:
-            samples = ev.sample_batches(args.batch_size, seeds)
-            labels = list(ev.last_classes.split(args.batch_size, 0))
-        for sample, classes in zip(samples, labels):
-            sample, classes = sample.contiguous(), classes.contiguous()
-            if world > 1:
-                gathered = [th.zeros_like(sample) for _ in range(world)]
-                gathered_labels = [th.zeros_like(classes) for _ in range(world)]
-                dist.all_gather(gathered, sample)
-                dist.all_gather(gathered_labels, classes)
-            else:
-                gathered, gathered_labels = [sample], [classes]
-            all_images.extend([s.cpu().numpy() for s in gathered])
-            all_labels.extend([lab.cpu().numpy() for lab in gathered_labels])
-            batch_idx += 1
-            logger.log("created " + str(len(all_images) * args.batch_size) + " samples")
+    all_images, all_labels = gather_batches(ev, args)
     sample_time = time.time() - t1
     arr = np.concatenate(all_images, axis=0)[: args.num_samples]
     label_arr = np.concatenate(all_labels, axis=0)[: args.num_samples]

@@ -21,7 +21,8 @@ candidates over ranks; otherwise every candidate's images are sharded and the st
 
 ``--use_dynamic_unet True`` runs the joint timestep + layer-skip search of
 search_dynamic_unet_imagenet64_classifier_guidance_progressive.py (flags ``--index_step``, ``--max_prun``,
-``--min_prun`` as there, :717-748): candidates are {'timesteps': [...], 'skip_layers': [[...], ...]}.
+``--min_prun`` as there, :717-748): candidates are {'timesteps': [...], 'skip_layers': [[...], ...]}.  List flags
+(``--search_space``) and ``--index_step`` are read as literals: ``--index_step 232``, not ``4*58``.
 """
 import argparse
 import importlib
@@ -37,9 +38,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import dist_util, logger  # noqa: E402
 from autodiffusion_amd.schedule import space_timesteps  # noqa: E402
-from autodiffusion_amd.script_util import (add_dict_to_argparser, args_to_dict, classifier_defaults,  # noqa: E402
-                                           create_classifier, create_model_and_diffusion,
-                                           model_and_diffusion_defaults)
+from autodiffusion_amd.evaluate import batch_plan, graph_auto, parse_int_list  # noqa: E402
+from autodiffusion_amd.script_util import (add_dict_to_argparser, classifier_defaults, load_classifier,  # noqa: E402
+                                           load_model_and_diffusion, model_and_diffusion_defaults, str2bool)
 from autodiffusion_amd.search import DynamicEvolutionSearcher, EvolutionSearcher  # noqa: E402
 
 
@@ -62,7 +63,7 @@ def create_argparser():
 def build_search_space(args, diffusion):
     if args.search_space == "":
         return None
-    core = sorted(eval(args.search_space))
+    core = sorted(parse_int_list(args.search_space, "--search_space"))
     if args.use_ddim_init_x:
         core += list(space_timesteps(diffusion.original_num_steps, ("ddim" if args.use_ddim else "") + str(args.time_step)))
     r = int(diffusion.original_num_steps / 100)
@@ -74,10 +75,9 @@ def build_search_space(args, diffusion):
 
 def main(argv=None):
     args = create_argparser().parse_args(argv)
-    from autodiffusion_amd.script_util import str2bool
-    from autodiffusion_amd.evaluate import graph_auto, merge_policy
-    # `auto` is decided on the MERGED batch -- the pass that is launched is what a graph captures
-    per_pass = merge_policy(args.image_size, args.batch_size, args.merge_batches, -(-args.num_samples // args.batch_size))[1]
+    # `auto` is decided on the MERGED batch -- the pass that is launched is what a graph captures (the plan of ONE rank taking
+    # every batch: this runs before the process group exists)
+    per_pass = len(batch_plan(args.num_samples, args.batch_size, 1, 0, args.image_size, args.merge_batches)[0]) * args.batch_size
     args.use_graph = graph_auto(args.image_size, per_pass) if str(args.use_graph).lower() == "auto" else str2bool(args.use_graph)
     os.environ.setdefault("MASTER_PORT", args.MASTER_PORT)
     torch.manual_seed(args.seed)
@@ -86,24 +86,8 @@ def main(argv=None):
     dist_util.setup_dist()
     logger.configure(args.save_dir or None)
     logger.log(str(args))
-    logger.log("creating model and diffusion...")
-    model, diffusion = create_model_and_diffusion(**args_to_dict(args, model_and_diffusion_defaults().keys()))
-    model.to(dist_util.dev())
-    if args.model_path:
-        model.load_state_dict(dist_util.load_state_dict(args.model_path, map_location="cpu"))
-    else:
-        model.randomize_(1234)
-    if args.use_fp16:
-        model.convert_to_fp16()
-    model.eval()
-    classifier = None
-    if not args.without_classifier:
-        classifier = create_classifier(**args_to_dict(args, classifier_defaults().keys()))
-        classifier.to(dist_util.dev())
-        if args.classifier_path:
-            classifier.load_state_dict(dist_util.load_state_dict(args.classifier_path, map_location="cpu"))
-        else:
-            classifier.randomize_(4321)
+    model, diffusion = load_model_and_diffusion(args)
+    classifier = load_classifier(args)
     if args.features:
         mod, fn = args.features.split(":")
         features, dim = getattr(importlib.import_module(mod), fn)(dist_util.dev())
