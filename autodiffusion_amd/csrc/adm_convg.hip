@@ -392,8 +392,10 @@ resize_bilinear_kernel(const void* __restrict__ in, uint16_t* __restrict__ out, 
     uint4 val = make_uint4(0, 0, 0, 0);
     if (sg == 0) {
       const int ox = (int)(pix % ow), oy = (int)((pix / ow) % oh), img = (int)(pix / ((long long)ow * oh));
-      float sy = half_pixel ? ((float)oy + 0.5f) * ry - 0.5f : (float)oy * ry;
-      float sx = half_pixel ? ((float)ox + 0.5f) * rx - 0.5f : (float)ox * rx;
+      // half-pixel centres in ONE fused multiply-add, as torch's F.interpolate computes them (what the compiler's contraction
+      // already made of the plain expression: spelled out because tests/inception_replay.py pins the coordinate to the bit)
+      float sy = half_pixel ? fmaf((float)oy + 0.5f, ry, -0.5f) : (float)oy * ry;
+      float sx = half_pixel ? fmaf((float)ox + 0.5f, rx, -0.5f) : (float)ox * rx;
       sy = fmaxf(sy, 0.0f);
       sx = fmaxf(sx, 0.0f);
       const int y0 = min((int)sy, h - 1), x0 = min((int)sx, w - 1);

@@ -6,6 +6,8 @@ holds an Inception output.  What IS checked here: every HIP layer against the pl
 the assembled network against the CPU restatement of the published architecture (oracle/inception.py) on synthetic
 weights.  Tolerances: operands rounded to the 16-bit type on both sides for the single layers (summation order + the
 output rounding remain: 4e-3 Frobenius); the ~50-layer network accumulates that rounding: 5e-3 in fp16, 4e-2 in bf16.
+The per-element checks -- every launch of the network at its shipped shape and batch against float64, within bounds derived from
+the arithmetic, and the assembled network layer by layer -- are tests/test_hip_inception_replay.py (tests/inception_replay.py).
 """
 import numpy as np
 import pytest
@@ -75,16 +77,21 @@ def test_conv2d_matches_torch(ops, dt, cin, cout, kh, kw, stride, pad, h, w):
     assert (big[..., :8] == 7).all() and (big[..., 8 + cout:] == 7).all()   # neighbours untouched
 
 
-@pytest.mark.parametrize("k,stride,pad,mode", [(3, 2, 0, "max"), (3, 1, 1, "avg"), (3, 1, 1, "max"), (2, 2, 0, "avg")])
-def test_pool2d_matches_torch(ops, k, stride, pad, mode):
+POOLS = [(3, 2, 0, "max"), (3, 1, 1, "avg"), (3, 1, 1, "max"), (2, 2, 0, "avg")]
+
+
+# both types; the fp16 cases keep the ids they had before bf16 joined them
+@pytest.mark.parametrize("k,stride,pad,mode,dt", [c + (torch.float16,) for c in POOLS] + [c + (torch.bfloat16,) for c in POOLS],
+                         ids=["%d-%d-%d-%s" % c for c in POOLS] + ["%d-%d-%d-%s-bf16" % c for c in POOLS])
+def test_pool2d_matches_torch(ops, k, stride, pad, mode, dt):
     x = rnd((2, 40, 13, 11), 5)
-    xd = nhwc(x, torch.float16)
-    ref = (F.max_pool2d(q(x, torch.float16), k, stride, pad) if mode == "max"
-           else F.avg_pool2d(q(x, torch.float16), k, stride, pad, count_include_pad=False))
+    xd = nhwc(x, dt)
+    ref = (F.max_pool2d(q(x, dt), k, stride, pad) if mode == "max"
+           else F.avg_pool2d(q(x, dt), k, stride, pad, count_include_pad=False))
     got = ops.pool2d(xd, k, stride, pad, mode).float().cpu().permute(0, 3, 1, 2)
     assert got.shape == ref.shape
-    torch.testing.assert_close(got, q(ref, torch.float16), rtol=2e-3, atol=2e-3)
-    big = torch.zeros((2, ref.shape[2], ref.shape[3], 64), dtype=torch.float16, device=DEV)
+    torch.testing.assert_close(got, q(ref, dt), rtol=2e-3, atol=2e-3)
+    big = torch.zeros((2, ref.shape[2], ref.shape[3], 64), dtype=dt, device=DEV)
     ops.pool2d(xd, k, stride, pad, mode, out=big[..., 16:56])
     assert torch.equal(big[..., 16:56].float().cpu().permute(0, 3, 1, 2), got) and (big[..., :16] == 0).all()
 
@@ -95,18 +102,22 @@ def test_global_avgpool(ops):
     torch.testing.assert_close(got, q(x, torch.float16).mean((2, 3)), rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("size", [64, 256, 299, 512])
-def test_resize_matches_both_conventions(ops, size):
+SIZES = [64, 256, 299, 512]
+
+
+@pytest.mark.parametrize("size,dt", [(s, torch.float16) for s in SIZES] + [(s, torch.bfloat16) for s in SIZES],
+                         ids=[str(s) for s in SIZES] + ["%d-bf16" % s for s in SIZES])
+def test_resize_matches_both_conventions(ops, size, dt):
     from oracle import inception as oi
     g = torch.Generator().manual_seed(size)
     u8 = torch.randint(0, 256, (2, size, size - 3, 3), generator=g, dtype=torch.uint8)
     ref = oi.prepare(u8, "tf1")                                     # TensorFlow-1 ResizeBilinear, (x - 128) / 128
-    got = ops.resize_bilinear(u8.to(DEV), 299, 299, 32, "u8_nhwc", False, 1 / 128.0, -1.0, torch.float16)
+    got = ops.resize_bilinear(u8.to(DEV), 299, 299, 32, "u8_nhwc", False, 1 / 128.0, -1.0, dt)
     assert (got[..., 3:] == 0).all()
     torch.testing.assert_close(got[..., :3].float().cpu().permute(0, 3, 1, 2), ref, rtol=0, atol=2e-3)
     f = torch.rand((2, 3, size, size + 5), generator=g)
     ref = oi.prepare(f, "pt")                                       # torch bilinear, align_corners=False, 2x - 1
-    got = ops.resize_bilinear(f.to(DEV), 299, 299, 32, "f32_nchw", True, 2.0, -1.0, torch.float16)
+    got = ops.resize_bilinear(f.to(DEV), 299, 299, 32, "f32_nchw", True, 2.0, -1.0, dt)
     torch.testing.assert_close(got[..., :3].float().cpu().permute(0, 3, 1, 2), ref, rtol=0, atol=2e-3)
 
 
