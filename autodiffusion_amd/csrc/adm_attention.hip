@@ -39,11 +39,6 @@ __device__ unsigned long long adm_attn_timing_buf[8 * 65536];
 #define ATT_TEND() do {} while (0)
 #endif
 
-#ifndef ADM_ATTN_ABL
-#define ADM_ATTN_ABL 0   // diagnostic builds only: drop one piece of the tile loop (results are then wrong) to price it
-#endif
-#define ABL_KEEP(x) asm volatile("" ::"v"(x))
-
 struct AttnK {
   const uint16_t* qkv; uint16_t* out; float* lse;
   const uint16_t* kv;      // keys / values: [N][kv_rows][Ckv], the first Tk rows of an image are attended to
@@ -55,7 +50,7 @@ struct AttnK {
 
 // Second build of the tuned kernel (round 2).  Per 64-key tile a wave issues 32 MFMAs (512 cycles of matrix pipe); the
 // first build also issued ~130 VALU instructions + 32 v_exp_f32 around them, at 164 registers = 3 waves per SIMD.
-// Ablations on MI355X (tools/attn_ablate.py: drop one piece, time the rest) price every piece of the loop at 15-25 % of
+// Ablations on MI355X (the ablation builds of round 2, profiles/r02/attn_fwd_ablations_T1024_H6.log: drop one piece, time the rest) priced every piece of the loop at 15-25 % of
 // its time with little overlap between them: the loop is LATENCY-bound (LDS round trips, MFMA drain, global loads,
 // barrier), so what pays is fewer dependent instructions per tile at the same or higher occupancy:
 //   * the running-max subtraction leaves the per-tile stream: -m is the INITIAL ACCUMULATOR of the S chains, so the
@@ -76,11 +71,8 @@ struct AttnK {
 // launch bounds: >= 2 waves per SIMD for every width caps the kernel at 256 registers, so hipcc keeps the MFMA accumulators in
 // VGPRs (with no bound it parks them in AGPRs and copies them out with v_accvgpr_read: slower, and the 80-wide
 // instantiation then returned wrong scores for one query tile); 3 waves (168 registers) up to 64-wide heads
-#ifndef ADM_ATTN_WAVES
-#define ADM_ATTN_WAVES 3
-#endif
 template <int D>
-__global__ void __launch_bounds__(256, D <= 64 ? ADM_ATTN_WAVES : 2)
+__global__ void __launch_bounds__(256, D <= 64 ? 3 : 2)
 attn_kernel(const AttnK p) {
   constexpr int KS = D / 32;   // 32-deep k-steps of QK^T
   constexpr bool R16 = (D % 32) == 16;  // plus one 16-deep step (v_mfma_f32_16x16x16_bf16): head widths 48, 80, 112
@@ -207,12 +199,8 @@ attn_kernel(const AttnK p) {
       const int slot = kt % NSET;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks)
-#if ADM_ATTN_ABL == 5
-        kfr[slot][ks] = qf[0][ks];
-#else
         kfr[slot][ks] = *reinterpret_cast<const adm_h8*>(
             &Kc[(kt * 16 + lc) * KROW + (DMA ? ((ks * 4 + lq) ^ (lc & 7)) * 8 : ks * 32 + lq * 8)]);
-#endif
       if constexpr (R16) kfr16[slot] = *reinterpret_cast<const adm_s16x4*>(&Kc[(kt * 16 + lc) * KROW + KS * 32 + lq * 4]);
     };
     __builtin_amdgcn_sched_barrier(0);
@@ -247,11 +235,7 @@ attn_kernel(const AttnK p) {
   auto tile = [&](int kt0, auto rag_, auto first_) {
     constexpr bool RAG = decltype(rag_)::value, FIRST = decltype(first_)::value;
     const int k0 = kt0 * KT;
-#if ADM_ATTN_ABL == 6
-    const bool next = false;
-#else
     const bool next = kt0 + 1 < ntiles;
-#endif
     if (next) {
       if constexpr (DMA) {
         dma_tile(kt0 + 1);
@@ -272,11 +256,7 @@ attn_kernel(const AttnK p) {
     auto vread = [&](int dt, int slot) {
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
-#if ADM_ATTN_ABL == 4
-        vfr[slot][kb] = qf[kb][0];
-#else
         vfr[slot][kb] = DMA ? adm_tr_frag_swz(Vc, kb * 32, dt * 16, lc, lq) : adm_tr_frag(Vc, KROW, kb * 32, dt * 16, lc, lq);
-#endif
     };
     vread(0, 0);
     __builtin_amdgcn_sched_barrier(0);
@@ -302,11 +282,7 @@ attn_kernel(const AttnK p) {
         for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[kt][qt][r]);
       mxl[qt] = mx;
     }
-#if ADM_ATTN_ABL == 8
-    if (FIRST) {
-#else
     if (FIRST || __any(fmaxf(mxl[0], mxl[1]) > thr_raw)) {
-#endif
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
         const float mx = adm_quarter_max(mxl[qt]);
@@ -335,13 +311,7 @@ attn_kernel(const AttnK p) {
         adm_h8 f;
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-#if ADM_ATTN_ABL == 1
-          f[e] = __builtin_bit_cast(adm_elem_t, (uint16_t)(__float_as_uint(st[2 * kb + (e >> 2)][qt][e & 3]) >> 16));
-#elif ADM_ATTN_ABL == 9
-          f[e] = (adm_elem_t)(st[2 * kb + (e >> 2)][qt][e & 3] * p.scale_log2);
-#else
           f[e] = (adm_elem_t)__builtin_amdgcn_exp2f(st[2 * kb + (e >> 2)][qt][e & 3] * p.scale_log2);
-#endif
         pf[qt][kb] = f;
       }
     // ---- O^T += V^T . P^T and l += 1 . P^T; contraction slot k = 8*lq + e  <->  key kb*32 + 16*(e>>2) + 4*lq + (e&3)
@@ -370,9 +340,7 @@ attn_kernel(const AttnK p) {
       vr.store(Vs[(kt0 + 1) & 1], KROW, tid);
     }
     ATT_T(6);
-#if ADM_ATTN_ABL != 7
     __syncthreads();
-#endif
     ATT_T(7);
   };
   using TT = std::true_type;

@@ -41,28 +41,8 @@ namespace {
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
-#ifndef ADM_FOLD_ABL
-#define ADM_FOLD_ABL 0
-#endif
-#ifndef ADM_CONV_1X1_NOEXIT
-#define ADM_CONV_1X1_NOEXIT 1   // 1x1 loop of the 128-pixel tiles without early exits (0: the exits, for A/B builds)
-#endif
-#ifndef ADM_CONV_1X1_DEEP
-#define ADM_CONV_1X1_DEEP 4   // 1x1 loop of the 128-pixel tiles: 4 (or 8) activation chunks in flight (8: weight K-steps too); 0: two (A/B builds). Same box, SD: 63.7 (0) / 64.2 (4) / 64.0 (8) latents/s
-#endif
-#ifndef ADM_CONV_FOLD_RING
-#define ADM_CONV_FOLD_RING 2   // skip-connection fold: activation chunks in flight in registers (2; 3 measured 1-5 % slower per tile: profiles/r03/conv_tile_timing_fold.log)
-#endif
-#ifndef ADM_CONV_RD
-#define ADM_CONV_RD 2    // 1x1: activation stages in flight (register ring)
-#endif
-#ifndef ADM_CONV_KS2
-#define ADM_CONV_KS2 0   // 1: 1x1 convs use 64-channel stages where the channel counts allow
-#endif
 constexpr int KC = 32;           // input channels per chunk (= one MFMA K)
-// LDS bytes per halo pixel: 64 data bytes per K-step of the stage + 32 pad (conflict-free ds_read_b128 fragments)
-constexpr int conv_rowb(int ks) { return 64 * ks + 32; }
-constexpr int ROWB = conv_rowb(1);
+constexpr int ROWB = 64 + 32;    // LDS bytes per halo pixel: 64 data bytes + 32 pad (conflict-free ds_read_b128 fragments)
 constexpr int TI_MAX = 4;
 constexpr unsigned OOB = 0x80000000u;  // buffer-load offset beyond num_records -> returns 0
 
@@ -125,14 +105,14 @@ constexpr int conv_smem_bytes() {
 // LDS map of conv_kernel: halo[0] | halo[1] ... | affine tables.  The epilogue's output staging (whole tile,
 // bf16 rows + 16 B pad) and the statistics reduction overlay halo[1] onwards, never halo[0] or the affine
 // tables: those receive the NEXT tile's first chunk while the current tile is being stored.
-template <int NT, int BN, int HALO, int BM, int KS>
+template <int NT, int BN, int HALO, int BM>
 struct ConvLds {
-  static constexpr int HB = ((HALO * 4 * KS + NT - 1) / NT) * (NT / (4 * KS)) * conv_rowb(KS);  // one halo buffer (whole passes)
+  static constexpr int HB = ((HALO * 4 + NT - 1) / NT) * (NT / 4) * ROWB;  // one halo buffer (whole passes)
   static constexpr int STG = BM * (BN * 2 + 16);             // output staging
   static constexpr int RED = NT * 64;                        // statistics reduction [NT*8/BN rows][BN][2] floats
   static constexpr int OVL = (STG > RED ? STG : RED) > HB ? (STG > RED ? STG : RED) : HB;
   static constexpr int ABUF = (HB + OVL + 15) & ~15;
-  static constexpr int BYTES = ABUF + 2 * 2 * TI_MAX * 32 * KS * 4;   // a | b, two stages each
+  static constexpr int BYTES = ABUF + 2 * 2 * TI_MAX * KC * 4;   // a | b, two stages each
 };
 
 #ifdef ADM_CONV_TIMING
@@ -186,12 +166,10 @@ conv_kernel(const ConvK p) {
   constexpr int NT = 64 * WM * WN;
   constexpr int BM = WM * TM * 16;
   constexpr int BN = WN * TN * 16;
-  // a STAGE is what one halo buffer holds: KS 32-channel K-steps of every halo pixel (3x3: KS = 1, the 9 taps
-  // give a stage its depth; 1x1: KS = 2 where the channel counts allow, or the loop is all barriers)
-  constexpr int KCS = KC * KS;             // channels per stage
-  constexpr int SEGP = 4 * KS;             // 16-byte segments per halo pixel
-  constexpr int SEGSH = KS == 1 ? 2 : 3;   // log2(SEGP)
-  constexpr int ROWB = conv_rowb(KS);      // LDS bytes per halo pixel
+  // KS (K-steps per halo stage) is always 1: it stays a parameter only because the kernel symbol names in profiles/ and tools/ carry it
+  static_assert(KS == 1, "one 32-channel K-step per halo stage");
+  constexpr int SEGP = 4;                  // 16-byte segments per halo pixel (one KC-channel chunk)
+  constexpr int SEGSH = 2;                 // log2(SEGP)
   constexpr int PASSES = (HALO * SEGP + NT - 1) / NT;
   // OCC == 1: the ONE-WAVE-PER-SIMD build of the 256-pixel tile (4 waves of 128 pixels x TN * 16 channels, 512 registers each:
   // the accumulators live in the AGPR half).  No partner wave hides anything, so the K loop is ONE software-pipelined stream per
@@ -199,13 +177,12 @@ conv_kernel(const ConvK p) {
   // of their MFMAs across tap boundaries, the GroupNorm affine of a lane's 8 channels rides in registers, and the prologue
   // VALU / load / LDS-write instructions are dealt two per MFMA gap (sched_group_barrier) instead of being fenced off
   constexpr bool ONEW = OCC == 1;
-  static_assert(!ONEW || (TAPS == 9 && HALO == 324 && WM == 2 && WN == 2 && KS == 1), "the one-wave-per-SIMD build is the 3x3 256-pixel tile");
+  static_assert(!ONEW || (TAPS == 9 && HALO == 324 && WM == 2 && WN == 2), "the one-wave-per-SIMD build is the 3x3 256-pixel tile");
   constexpr bool T3 = TAPS == 9 || TAPS == 4;   // 3x3 geometry; TAPS == 4: an up-conv phase (4 of the 9 taps live)
   constexpr bool UPPH = TAPS == 4;
   constexpr int PAD = T3 ? 1 : 0;
   constexpr int SGROUPS = stat_groups<BM>();  // statistics slabs per tile
-  using Lds = ConvLds<NT, BN, HALO, BM, KS>;
-  static_assert(KS == 1 || (KS == 2 && TAPS == 1), "multi-step stages are a 1x1 feature");
+  using Lds = ConvLds<NT, BN, HALO, BM>;
   static_assert(TAPS == 1 || PASSES <= (T3 ? 9 : TAPS) - 1, "halo passes must fit in the taps of one chunk");
   static_assert(PASSES <= 8, "ti_pack holds 8 passes");
 
@@ -236,8 +213,8 @@ conv_kernel(const ConvK p) {
   const int HP = p.TI * HPI;
   const int Cin = p.C0 + p.C1;
   const int HWimg = p.H * p.W;
-  const int chunks = Cin / KCS;            // stages of the K loop
-  const int c0chunks = p.C0 / KCS;
+  const int chunks = Cin / KC;             // stages of the K loop
+  const int c0chunks = p.C0 / KC;
   const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.wbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, p.Cout * 4, 0x00020000);
 
@@ -333,7 +310,7 @@ conv_kernel(const ConvK p) {
     const int seg_s = tid_s & (SEGP - 1), lane_s = tid_s & 63;
     {
       const bool first = cb < c0chunks;   // the tile's first chunk (chunk cb: 0 unless the K loop is split)
-      const int cs = first ? p.C0 : p.C1, co = (first ? cb : cb - c0chunks) * KCS;
+      const int cs = first ? p.C0 : p.C1, co = (first ? cb : cb - c0chunks) * KC;
       const __amdgpu_buffer_rsrc_t rsf = first ? rs0 : rs1;
 #pragma unroll
       for (int ps = 0; ps < PASSES; ++ps) {
@@ -342,17 +319,17 @@ conv_kernel(const ConvK p) {
       }
     }
     // ... and the affine tables of stages 0 and 1 (they are staged two stages ahead): the LDS table is
-    // a[buf][ti][KCS] followed by b[buf][ti][KCS]; each half is 2*KCS lanes x 16 B, lane-linear, so KS
-    // wave-instructions move it: waves 0..KS-1 the a half, waves KS..2KS-1 the b half (32-bit offsets into
+    // a[buf][ti][KC] followed by b[buf][ti][KC]; each half is 2*KC lanes x 16 B, lane-linear, so one
+    // wave-instruction moves it: wave 0 the a half, wave 1 the b half (32-bit offsets into
     // a descriptor over the whole [N][Cin] table)
     if constexpr (PRO != 0 && !ONEW) {
-      if (wave < 2 * KS) {
-        const int half = wave / KS, idx = (wave % KS) * 64 + lane_s;  // idx = (buf * TI_MAX + ti) * (KCS/4) + part
+      if (wave < 2) {
+        const int half = wave, idx = lane_s;  // idx = (buf * TI_MAX + ti) * (KC/4) + part
         const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)(half == 0 ? p.aa : p.ab), 0, p.N * Cin * 4, 0x00020000);
-        const int buf = idx / (TI_MAX * (KCS / 4)), ti = (idx / (KCS / 4)) % TI_MAX, part = idx % (KCS / 4);
+        const int buf = idx / (TI_MAX * (KC / 4)), ti = (idx / (KC / 4)) % TI_MAX, part = idx % (KC / 4);
         const int n = min(img0 + ti, p.N - 1);
-        const unsigned voff = ti < p.TI ? (unsigned)(n * Cin + min(cb + buf, ce - 1) * KCS + part * 4) * 4u : OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_ptr_t)(abuf + half * (2 * TI_MAX * KCS) + (wave % KS) * 256), 16, (int)voff, 0, 0, 0);
+        const unsigned voff = ti < p.TI ? (unsigned)(n * Cin + min(cb + buf, ce - 1) * KC + part * 4) * 4u : OOB;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_ptr_t)(abuf + half * (2 * TI_MAX * KC)), 16, (int)voff, 0, 0, 0);
       }
     }
 #pragma unroll
@@ -367,7 +344,7 @@ conv_kernel(const ConvK p) {
   // activation segment `ps` of chunk c (the descriptor select is scalar; out-of-image lanes read zero)
   auto halo_load = [&](int c, int ps) -> uint4 {
     const bool first = c < c0chunks;
-    const int cs = first ? p.C0 : p.C1, co = (first ? c : c - c0chunks) * KCS;
+    const int cs = first ? p.C0 : p.C1, co = (first ? c : c - c0chunks) * KC;
     const __amdgpu_buffer_rsrc_t rs = first ? rs0 : rs1;
     const unsigned voff = pixrel[ps] >= 0 ? (unsigned)(pixrel[ps] * cs + co + seg * 8) * 2u : OOB;
     return bufload16(rs, voff, 0);
@@ -377,16 +354,16 @@ conv_kernel(const ConvK p) {
   [[maybe_unused]] auto halo_load_pad = [&](int c, int lastc, int ps) -> uint4 {
     const int cc = min(c, lastc);
     const bool first = cc < c0chunks;
-    const int cs = first ? p.C0 : p.C1, co = (first ? cc : cc - c0chunks) * KCS;
+    const int cs = first ? p.C0 : p.C1, co = (first ? cc : cc - c0chunks) * KC;
     const __amdgpu_buffer_rsrc_t rs = first ? rs0 : rs1;
     const unsigned voff = (pixrel[ps] >= 0 && c <= lastc) ? (unsigned)(pixrel[ps] * cs + co + seg * 8) * 2u : OOB;
     return bufload16(rs, voff, 0);
   };
   // FOLD: segment `ps` of chunk k of the skip_connection's input (same halo geometry: only its centre tap is used), and its raw park
   [[maybe_unused]] auto fold_load = [&](int k, int ps) -> uint4 {
-    const int f0chunks = p.FC0 / KCS;
+    const int f0chunks = p.FC0 / KC;
     const bool first = k < f0chunks;
-    const int cs = first ? p.FC0 : p.FC1, co = (first ? k : k - f0chunks) * KCS;
+    const int cs = first ? p.FC0 : p.FC1, co = (first ? k : k - f0chunks) * KC;
     const __amdgpu_buffer_rsrc_t rs = first ? rs2 : rs3;
     const unsigned voff = pixrel[ps] >= 0 ? (unsigned)(pixrel[ps] * cs + co + seg * 8) * 2u : OOB;
     return bufload16(rs, voff, 0);
@@ -394,14 +371,14 @@ conv_kernel(const ConvK p) {
   [[maybe_unused]] auto raw_write = [&](uint4 v, int ps, int buf) {
     *reinterpret_cast<uint4*>(halo + buf * Lds::HB + ps * (NT / SEGP) * ROWB + hslot) = v;
   };
-  // affine table of stage c: threads < TI * KCS/2 fetch one float4 of a (parts < KCS/4) or b
-  constexpr int APT = KCS / 2;             // threads per image of the tile
+  // affine table of stage c: threads < TI * KC/2 fetch one float4 of a (parts < KC/4) or b
+  constexpr int APT = KC / 2;             // threads per image of the tile
   auto affine_load = [&](int c, int im0) -> float4 {
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (PRO != 0) {
       if (tid < p.TI * APT) {
         const int n = min(im0 + tid / APT, p.N - 1), part = tid % APT;
-        v = *reinterpret_cast<const float4*>((part < APT / 2 ? p.aa : p.ab) + (long long)n * Cin + c * KCS + (part % (APT / 2)) * 4);
+        v = *reinterpret_cast<const float4*>((part < APT / 2 ? p.aa : p.ab) + (long long)n * Cin + c * KC + (part % (APT / 2)) * 4);
       }
     }
     return v;
@@ -410,7 +387,7 @@ conv_kernel(const ConvK p) {
     if constexpr (PRO != 0) {
       if (tid < p.TI * APT) {
         const int part = tid % APT;
-        *reinterpret_cast<float4*>(abuf + (part < APT / 2 ? 0 : 2 * TI_MAX * KCS) + (buf * TI_MAX + tid / APT) * KCS + (part % (APT / 2)) * 4) = v;
+        *reinterpret_cast<float4*>(abuf + (part < APT / 2 ? 0 : 2 * TI_MAX * KC) + (buf * TI_MAX + tid / APT) * KC + (part % (APT / 2)) * 4) = v;
       }
     }
   };
@@ -419,7 +396,7 @@ conv_kernel(const ConvK p) {
   [[maybe_unused]] float4 afr[4];
   auto affine_regs = [&](int c, int im0) {
     if constexpr (PRO != 0) {
-      const long long o = (long long)min(im0, p.N - 1) * Cin + c * KCS + seg * 8;
+      const long long o = (long long)min(im0, p.N - 1) * Cin + c * KC + seg * 8;
       afr[0] = *reinterpret_cast<const float4*>(p.aa + o);
       afr[1] = *reinterpret_cast<const float4*>(p.aa + o + 4);
       afr[2] = *reinterpret_cast<const float4*>(p.ab + o);
@@ -437,11 +414,11 @@ conv_kernel(const ConvK p) {
         *reinterpret_cast<float4*>(b8 + 4) = afr[3];
       } else {
       const int ti = (ti_pack >> (4 * ps)) & 15;
-      const float* ab = abuf + (buf * TI_MAX + ti) * KCS + seg * 8;
+      const float* ab = abuf + (buf * TI_MAX + ti) * KC + seg * 8;
       *reinterpret_cast<float4*>(a8) = *reinterpret_cast<const float4*>(ab);
       *reinterpret_cast<float4*>(a8 + 4) = *reinterpret_cast<const float4*>(ab + 4);
-      *reinterpret_cast<float4*>(b8) = *reinterpret_cast<const float4*>(ab + 2 * TI_MAX * KCS);
-      *reinterpret_cast<float4*>(b8 + 4) = *reinterpret_cast<const float4*>(ab + 2 * TI_MAX * KCS + 4);
+      *reinterpret_cast<float4*>(b8) = *reinterpret_cast<const float4*>(ab + 2 * TI_MAX * KC);
+      *reinterpret_cast<float4*>(b8 + 4) = *reinterpret_cast<const float4*>(ab + 2 * TI_MAX * KC + 4);
       }
       uint32_t u[4] = {v.x, v.y, v.z, v.w};
       const bool valid = pixrel[ps] >= 0;
@@ -499,13 +476,14 @@ conv_kernel(const ConvK p) {
   // The narrow register loads (first weight fragments: 3x3 ring of 3 K-steps, two in flight; 1x1 ring of
   // 4, three in flight, plus the activation segments of chunk 1; the bias fragment the accumulators start
   // from) go out once the accumulators' registers are free.
-  // 1x1 loop of the 128-pixel tiles (never split-K: chunk 0 first): DEEPN activation chunks and weight K-steps in flight instead of
-  // two / three -- a step of these tiles is 8-12 MFMAs per wave, so two steps of prefetch distance are far less than the load latency
-  constexpr int DEEPN = ADM_CONV_1X1_DEEP;    // 0: off, else 4 or 8
-  constexpr bool DEEP1 = DEEPN != 0 && TAPS == 1 && KS == 1 && TM == 4 && !COLD && ADM_CONV_RD == 2;
-  constexpr int WRING = (TAPS == 9 || TAPS == 4) ? 3 : (KS == 1 ? (DEEP1 && DEEPN == 8 ? 8 : 4) : 2 * KS);
+  // NOEXIT: the 128-pixel tiles, which never split K (chunk 0 first).  Their 1x1 loop has four activation chunks in flight instead
+  // of two and no early exits (see the 1x1 loop) -- a step of these tiles is 8-12 MFMAs per wave, so two steps of prefetch distance
+  // are far less than the load latency.  (SD v1, same box: 63.7 latents/s with two chunks in flight, 64.2 with four, 64.0 with
+  // eight and the weight ring as deep: profiles/r03/ab_1x1_small_tile_loop/.)
+  constexpr bool NOEXIT = TM == 4 && !COLD;
+  constexpr int WRING = T3 ? 3 : 4;                        // weight K-steps in registers
   uint4 wr[WRING][TN];
-  constexpr int RINGN = FOLD ? ADM_CONV_FOLD_RING : (DEEP1 ? DEEPN : ADM_CONV_RD);
+  constexpr int RINGN = (TAPS == 1 && NOEXIT) ? 4 : 2;     // activation chunks in registers (1x1 loops, skip-connection fold)
   uint4 ring[RINGN][PASSES];
   float4 bs[TN];
   // 1x1 loops: `last` = the tile's last chunk, ce - 1 (chunks - 1 unless the K loop is split: the split 1x1 tile runs chunks
@@ -516,33 +494,18 @@ conv_kernel(const ConvK p) {
       load_w(cb * 9, wr[0]);
       load_w(cb * 9 + 1, wr[1]);
     } else {
-      if constexpr (KS == 1) {
-        constexpr bool NOEXIT1 = ADM_CONV_1X1_NOEXIT && TM == 4 && !COLD;   // see the 1x1 loop: K-steps past the last read zero weights
-        load_w(cb, wr[0]);
-        load_w(NOEXIT1 ? cb + 1 : min(cb + 1, last), wr[1]);
-        load_w(NOEXIT1 ? cb + 2 : min(cb + 2, last), wr[2]);
-        if constexpr (WRING == 8) {
+      load_w(cb, wr[0]);   // NOEXIT (see the 1x1 loop): K-steps past the last read zero weights
+      load_w(NOEXIT ? cb + 1 : min(cb + 1, last), wr[1]);
+      load_w(NOEXIT ? cb + 2 : min(cb + 2, last), wr[2]);
 #pragma unroll
-          for (int q = 3; q < 7; ++q) load_w(NOEXIT1 ? cb + q : min(cb + q, last), wr[q]);
-        }
-      } else {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) load_w(ks, wr[ks]);  // stage 0's K-steps
-      }
-      constexpr bool NOEXIT1P = KS == 1 && ADM_CONV_1X1_NOEXIT && TM == 4 && !COLD;
-#pragma unroll
-      for (int ps = 0; ps < PASSES; ++ps) ring[1][ps] = NOEXIT1P ? halo_load_pad(cb + 1, last, ps) : halo_load(min(cb + 1, last), ps);
-      if constexpr (DEEP1) {
+      for (int ps = 0; ps < PASSES; ++ps) ring[1][ps] = NOEXIT ? halo_load_pad(cb + 1, last, ps) : halo_load(min(cb + 1, last), ps);
+      if constexpr (RINGN > 2) {
 #pragma unroll
         for (int q = 2; q < RINGN; ++q) {
 #pragma unroll
-          for (int ps = 0; ps < PASSES; ++ps) ring[q][ps] = NOEXIT1P ? halo_load_pad(cb + q, last, ps) : halo_load(min(cb + q, last), ps);
+          for (int ps = 0; ps < PASSES; ++ps) ring[q][ps] = NOEXIT ? halo_load_pad(cb + q, last, ps) : halo_load(min(cb + q, last), ps);
         }
       }
-#if ADM_CONV_RD == 3
-#pragma unroll
-      for (int ps = 0; ps < PASSES; ++ps) ring[2][ps] = halo_load(min(2, last), ps);
-#endif
     }
     if constexpr (ONEW) affine_regs(cb, img0);   // first_park transforms the tile's first chunk with these
     // bias fragment (whole float4 or nothing: a ragged last fragment only exists with the fp32 NCHW output,
@@ -733,8 +696,9 @@ conv_kernel(const ConvK p) {
         // first two weight K-steps (they follow the 3x3 weights: ring slots 0, 1 again since 9 % 3 == 0)
         chunk(ce - 1, std::true_type{}, std::true_type{});
         // ---- the skip_connection as one-tap K-steps: activations RINGN chunks ahead in registers (chunk k >= 1 in slot k % RINGN),
-        // weights two K-steps ahead (ring of 3), one barrier per step like the 1x1 loop; only the centre tap's fragment rows are read
-        const int fch = (p.FC0 + p.FC1) / KCS, flast = fch - 1;
+        // weights two K-steps ahead (ring of 3), one barrier per step like the 1x1 loop; only the centre tap's fragment rows are read.
+        // (Three chunks in flight instead of two were 1-5 % slower per tile: profiles/r03/conv_tile_timing_fold.log.)
+        const int fch = (p.FC0 + p.FC1) / KC, flast = fch - 1;
         const int fstep0 = chunks * 9;
         const unsigned char* const hc = halo + (HW2 + 1) * ROWB;     // centre tap
         // From skip chunk 1 on only the tile's BM CENTRE pixels are staged (into their slots of the halo geometry; the border slots
@@ -759,9 +723,9 @@ conv_kernel(const ConvK p) {
           }
         }
         auto cload = [&](int k, int ps) -> uint4 {
-          const int f0chunks = p.FC0 / KCS;
+          const int f0chunks = p.FC0 / KC;
           const bool first = k < f0chunks;
-          const int cs = first ? p.FC0 : p.FC1, co = (first ? k : k - f0chunks) * KCS;
+          const int cs = first ? p.FC0 : p.FC1, co = (first ? k : k - f0chunks) * KC;
           const __amdgpu_buffer_rsrc_t rs = first ? rs2 : rs3;
           const unsigned voff = cpix[ps] >= 0 ? (unsigned)(cpix[ps] * cs + co + seg * 8) * 2u : OOB;
           return bufload16(rs, voff, 0);
@@ -775,20 +739,12 @@ conv_kernel(const ConvK p) {
           constexpr int S = decltype(s_)::value;     // j % 6: ring slots (j + 1) % RINGN (activations), j % 3 (weights)
           if (j > flast) return;
           const int buf = (ce + j) & 1;
-#if ADM_FOLD_ABL != 2   // diagnostic builds only (wrong results): 1 no activation loads, 2 no weight loads, 3 no LDS park, 4 no MFMAs
           load_w(fstep0 + min(j + 2, flast), wr[(S + 2) % 3]);
-#endif
-#if ADM_FOLD_ABL != 4
           mfma_tap(hc + buf * Lds::HB, wr[S % 3]);
-#endif
-#if ADM_FOLD_ABL != 3
 #pragma unroll
           for (int ps = 0; ps < CPASS; ++ps) *reinterpret_cast<uint4*>(halo + (buf ^ 1) * Lds::HB + cslot[ps]) = ring[(S + 1) % RINGN][ps];
-#endif
-#if ADM_FOLD_ABL != 1
 #pragma unroll
           for (int ps = 0; ps < CPASS; ++ps) ring[(S + 1) % RINGN][ps] = cload(min(j + 1 + RINGN, flast), ps);
-#endif
           __syncthreads();
         };
         using J0 = std::integral_constant<int, 0>; using J1 = std::integral_constant<int, 1>; using J2 = std::integral_constant<int, 2>;
@@ -800,104 +756,50 @@ conv_kernel(const ConvK p) {
         }
       }
     } else {
-      // 1x1: a stage is KS K-steps (KS*TM*TN MFMAs per wave) and ends in the loop's only barrier, so HBM/L2
-      // latency must be covered by depth, not by taps: activation segments are fetched 2 stages ahead (register
-      // ring of 2), weight fragments 3 K-steps (KS = 1: ring of 4) or one stage (KS = 2: ring of 2 stages) ahead.
-      // The loop is unrolled so that every ring slot is a compile-time register; indices past the last stage are
-      // clamped (harmless re-reads).
-      // (Measured, MI355X: neither 64-channel stages nor running the two waves of a SIMD in opposite phases --
-      // MFMAs of stage c against transform + park of stage c+1 -- shortened this loop: ~1 us per K-step either way.
+      // 1x1: a K-step (TM*TN MFMAs per wave) ends in the loop's only barrier, so HBM/L2 latency must be covered by
+      // depth, not by taps: activation segments are fetched RINGN steps ahead (register ring), weight fragments
+      // 3 K-steps (ring of 4).  The loop is unrolled so that every ring slot is a compile-time register; indices
+      // past the last step are clamped (harmless re-reads).
+      // (Measured, MI355X: neither 64-channel stages (two K-steps per barrier), nor rings of three activation stages
+      // and weight K-steps, nor running the two waves of a SIMD in opposite phases -- MFMAs of stage c against
+      // transform + park of stage c+1 -- shortened this loop: ~1 us per K-step either way, docs/history_r01-r03.md
+      // section 3; the code of the first two was removed.
       // Ablations on the timing build: without the transform + park the GN-prologue loop is 43 % shorter, without
       // the activation loads the raw loop is 48 % shorter; weights and the barrier are not the limit.)
       using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
       using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
       const int last = ce - 1;
-#if ADM_CONV_RD == 3
-      if constexpr (KS == 1) {
-        // experiment: three activation stages in flight, weights two K-steps ahead (rings of 3, unrolled by 3)
-        auto body = [&](int c, auto s_) {
-          constexpr int S = decltype(s_)::value;
+      // NOEXIT (the 128-pixel tiles, never split-K): whole groups of four steps without the early exit.  With it every step is a
+      // control-flow merge and hipcc's wait-count insertion drains the prefetch (vmcnt(0) in two of the four steps, vmcnt(5) in
+      // the others, where the rings allow 6-8 loads in flight): the load latency was exposed in every other step -- 0.85 us per
+      // step on SD v1's 1280-wide projections, whose 8 MFMAs per wave need 0.1.  Steps past the last one multiply the re-read
+      // last chunk by weight fragments the buffer descriptor returns as zeros (K-step index beyond wbytes): they add nothing.
+      // (The 256-pixel tiles keep the exit: their GN-prologue instantiation spills without it, see below.)
+      auto body = [&](int c, auto sa_, auto sw_) {
+        constexpr int SA = decltype(sa_)::value, SW = decltype(sw_)::value;
+        if constexpr (!NOEXIT) {
           if (c > last) return;
-          affine_park(affine_load(min(c + 2, last), img0), c & 1);
-#pragma unroll
-          for (int ps = 0; ps < PASSES; ++ps) ring[S][ps] = halo_load(min(c + 3, last), ps);
-          load_w(min(c + 2, last), wr[(S + 2) % 3]);
-          mfma_tap(halo + (c & 1) * Lds::HB, wr[S]);
-#pragma unroll
-          for (int ps = 0; ps < PASSES; ++ps) halo_write(ring[(S + 1) % 3][ps], ps, (c + 1) & 1);
-          __syncthreads();
-        };
-        for (int c0 = 0; c0 < chunks; c0 += 3) {
-          body(c0, I0{});
-          body(c0 + 1, I1{});
-          body(c0 + 2, I2{});
         }
-      } else
-#endif
-      if constexpr (KS == 1) {
-        // NOEXIT (the 128-pixel tiles, never split-K): whole groups of four steps without the early exit.  With it every step is a
-        // control-flow merge and hipcc's wait-count insertion drains the prefetch (vmcnt(0) in two of the four steps, vmcnt(5) in
-        // the others, where the rings allow 6-8 loads in flight): the load latency was exposed in every other step -- 0.85 us per
-        // step on SD v1's 1280-wide projections, whose 8 MFMAs per wave need 0.1.  Steps past the last one multiply the re-read
-        // last chunk by weight fragments the buffer descriptor returns as zeros (K-step index beyond wbytes): they add nothing.
-        // (The 256-pixel tiles keep the exit: their GN-prologue instantiation spills without it, see below.)
-        constexpr bool NOEXIT = ADM_CONV_1X1_NOEXIT && TM == 4 && !COLD;
-        auto body = [&](int c, auto sa_, auto sw_) {
-          constexpr int SA = decltype(sa_)::value, SW = decltype(sw_)::value;
-          if constexpr (!NOEXIT) {
-            if (c > last) return;
-          }
-          const int c2 = min(c + 2, last);
-          affine_park(affine_load(c2, img0), c & 1);
-          // activation ring: chunk k lives in slot k % RINGN; chunk c's slot is free (parked during step c - 1)
-          (void)SA;
+        const int c2 = min(c + 2, last);
+        affine_park(affine_load(c2, img0), c & 1);
+        // activation ring: chunk k lives in slot k % RINGN; chunk c's slot is free (parked during step c - 1)
+        (void)SA;
 #pragma unroll
-          for (int ps = 0; ps < PASSES; ++ps) ring[SW % RINGN][ps] = NOEXIT ? halo_load_pad(c + RINGN, last, ps) : halo_load(min(c + RINGN, last), ps);
-          load_w(NOEXIT ? c + WRING - 1 : min(c + WRING - 1, last), wr[(SW + WRING - 1) % WRING]);
-          mfma_tap(halo + (c & 1) * Lds::HB, wr[SW % WRING]);
+        for (int ps = 0; ps < PASSES; ++ps) ring[SW % RINGN][ps] = NOEXIT ? halo_load_pad(c + RINGN, last, ps) : halo_load(min(c + RINGN, last), ps);
+        load_w(NOEXIT ? c + WRING - 1 : min(c + WRING - 1, last), wr[(SW + WRING - 1) % WRING]);
+        mfma_tap(halo + (c & 1) * Lds::HB, wr[SW % WRING]);
 #pragma unroll
-          for (int ps = 0; ps < PASSES; ++ps) halo_write(ring[(SW + 1) % RINGN][ps], ps, (c + 1) & 1);
-          __syncthreads();
-        };
-        // (Peeling the tail so that the unrolled group has no early exit removes the s_waitcnt vmcnt(0) hipcc puts
-        // at the loop header, but the 192-wide GN-prologue instantiation then spills inside the loop: 530 -> 690 us
-        // on qkv 384->1152 @32^2; the 128-wide tile, which does not spill, gained 3 %.)
-        if constexpr (WRING == 8) {
-          using I4 = std::integral_constant<int, 4>; using I5 = std::integral_constant<int, 5>;
-          using I6 = std::integral_constant<int, 6>; using I7 = std::integral_constant<int, 7>;
-          for (int c0 = cb; c0 < ce; c0 += 8) {
-            body(c0, I0{}, I0{}); body(c0 + 1, I1{}, I1{}); body(c0 + 2, I0{}, I2{}); body(c0 + 3, I1{}, I3{});
-            body(c0 + 4, I0{}, I4{}); body(c0 + 5, I1{}, I5{}); body(c0 + 6, I0{}, I6{}); body(c0 + 7, I1{}, I7{});
-          }
-        } else
-        for (int c0 = cb; c0 < ce; c0 += 4) {   // cb: 0, or even (split-K)
-          body(c0, I0{}, I0{});
-          body(c0 + 1, I1{}, I1{});
-          body(c0 + 2, I0{}, I2{});
-          body(c0 + 3, I1{}, I3{});
-        }
-      } else {
-        auto body = [&](int c, auto sa_) {
-          constexpr int SA = decltype(sa_)::value;  // parity of c
-          if (c > last) return;
-          const int c2 = min(c + 2, last);
-          // weights first: the wait for them at the next stage must not also drain the (slower, HBM) activation
-          // loads issued behind them -- vmcnt retires in order
-#pragma unroll
-          for (int ks = 0; ks < KS; ++ks) load_w(min(c + 1, last) * KS + ks, wr[(SA ^ 1) * KS + ks]);
-          affine_park(affine_load(c2, img0), c & 1);
-#pragma unroll
-          for (int ps = 0; ps < PASSES; ++ps) ring[SA][ps] = halo_load(c2, ps);
-#pragma unroll
-          for (int ks = 0; ks < KS; ++ks) mfma_tap(halo + SA * Lds::HB + ks * 64, wr[SA * KS + ks]);
-#pragma unroll
-          for (int ps = 0; ps < PASSES; ++ps) halo_write(ring[SA ^ 1][ps], ps, SA ^ 1);
-          __syncthreads();
-        };
-        for (int c0 = 0; c0 < chunks; c0 += 2) {
-          body(c0, I0{});
-          body(c0 + 1, I1{});
-        }
+        for (int ps = 0; ps < PASSES; ++ps) halo_write(ring[(SW + 1) % RINGN][ps], ps, (c + 1) & 1);
+        __syncthreads();
+      };
+      // (Peeling the tail so that the unrolled group has no early exit removes the s_waitcnt vmcnt(0) hipcc puts
+      // at the loop header, but the 192-wide GN-prologue instantiation then spills inside the loop: 530 -> 690 us
+      // on qkv 384->1152 @32^2; the 128-wide tile, which does not spill, gained 3 %.)
+      for (int c0 = cb; c0 < ce; c0 += 4) {   // cb: 0, or even (split-K)
+        body(c0, I0{}, I0{});
+        body(c0 + 1, I1{}, I1{});
+        body(c0 + 2, I0{}, I2{});
+        body(c0 + 3, I1{}, I3{});
       }
     }
     ADM_TSTAMP(ltile, 2);
@@ -1498,7 +1400,7 @@ template <int WM, int WN, int TM, int TN, int OCC, int TAPS, int HALO, int PRO, 
 int launch_conv_p(const ConvK& k, int m_tiles, hipStream_t s) {
   constexpr int NT = 64 * WM * WN;
   constexpr int BN = WN * TN * 16;
-  constexpr int smem = ConvLds<NT, BN, HALO, WM * TM * 16, KS>::BYTES;
+  constexpr int smem = ConvLds<NT, BN, HALO, WM * TM * 16>::BYTES;
   static_assert(smem <= 160 * 1024, "conv_kernel LDS map exceeds the CU's 160 KB");
   // per device: opt in to the LDS size once, and size the persistent grid to the resident blocks
   static int percu_dev[64] = {}, ncu_dev[64] = {};
@@ -1595,8 +1497,6 @@ int dispatch_conv(ConvK& k, int taps, int prologue, hipStream_t s) {
   } else {   // 1x1 (COLD: split-K on the 8-wave tiles, fp32 NCHW output on the 16-wide tile)
     if (conv_geometry(k, BM, 1, BM)) {
       const int m_tiles = k.TI == 1 ? k.N * k.tiles_x * k.tiles_y : (k.N + k.TI - 1) / k.TI;
-      // 64-channel stages (two K-steps per barrier) when neither source straddles a stage
-      if (ADM_CONV_KS2 && k.C0 % 64 == 0 && k.C1 % 64 == 0) return launch_conv<WM, WN, TM, TN, OCC, 1, BM, ADM_CONV_KS2 ? 2 : 1, COLD>(k, prologue, m_tiles, s);
       return launch_conv<WM, WN, TM, TN, OCC, 1, BM, 1, COLD>(k, prologue, m_tiles, s);
     }
   }
@@ -1759,7 +1659,6 @@ extern "C" int adm_conv(const adm_conv_args* a, void* stream) {
   if (k.ksplit > 1) {
     const int chunks = (a->c0 + a->c1) / KC;
     ADM_REQUIRE(a->out_mode == 0 && !k.res_up && a->ws, ADM_E_ARG, "adm_conv: ksplit needs bf16 output, no res_up and a workspace");
-    ADM_REQUIRE(a->taps == 9 || (ADM_CONV_KS2 == 0 && ADM_CONV_RD == 2), ADM_E_ARG, "adm_conv: this build's 1x1 loop does not split K");
     ADM_REQUIRE(chunks % k.ksplit == 0 && (chunks / k.ksplit) % 2 == 0, ADM_E_SHAPE,
                 "adm_conv: ksplit %d does not divide the %d 32-channel chunks into even runs", k.ksplit, chunks);
     ADM_REQUIRE(a->cout % 8 == 0 && a->cout <= 2048 && adm_aligned16(a->ws), ADM_E_SHAPE, "adm_conv: ksplit needs cout %% 8 == 0, cout <= 2048, aligned ws");

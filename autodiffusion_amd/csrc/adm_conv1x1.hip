@@ -18,16 +18,15 @@
 //              LDS -> 16-byte row-segment stores with the residual and the output's GroupNorm partial sums; with
 //              no barrier in the Cout loop the waves drift apart and one wave's stores overlap another's MFMAs
 //   launch     persistent over pixel tiles (flattened N*H*W; BM <= H*W, so a tile lies in one image)
+// Ablation builds of round 2 dropped one phase of the tile each (docs/history_r01-r03.md section 6.1): 384->384 + residual
+// @32^2 took 151 us; 141 without the residual loads, 134 without the stores, 119 without the activation fetch, 113
+// without the K loop -- fetch, K loop and epilogue ran one after the other on a CU.
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "adm_common.h"
 #include "adm_conv_internal.h"
-
-#ifndef ADM_C1_ABL
-#define ADM_C1_ABL 0   // diagnostic builds only: drop one phase of the tile (results are then wrong) to price it
-#endif
 
 namespace {
 
@@ -108,7 +107,7 @@ conv1x1r_kernel(const Conv1K p) {
       }
       __syncthreads();
     }
-    for (int i0 = 0; i0 < (ADM_C1_ABL == 3 ? 0 : BM * segk); i0 += 4 * NT) {
+    for (int i0 = 0; i0 < BM * segk; i0 += 4 * NT) {
       uint4 v[4];
       int px[4], sg[4];
 #pragma unroll
@@ -200,7 +199,6 @@ conv1x1r_kernel(const Conv1K p) {
       load_w(min(1, last), wr[1]);
       load_w(min(2, last), wr[2]);
       int k0 = 0;
-      if (ADM_C1_ABL == 4) k0 = last + 1;
       for (; k0 + 3 <= last; k0 += 4) {  // whole groups of 4: no early exit inside the unrolled group
         load_w(min(k0 + 3, last), wr[3]); kstep(k0, wr[0]);
         load_w(min(k0 + 4, last), wr[0]); kstep(k0 + 1, wr[1]);
@@ -274,7 +272,7 @@ conv1x1r_kernel(const Conv1K p) {
             const long long eo = ((long long)pb + wm * TM * 16 + c * 32 + r) * p.Cout + cbw + sgl * 8;
             uint4 v = *reinterpret_cast<const uint4*>(wst + r * WROW + sgl * 16);
             uint32_t a4[4] = {v.x, v.y, v.z, v.w};
-            if (p.res && ADM_C1_ABL != 1) {
+            if (p.res) {
               const uint4 rr = *reinterpret_cast<const uint4*>(p.res + eo);
               const uint32_t r4[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
@@ -285,7 +283,7 @@ conv1x1r_kernel(const Conv1K p) {
               }
               v = make_uint4(a4[0], a4[1], a4[2], a4[3]);
             }
-            if (ADM_C1_ABL != 2 || v.x == 0x12345678u) *reinterpret_cast<uint4*>(p.out + eo) = v;
+            *reinterpret_cast<uint4*>(p.out + eo) = v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const f32x2 t = f32x2{adm_lo_f32(a4[e]), adm_hi_f32(a4[e])};
@@ -343,7 +341,7 @@ conv1x1r_kernel(const Conv1K p) {
         for (int k = 0; k < NIT; ++k) {
           const int m = prow + k * PR;
           rr[k] = make_uint4(0, 0, 0, 0);
-          if (p.res && act && m < BM && ADM_C1_ABL != 1) rr[k] = *reinterpret_cast<const uint4*>(p.res + ((long long)pb + m) * p.Cout + gch);
+          if (p.res && act && m < BM) rr[k] = *reinterpret_cast<const uint4*>(p.res + ((long long)pb + m) * p.Cout + gch);
         }
         __syncthreads();
         f32x2 s1[4], s2[4];
@@ -365,7 +363,7 @@ conv1x1r_kernel(const Conv1K p) {
             }
             v = make_uint4(a4[0], a4[1], a4[2], a4[3]);
           }
-          if (ADM_C1_ABL != 2 || v.x == 0x12345678u) *reinterpret_cast<uint4*>(p.out + ((long long)pb + m) * p.Cout + gch) = v;
+          *reinterpret_cast<uint4*>(p.out + ((long long)pb + m) * p.Cout + gch) = v;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const f32x2 t = f32x2{adm_lo_f32(a4[q]), adm_hi_f32(a4[q])};
