@@ -119,6 +119,9 @@ SIGNATURES = {
     "adm_vec_gn_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "adm_knn_smallest": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _P, _P, _I, _P]),
     "adm_knn_cover": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "adm_attention_1h512": (_I, [_P, _P, _I, _I, _P]),
+    "adm_vae_latent_in": (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P]),
+    "adm_vae_image_out": (_I, [_P, _P, _P, _I, _I, _I, _P]),
 }
 
 _libs = {}

@@ -439,10 +439,17 @@ def _conv_up_phases(x0, w_up, bias, cout, aff, silu, out, want_stats):
 
 # ------------------------------------------------------------------ attention
 def attention(qkv, heads: int, new_order: bool, want_lse: bool = False):
-    """qkv bf16 [N, T, 3*H*D] -> bf16 [N, T, H*D] (and the fp32 [N, H, T] log-sum-exp if want_lse)."""
+    """qkv bf16 [N, T, 3*H*D] -> bf16 [N, T, H*D] (and the fp32 [N, H, T] log-sum-exp if want_lse).
+    heads == 1 with D == 512 (q | k | v at columns 0 / 512 / 1024) runs on adm_attention_1h512."""
     n, t, c3 = qkv.shape
     c = c3 // 3
     d = c // heads
+    if heads == 1 and d == 512:   # the VAE decoder's mid attention: one head of width 512 (csrc/adm_vae.hip)
+        if want_lse:
+            raise AdmError("attention: the 512-wide single-head kernel has no log-sum-exp output (forward only)")
+        out = torch.empty((n, t, c), dtype=qkv.dtype, device=qkv.device)
+        check(_L(qkv).adm_attention_1h512(_ptr(qkv, qkv.dtype, "qkv"), _ptr(out), n, t, _stream()), "adm_attention_1h512")
+        return out
     out = torch.empty((n, t, c), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty((n, heads, t), dtype=torch.float32, device=qkv.device) if want_lse else None
     check(_L(qkv).adm_attention_lse(_ptr(qkv, qkv.dtype, "qkv"), _ptr(out), _ptr(lse), n, t, heads, d,
@@ -464,6 +471,39 @@ def attention_cross(q, kv, heads: int, d: int, tk: int, scale: float, q_cols: in
     check(_L(q).adm_attention_cross(q.data_ptr(), q.stride(1), kv.data_ptr(), kv.stride(1), kv.shape[1],
                                           _ptr(out), n, tq, tk, heads, d, float(scale), _stream()), "adm_attention_cross")
     return out
+
+
+# ------------------------------------------------------------------ KL-f8 VAE decoder entry / exit (csrc/adm_vae.hip)
+def vae_latent_in(z, w, b, inv_scale: float = 1.0, dtype=BF16):
+    """fp32 NCHW latents [N, e, H, W] -> 16-bit NHWC [N, H, W, 32]: channels [0, zc) = post_quant_conv(inv_scale * z) (weight
+    fp32 [zc, e] or [zc, e, 1, 1], bias fp32 [zc]; fp32 math), the rest zero -- the operand of the decoder's conv_in."""
+    if z.dim() != 4:
+        raise AdmError(f"vae_latent_in: expected [N, e, H, W] latents, got {tuple(z.shape)}")
+    n, e, h, wd = z.shape
+    zc = w.shape[0]
+    if w.numel() != zc * e or b.numel() != zc:
+        raise AdmError(f"vae_latent_in: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not map {e} -> {zc} channels")
+    zp, wp, bp = _ptr(z, torch.float32, "z"), _ptr(w, torch.float32, "w"), _ptr(b, torch.float32, "b")
+    out = torch.empty((n, h, wd, 32), dtype=dtype, device=z.device)
+    check(_L(out).adm_vae_latent_in(zp, wp, bp, float(inv_scale), _ptr(out), n, zc, e, h, wd, _stream()), "adm_vae_latent_in")
+    return out
+
+
+def vae_image_out(x, want_unit: bool = True, want_u8: bool = False, unit_out=None):
+    """Decoder output fp32 NCHW [N, 3, H, W] -> (unit fp32 NCHW = clamp((x + 1) / 2, 0, 1) | None, uint8 NHWC = trunc(255 * unit) | None).
+    unit_out: a contiguous fp32 [N, 3, H, W] tensor (e.g. rows of a staging batch) to receive `unit` instead of a fresh one."""
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise AdmError(f"vae_image_out: expected [N, 3, H, W] images, got {tuple(x.shape)}")
+    n, _, h, w = x.shape
+    xp = _ptr(x, torch.float32, "x")
+    if unit_out is not None:
+        if tuple(unit_out.shape) != tuple(x.shape):
+            raise AdmError(f"vae_image_out: unit_out {tuple(unit_out.shape)} does not match {tuple(x.shape)}")
+        _ptr(unit_out, torch.float32, "unit_out")
+    unit = unit_out if unit_out is not None else (torch.empty_like(x) if want_unit else None)
+    u8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=x.device) if want_u8 else None
+    check(_lib.load().adm_vae_image_out(xp, _ptr(unit), _ptr(u8), n, h, w, _stream()), "adm_vae_image_out")
+    return unit, u8
 
 
 # ------------------------------------------------------------------ Stable-Diffusion token kernels

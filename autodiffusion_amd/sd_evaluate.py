@@ -1,0 +1,142 @@
+"""Score one Stable-Diffusion candidate on decoded images: sampler -> VAE decoder -> [0, 1] images -> extractor -> FID.
+
+The body of the reference's ``EvolutionSearcher.get_cand_fid`` ("Stable Diffusion"/scripts/search_ea.py:504-566) on the HIP
+parts: ``sd_sampler`` (UNet + sampler with ``sampled_timestep``), ``sd_vae`` (``decode_first_stage``), ``adm_vae_image_out``
+(the clamp expression of :540), ``inception.InceptionV3`` (pytorch_fid's extractor) and ``fid.ActivationAccumulator``.
+Between the sampler's output and the float64 statistics every step is a libadm_hip.so launch: no torch compute op, no host copy
+of an image (the reference moves every batch to the host and back, :541-549).
+
+Kept from the reference: one sampler call per batch of the conditioning iterable; batches are collected until
+``len(samples) > num_samples`` (strict: :553) and ALL collected samples are scored; the extractor sees them 320 at a time
+(``calculate_fid(..., batch_size=320)``, :561); with ``opt.fixed_code`` one start code is drawn per call and reused for every
+batch (:506-508, :537); the ``sample_time`` / ``fid_time`` log line (:565).
+
+Different by design: the prompts arrive as precomputed ``(c, uc)`` embeddings (the CLIP text encoder is not built here), and the
+start noise always comes from a CPU generator seeded from (seed, candidate, batch index) and is passed as ``x_T`` -- a
+candidate's score does not depend on what was evaluated before it.
+"""
+from __future__ import annotations
+
+import time
+import zlib
+
+import numpy as np
+import torch
+
+from . import logger, ops
+from ._lib import AdmError
+from .fid import ActivationAccumulator, FIDStatistics
+
+FID_BATCH = 320   # the reference's calculate_fid(batch_size=320)
+
+
+def candidate_seed(seed: int, cand) -> int:
+    """Base seed of a candidate's start noise (search.py: seed * 1000003 + crc32(str(cand)))."""
+    key = str([t.item() if hasattr(t, "item") else t for t in cand])
+    return (int(seed) * 1000003 + zlib.crc32(key.encode())) & 0x7FFFFFFF
+
+
+def batch_seed(seed0: int, batch: int) -> int:
+    return seed0 + 7919 * int(batch)
+
+
+def inception_features(net, dims: int = 2048, allow_random: bool = False):
+    """The default extractor: ``InceptionV3.forward`` on float [N, 3, H, W] images in [0, 1] -> fp32 [N, dims]."""
+    if not getattr(net, "weights_loaded", False) and not allow_random:
+        raise ValueError("SDCandidateEvaluator: the Inception-v3 extractor has no checkpoint loaded: FID values on random weights "
+                         "are meaningless; pass allow_random_inception=True for throughput runs and tests")
+
+    def features(images):
+        pred = net(images)[0]
+        if pred.shape[2] != 1 or pred.shape[3] != 1:
+            raise AdmError(f"SDCandidateEvaluator: the extractor's block returns {tuple(pred.shape[2:])} maps; use the pooled block")
+        return pred.reshape(pred.shape[0], pred.shape[1])
+    features.random_weights = not getattr(net, "weights_loaded", False)
+    features.dims = dims
+    return features
+
+
+class SDCandidateEvaluator:
+    def __init__(self, model, sampler, conditioning, ref_mu, ref_sigma, num_samples: int, *, features=None, inception=None,
+                 dims: int = 2048, allow_random_inception: bool = False, seed: int = 0, device=None, image_out=None,
+                 accumulator=None):
+        """model: ``sd_sampler.LatentDiffusion`` with a first stage (``decode_first_stage``); sampler: one of the
+        ``sd_sampler`` samplers around it; conditioning: iterable of per-batch ``(c, uc)`` device tensors (``uc`` may be None
+        when ``opt.scale == 1``), re-iterated by every call; features: callable float [N, 3, H, W] in [0, 1] -> [N, dims]
+        (default: ``inception`` -- an ``InceptionV3`` -- through ``inception_features``).
+        image_out / accumulator: the clamp launch and the statistics sink, replaceable for host-only tests of the batch plan."""
+        self.model, self.sampler, self.conditioning = model, sampler, conditioning
+        self.ref_stats = FIDStatistics(np.asarray(ref_mu, dtype=np.float64), np.asarray(ref_sigma, dtype=np.float64))
+        self.num_samples, self.seed, self.dims = int(num_samples), int(seed), int(dims)
+        self.device = torch.device(device) if device is not None else getattr(model, "device", torch.device("cpu"))
+        if features is None:
+            if inception is None:
+                raise ValueError("SDCandidateEvaluator: pass features= (a callable) or inception= (an InceptionV3)")
+            features = inception_features(inception, dims, allow_random_inception)
+        self.features = features
+        self.fid_note = (" [FID on RANDOM Inception weights: not a quality metric]"
+                         if getattr(features, "random_weights", False) else "")
+        self._image_out = image_out or (lambda x, out: ops.vae_image_out(x, unit_out=out)[0])
+        self._accumulator = accumulator or (lambda: ActivationAccumulator(self.dims, self.device))
+        self.last_times = None
+        self.last_plan = None    # [(batch index, noise seed)] of the last call
+
+    # ------------------------------------------------------------------ start noise
+    def start_code(self, opt, seed: int):
+        """fp32 [n_samples, C, H / f, W / f] from a CPU generator (device-independent), moved to the evaluator's device."""
+        g = torch.Generator().manual_seed(int(seed))
+        x = torch.randn([opt.n_samples, opt.C, opt.H // opt.f, opt.W // opt.f], generator=g, dtype=torch.float32)
+        return x.to(self.device)
+
+    # ------------------------------------------------------------------ search_ea.py:504-566
+    def get_cand_fid(self, cand=None, opt=None, device=None):
+        t1 = time.time()
+        seed0 = candidate_seed(self.seed, cand)
+        fixed = self.start_code(opt, batch_seed(seed0, 0)) if opt.fixed_code else None
+        shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
+        sampled_timestep = np.array(cand)
+        acc = self._accumulator()
+        stage, fill, count, plan = None, 0, 0, []
+        with torch.no_grad():
+            for itr, (c, uc) in enumerate(self.conditioning):
+                if opt.scale == 1.0:
+                    uc = None
+                seed = batch_seed(seed0, 0 if opt.fixed_code else itr)
+                x_T = fixed if opt.fixed_code else self.start_code(opt, seed)
+                plan.append((itr, seed))
+                samples, _ = self.sampler.sample(S=opt.time_step, conditioning=c, batch_size=opt.n_samples, shape=shape,
+                                                 verbose=False, unconditional_guidance_scale=opt.scale,
+                                                 unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T,
+                                                 sampled_timestep=sampled_timestep)
+                x = self.model.decode_first_stage(samples)
+                # clamp((x + 1) / 2, 0, 1) straight into the extractor's staging batch of 320 images
+                if stage is None:
+                    stage = torch.empty((FID_BATCH,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+                done = 0
+                while done < x.shape[0]:
+                    take = min(x.shape[0] - done, FID_BATCH - fill)
+                    self._image_out(x[done:done + take], stage[fill:fill + take])
+                    fill, done = fill + take, done + take
+                    if fill == FID_BATCH:
+                        acc.add(self.features(stage))
+                        fill = 0
+                count += int(x.shape[0])
+                logger.log('samples: ' + str(count))
+                if count > self.num_samples:
+                    logger.log('samples: ' + str(count))
+                    break
+            if fill:
+                acc.add(self.features(stage[:fill]))
+        if count == 0:
+            raise AdmError("SDCandidateEvaluator: the conditioning iterable is empty")
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        sample_time = time.time() - t1
+        t1 = time.time()
+        fid = float(acc.statistics(None, local=True).frechet_distance(self.ref_stats))
+        logger.log('FID: ' + str(fid) + self.fid_note)
+        fid_time = time.time() - t1
+        logger.log('sample_time: ' + str(sample_time) + ', fid_time: ' + str(fid_time))
+        self.last_times = {"sample_time": sample_time, "fid_time": fid_time, "images": count, "batches": len(plan)}
+        self.last_plan = plan
+        return fid

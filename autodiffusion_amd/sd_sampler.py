@@ -75,7 +75,7 @@ class LatentDiffusion:
     parameterization = "eps"
 
     def __init__(self, unet, timesteps=1000, beta_schedule="linear", linear_start=0.00085, linear_end=0.0120,
-                 cosine_s=8e-3, device=None):
+                 cosine_s=8e-3, device=None, first_stage=None, scale_factor=0.18215):
         betas = make_beta_schedule(beta_schedule, timesteps, linear_start=linear_start, linear_end=linear_end,
                                    cosine_s=cosine_s)
         ac = np.cumprod(1.0 - betas, axis=0)
@@ -85,6 +85,62 @@ class LatentDiffusion:
         self.alphas_cumprod = torch.tensor(ac, dtype=torch.float32, device=self.device)
         self.alphas_cumprod_prev = torch.tensor(np.append(1.0, ac[:-1]), dtype=torch.float32, device=self.device)
         self.model = unet
+        self.first_stage_model = first_stage       # sd_vae.AutoencoderKL (None: latents only, as before)
+        self.scale_factor = float(scale_factor)
+
+    DECODE_CHUNK_64 = 8   # latents per decoder pass at 64 x 64 (peak: two 512 x 512 x 128 16-bit maps + the fp32 image per latent)
+
+    def decode_first_stage(self, z, chunk=None):
+        """ddpm.py:706-713 + autoencoder.py:329-332: first_stage_model.decode(z / scale_factor) -> fp32 NCHW images in about
+        [-1, 1].  The batch goes through the decoder ``chunk`` latents at a time (default 8 at 64 x 64, scaled by the latent's
+        area) so that peak activation memory does not grow with the batch; every kernel's arithmetic per latent is independent
+        of the batch it rides in, so the result is bitwise independent of ``chunk``."""
+        if self.first_stage_model is None:
+            raise AdmError("LatentDiffusion.decode_first_stage: constructed without first_stage= (sd_vae.AutoencoderKL)")
+        if not torch.is_tensor(z) or z.dim() != 4:
+            raise AdmError("decode_first_stage: expected [N, C, H, W] latents")
+        n, _, h, w = z.shape
+        if chunk is None:
+            chunk = max(1, self.DECODE_CHUNK_64 * 64 * 64 // max(1, h * w))
+        chunk = max(1, int(chunk))
+        inv_scale = float(np.float32(1.0 / self.scale_factor))
+        z = z.to(torch.float32).contiguous()
+        if n <= chunk:
+            return self.first_stage_model.decode(z, inv_scale)
+        out = None
+        for i in range(0, n, chunk):
+            x = self.first_stage_model.decode(z[i:i + chunk], inv_scale)
+            if out is None:
+                out = torch.empty((n,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+            out[i:i + chunk].copy_(x)
+        return out
+
+    _ROUTES = (("model.diffusion_model.", "model"), ("first_stage_model.", "first_stage_model"))
+
+    def load_state_dict(self, sd, strict=True):
+        """A full latent-diffusion checkpoint's state dict: ``model.diffusion_model.*`` goes to the UNet, ``first_stage_model.*``
+        to the first stage (when one was given); everything else (``cond_stage_model.*``, ``model_ema.*``, the schedule buffers)
+        is not used on this path and is reported in one log line.  Returns {route: number of tensors}."""
+        from . import logger
+        parts = {attr: {} for _, attr in self._ROUTES}
+        other = {}
+        for k, v in sd.items():
+            for prefix, attr in self._ROUTES:
+                if k.startswith(prefix):
+                    parts[attr][k[len(prefix):]] = v
+                    break
+            else:
+                head = k.split(".", 1)[0]
+                other[head] = other.get(head, 0) + 1
+        self.model.load_state_dict(parts["model"], strict=strict)
+        if self.first_stage_model is not None:
+            self.first_stage_model.load_state_dict(parts["first_stage_model"], strict=strict)
+        elif parts["first_stage_model"]:
+            other["first_stage_model"] = len(parts["first_stage_model"])
+        logger.log("LatentDiffusion.load_state_dict: %d UNet tensors, %d first-stage tensors; not used on this path: %s"
+                   % (len(parts["model"]), len(parts["first_stage_model"]) if self.first_stage_model is not None else 0,
+                      ", ".join(f"{k} ({v})" for k, v in sorted(other.items())) or "none"))
+        return {"model": len(parts["model"]), "first_stage_model": len(parts["first_stage_model"]), "ignored": other}
 
     def apply_model(self, x_noisy, t, cond, context_key=None):
         if context_key is not None and getattr(self.model, "accepts_context_key", False):

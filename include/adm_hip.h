@@ -33,7 +33,8 @@ extern "C" {
                                7: adm_gn_finalize_add gained stats, adm_gn_bwd_finalize gained add / add_stride; the classifier's other heads;
                                8: adm_conv_args gained fold0 / fold1 / fc0 / fc1;
                                9: adm_conv_args gained out_scale; CU-partitioned streams (adm_stream_create_cumask / _set_cus / _destroy);
-                               10: the evaluation suite's k-NN entry points (adm_knn_smallest / adm_knn_cover) */
+                               10: the evaluation suite's k-NN entry points (adm_knn_smallest / adm_knn_cover);
+                               still 10 (additive, nothing existing changed): the VAE decoder's adm_attention_1h512 / adm_vae_latent_in / adm_vae_image_out */
 
 #define ADM_E_ARG      (-1)  /* bad pointer / size / flag combination          */
 #define ADM_E_SHAPE    (-2)  /* shape not supported by the gfx950 tiling       */
@@ -410,6 +411,24 @@ int adm_knn_smallest(const void* q, int nq, const float* qnorm, const void* x, i
                      float* out, float* ws, int splits, void* stream);
 int adm_knn_cover(const void* a, int na, const float* anorm, const float* ra, const void* b, int nb, const float* bnorm,
                   const float* rb, int d, int K, uint8_t* a_in, uint8_t* b_in, void* stream);
+
+/* ---------------------------------------------------------------- KL-f8 VAE decoder (K14: Stable Diffusion first stage)
+ * The decoder (ldm/modules/diffusionmodules/model.py:462-568) runs on adm_conv / adm_gn_* / adm_attention; these are the three
+ * pieces those do not cover.
+ *   adm_attention_1h512  single-head attention of width 512 (AttnBlock, model.py:186-198): qkv 16-bit [n][t][1536] with q | k | v
+ *                        at columns 0 / 512 / 1024 -> out 16-bit [n][t][512] = softmax(q k^T * 512^-1/2) v.  One launch, fp32
+ *                        online softmax, no [t][t] tensor in memory; any t >= 1 (rows beyond t are read as zeros, never written);
+ *                        an image's result does not depend on n.
+ *   adm_vae_latent_in    z fp32 NCHW [n][e][h][w] -> out 16-bit NHWC [n][h][w][32]: channels [0, zc) = post_quant_conv(inv_scale * z)
+ *                        (the 1x1 Conv2d(e, zc) of ldm/models/autoencoder.py:303, 330-331 after ddpm.py:713; weight fp32 [zc][e],
+ *                        bias fp32 [zc], fp32 math), channels [zc, 32) = 0: the operand of the decoder's conv_in.  zc <= 32, e <= 16.
+ *   adm_vae_image_out    x fp32 NCHW [n][3][h][w] -> unit fp32 NCHW = min(max((x + 1) / 2, 0), 1) (scripts/search_ea.py:540) and / or
+ *                        u8 uint8 NHWC = (uint8)(255 * unit), truncated (scripts/txt2img.py:337-339).  Either output may be NULL,
+ *                        not both.                                                                                              */
+int adm_attention_1h512(const adm_bf16* qkv, adm_bf16* out, int n, int t, void* stream);
+int adm_vae_latent_in(const float* z, const float* w, const float* b, float inv_scale, adm_bf16* out, int n, int zc, int e, int h,
+                      int w_, void* stream);
+int adm_vae_image_out(const float* x, float* unit, uint8_t* u8, int n, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }

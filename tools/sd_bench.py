@@ -3,7 +3,10 @@
 path: ms per UNet evaluation, latents/s and model TFLOP/s (803.3 GFLOP per latent per evaluation).
 GRAPH=1 replays a captured hipGraph.  BATCH (default 12 = the reference's n_samples 6 with classifier-free guidance), REPS, BREAKDOWN=1 for per-shape conv time.
 SAMPLER=ddim|plms|dpm additionally times BASELINE config 4's candidate evaluation: K searched steps (K, default 6),
-classifier-free guidance 7.5, N_SAMPLES latents per batch (default 6) -> finished latents/s."""
+classifier-free guidance 7.5, N_SAMPLES latents per batch (default 6) -> finished latents/s.
+--decode times the first stage instead: `decode_first_stage` of 6 latents of 64 x 64 through the v1 KL-f8 decoder per torso (ms per
+latent, model TFLOP/s from the plan's algorithmic FLOPs) and `adm_attention_1h512` alone at n = 6, T = 4096 next to a
+torch-composed 16-bit bmm-softmax-bmm, alternating, median of 5."""
 import os
 import sys
 import time
@@ -56,6 +59,57 @@ def main():
             print(f"  conv {key} nhwc_in={shape[:4]} cout={shape[4]} x{cnt // reps}: {ms_ / reps:8.2f} ms {fl_ / ms_ / 1e9:7.1f} TFLOP/s")
 
 
+def _timed(fn, reps=1):
+    """ms of `reps` calls between two device events (a launch returns before the kernel finishes)."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def decode_bench():
+    import statistics
+    from autodiffusion_amd.sd_sampler import LatentDiffusion
+    from autodiffusion_amd.sd_vae import SD_V1_VAE, AutoencoderKL
+    n, hw = int(os.environ.get("N_SAMPLES", "6")), 64
+    z = torch.randn(n, 4, hw, hw, device=DEV, generator=torch.Generator(device=DEV).manual_seed(0)) * 0.9
+    for torso in ("bf16", "fp16"):
+        vae = AutoencoderKL(**SD_V1_VAE).set_torso(torso).to(DEV).randomize_(4321)
+        ld = LatentDiffusion(vae.decoder, device=DEV, first_stage=vae)   # the schedule tables are not used here
+        gflop = vae.decoder.plan.flops(hw, hw) / 1e9
+        for _ in range(2):
+            out = ld.decode_first_stage(z)
+        torch.cuda.synchronize()
+        assert out.shape == (n, 3, 8 * hw, 8 * hw) and torch.isfinite(out).all()
+        ms = statistics.median(_timed(lambda: ld.decode_first_stage(z)) for _ in range(5))
+        exit_ms = statistics.median(_timed(lambda: ops.vae_image_out(out), 5) for _ in range(5))
+        print(f"SD v1 VAE decode [{torso}] {n} latents of {hw}x{hw}: {ms:.1f} ms / pass, {ms / n:.2f} ms / latent, "
+              f"{n * gflop / ms:.1f} model TFLOP/s ({gflop:.1f} GFLOP per latent, from the plan); adm_vae_image_out {exit_ms:.3f} ms")
+        # the 512-wide attention alone: n = 6, T = 4096, against torch's composed 16-bit bmm - softmax - bmm, alternating
+        dt = vae.compute_dtype
+        qkv = (torch.randn(n, hw * hw, 1536, device=DEV, generator=torch.Generator(device=DEV).manual_seed(1))).to(dt)
+        q, k, v = (t.contiguous() for t in qkv.chunk(3, dim=-1))
+
+        def composed():
+            return torch.bmm(torch.softmax(torch.bmm(q, k.transpose(1, 2)) * (512 ** -0.5), dim=-1), v)
+        for _ in range(3):
+            a, b = ops.attention(qkv, 1, True), composed()
+        torch.cuda.synchronize()
+        err = float((a.float() - b.float()).norm() / b.float().norm())
+        ta, tb = [], []
+        for _ in range(5):
+            ta.append(_timed(lambda: ops.attention(qkv, 1, True), 10))
+            tb.append(_timed(composed, 10))
+        fl = 4.0 * n * (hw * hw) ** 2 * 512
+        ma, mb = statistics.median(ta), statistics.median(tb)
+        print(f"attention 1 x 512 [{torso}] n={n} T={hw * hw}: adm_attention_1h512 {ma:.3f} ms ({fl / ma / 1e9:.1f} TFLOP/s), "
+              f"torch bmm-softmax-bmm {mb:.3f} ms ({fl / mb / 1e9:.1f} TFLOP/s); rel diff of the two {err:.2g}")
+        del vae, ld
+
+
 def sampler_bench(m):
     from autodiffusion_amd.sd_sampler import DDIMSampler, DPMSolverSampler, LatentDiffusion, PLMSSampler
     kind = os.environ["SAMPLER"]
@@ -87,4 +141,7 @@ def sampler_bench(m):
 
 
 if __name__ == "__main__":
-    main()
+    if "--decode" in sys.argv[1:]:
+        decode_bench()
+    else:
+        main()
