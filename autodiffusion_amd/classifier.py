@@ -51,7 +51,7 @@ class EncoderUNetModel(AdmNet):
         return self.FP16_GRAD_SCALE if self.compute_dtype == torch.float16 else 1.0
 
     # ------------------------------------------------------------------ head weights
-    def _prepare_head(self, pr, P, f32):
+    def _prepare_head(self, pr, P, f32, pack):
         h = self.plan.head
         p = h.prefix
         if isinstance(h, PoolHeadSpec):
@@ -69,7 +69,7 @@ class EncoderUNetModel(AdmNet):
         wc = f32(f"{p}.2.c_proj.weight").reshape(h.out_dim, h.channels).contiguous()
         pr.head = dict(
             g=f32(f"{p}.0.weight"), b=f32(f"{p}.0.bias"), pos=f32(f"{p}.2.positional_embedding"),
-            wqkv=ops.pack_conv_weight(P[f"{p}.2.qkv_proj.weight"], self.compute_dtype), bqkv=f32(f"{p}.2.qkv_proj.bias"),
+            wqkv=pack(P[f"{p}.2.qkv_proj.weight"]), bqkv=f32(f"{p}.2.qkv_proj.bias"),
             wqkv_bwd=ops.pack_conv_weight_bwd(P[f"{p}.2.qkv_proj.weight"], self.compute_dtype),
             wc=wc, bc=f32(f"{p}.2.c_proj.bias"), wc_t=wc.t().contiguous(),
         )

@@ -24,11 +24,11 @@ Engine: activations are bf16 NHWC, so a token of the SpatialTransformer IS a pix
 from __future__ import annotations
 
 import os
-from typing import Dict, List
+from typing import Dict
 
 import torch
 
-from . import ops
+from . import blocks, ops
 from ._lib import AdmError
 from .sd_arch import (SDDownSpec, SDResBlockSpec, SDStemSpec, SDTransformerSpec, SDUNetPlan, SDUpSpec,
                       sd_unet_plan)
@@ -91,21 +91,13 @@ class UNetModel(HipModule):
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.num_classes = None
 
-    @staticmethod
-    def _init_param(name, shape, g):
-        if name.endswith(("out_layers.3.weight", "out_layers.3.bias", "proj_out.weight", "proj_out.bias")) \
-                or name in ("out.2.weight", "out.2.bias"):
-            return torch.zeros(shape)  # zero_module (openaimodel.py:224-226, 703; attention.py:241-245)
-        return HipModule._init_param(name, shape, g)
-
     # ------------------------------------------------------------------ weight preparation
     def _prepare(self):
         P, dev, plan = self._params, self.device, self.plan
         if dev.type != "cuda":
             raise AdmError("latent UNetModel: parameters are on the CPU; call .to(device) first (no CPU fallback)")
         pr = _Prep()
-        f32 = lambda k: P[k].to(torch.float32).contiguous()  # noqa: E731
-        pack = lambda w: ops.pack_conv_weight(w, self.compute_dtype)  # noqa: E731
+        f32, pack = blocks.packers(P, self.compute_dtype)
         pr.te0_w, pr.te0_b = f32("time_embed.0.weight"), f32("time_embed.0.bias")
         pr.te2_w, pr.te2_b = f32("time_embed.2.weight"), f32("time_embed.2.bias")
         ws, bs, off = [], [], 0
@@ -115,31 +107,18 @@ class UNetModel(HipModule):
         for b in plan.all_blocks():
             p = b.prefix
             if isinstance(b, SDStemSpec):
-                wpad = torch.zeros((b.cout, 32, 3, 3), dtype=torch.float32, device=dev)
-                wpad[:, :b.cin] = P[f"{p}.weight"].to(torch.float32)
-                pr.blocks[p] = dict(w=pack(wpad), b=f32(f"{p}.bias"))
+                pr.blocks[p] = blocks.stem_weights(P, f32, pack, p, b.cin, b.cout)
             elif isinstance(b, SDResBlockSpec):
                 ws.append(f32(f"{p}.emb_layers.1.weight"))
                 bs.append(f32(f"{p}.emb_layers.1.bias"))
                 pr.emb_off[p] = off
                 off += b.cout
-                d = dict(g1=f32(f"{p}.in_layers.0.weight"), b1=f32(f"{p}.in_layers.0.bias"),
-                         w1=pack(P[f"{p}.in_layers.2.weight"]), c1b=f32(f"{p}.in_layers.2.bias"),
-                         g2=f32(f"{p}.out_layers.0.weight"), b2=f32(f"{p}.out_layers.0.bias"),
-                         w2=pack(P[f"{p}.out_layers.3.weight"]), c2b=f32(f"{p}.out_layers.3.bias"))
-                if b.has_skip_conv:
-                    d["ws"] = pack(P[f"{p}.skip_connection.weight"])
-                    d["wsb"] = f32(f"{p}.skip_connection.bias")
-                    if self.fold_skip:
-                        d["w2f"] = ops.fold_weights(d["w2"], d["ws"])
-                        d["c2fb"] = (d["c2b"] + d["wsb"]).contiguous()
-                pr.blocks[p] = d
+                pr.blocks[p] = blocks.resblock_weights(P, f32, pack, p, blocks.ADM_RES_KEYS, b.has_skip_conv, self.fold_skip)
             elif isinstance(b, SDDownSpec):
                 pr.blocks[p] = dict(w=pack(P[f"{p}.op.weight"]), b=f32(f"{p}.op.bias"),
                                     w2d=ops.pack_conv2d_weight(P[f"{p}.op.weight"], None, self.compute_dtype))   # real stride-2 taps (adm_conv2d)
             elif isinstance(b, SDUpSpec):
-                pr.blocks[p] = dict(w=pack(P[f"{p}.conv.weight"]), b=f32(f"{p}.conv.bias"),
-                                    w_up=ops.pack_conv_weight_up(P[f"{p}.conv.weight"], self.compute_dtype))
+                pr.blocks[p] = blocks.upsample_weights(P, f32, pack, f"{p}.conv", self.compute_dtype)
             elif isinstance(b, SDTransformerSpec):
                 h, dh, dp = b.heads, b.d_head, _padded_head(b.d_head)
                 d = dict(g=f32(f"{p}.norm.weight"), b=f32(f"{p}.norm.bias"), dp=dp,
@@ -173,7 +152,7 @@ class UNetModel(HipModule):
         pr.emb_b = torch.cat(bs, dim=0).contiguous()
         pr.emb_total = off
         pr.zero_bias = torch.zeros(max(zmax, 32), dtype=torch.float32, device=dev)  # the bias-free Linear layers
-        pr.head = dict(g=f32("out.0.weight"), b=f32("out.0.bias"), w=pack(P["out.2.weight"]), cb=f32("out.2.bias"))
+        pr.head = blocks.head_weights(P, f32, pack, "out.0", "out.2")
         pr.graphs = {}  # captured evaluations; they die with the packed weights they point into
         pr.kv_cache = None  # (context key, k|v projections of the cross-attention layers)
         self._packed = pr
@@ -188,15 +167,8 @@ class UNetModel(HipModule):
         off = pr.emb_off[s.prefix]
         aff2 = ops.gn_affine(h, d["g2"], d["b2"], add=emb[:, off:off + s.cout])
         ks2 = self._ks(h, h.shape[3])
-        if s.has_skip_conv:
-            if "w2f" in d and ks2 == 1 and ops.fold_ok(h.shape[1], h.shape[2]):
-                # skip_connection(x) + h (openaimodel.py:262) as extra one-tap K-steps of the out_layers conv (adm_conv_args.fold0)
-                return ops.conv(h, d["w2f"], d["c2fb"], s.cout, 9, aff=aff2, silu=True, fold=(x0, x1), want_stats=True)
-            res = ops.conv(x0, d["ws"], d["wsb"], s.cout, 1, x1=x1)
-        else:
-            assert x1 is None
-            res = x0
-        return ops.conv(h, d["w2"], d["c2b"], s.cout, 9, aff=aff2, silu=True, res=res, want_stats=True, ksplit=ks2)
+        assert s.has_skip_conv or x1 is None
+        return blocks.resblock_tail(d, s.cout, h, aff2, x0, x1, fold=ks2 == 1, ksplit=ks2)   # the folded conv has no split-K schedule
 
     def _transformer(self, pr, s: SDTransformerSpec, x, kvs, n_ctx):
         d = pr.blocks[s.prefix]
@@ -233,7 +205,7 @@ class UNetModel(HipModule):
         for blk in seq:
             d = pr.blocks[blk.prefix]
             if isinstance(blk, SDStemSpec):
-                h = ops.conv(ops.nchw_to_nhwc_pad(x_nchw, 32, self.compute_dtype), d["w"], d["b"], blk.cout, 9, want_stats=True)
+                h = blocks.stem(d, x_nchw, blk.cout, self.compute_dtype)
             elif isinstance(blk, SDResBlockSpec):
                 h = self._resblock(pr, blk, h, skip if first else None, emb)
             elif isinstance(blk, SDTransformerSpec):
@@ -244,10 +216,7 @@ class UNetModel(HipModule):
                 else:              # stride-1 conv + every-second-pixel pick: 4 x the MACs on the faster tile kernel
                     h = ops.resample(ops.conv(h, d["w"], d["b"], blk.channels, 9), "stride2")
             elif isinstance(blk, SDUpSpec):
-                # the four 2x2-tap phase convs of the upsample in one launch (adm_conv_args.up_phase = 5): 4/9 of the MACs,
-                # x 1.2-1.3 on these layers at the search's 6-latent half batches (tools/upconv_bench.py)
-                h = ops.conv(h, d["w"], d["b"], blk.channels, 9, in_up=True, want_stats=True,
-                             w_up=d["w_up"] if self.upconv_phases else None)
+                h = blocks.upsample_conv(d, h, blk.channels, self.upconv_phases)
             else:
                 raise TypeError(blk)
             first = False
@@ -266,7 +235,6 @@ class UNetModel(HipModule):
         if self._packed is not None:
             self._packed.graphs = {}
         return self
-
 
     def enable_splitk(self, flag: bool = True):
         """For the search's batch (n_samples 6, i.e. 6-latent half batches under guidance): the 3x3 convs of the 8x8 and
@@ -351,29 +319,17 @@ class UNetModel(HipModule):
         key = (tuple(x.shape), x.dtype, tuple(timesteps.shape), timesteps.dtype, tuple(context.shape),
                torch.cuda.current_stream(x.device).cuda_stream, self.small_batch_splitk, self.upconv_phases, self.fuse_geglu)
         entry = pr.graphs.get(key)
-        if entry is None:
-            sx, st = x.clone(), timesteps.clone()
-            skv = {k: v.clone() for k, v in kvs.items()}
-            side = torch.cuda.Stream(device=x.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # first calls size per-kernel attributes; they must not land in the capture
-                for _ in range(2):
-                    self._forward(sx, st, skv, context.shape[1], y)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                so = self._forward(sx, st, skv, context.shape[1], y)
-            entry = pr.graphs[key] = [graph, sx, st, skv, so, None]
+        if entry is None:   # static inputs: x, timesteps, then the k|v projections in the order of kvs
+            names = list(kvs)
+            graph, static_in, so, _ = blocks.capture_graph(
+                lambda x_, t_, *kv: self._forward(x_, t_, dict(zip(names, kv)), context.shape[1], y), (x, timesteps, *kvs.values()))
+            entry = pr.graphs[key] = [graph, static_in, so, None]   # None: the k|v dict the static buffers were last filled from
             fresh = True
-        graph, sx, st, skv, so, held = entry
-        sx.copy_(x)
-        st.copy_(timesteps)
-        if fresh or held is not kvs:  # the graph reads its own k|v buffers: refill them only when the conditioning changed
-            for k, v in kvs.items():
-                skv[k].copy_(v)
-            entry[5] = kvs if context_key is not None else None
-        graph.replay()
-        return so.clone()
+        ins = (x, timesteps)
+        if fresh or entry[3] is not kvs:  # the graph reads its own k|v buffers: refill them only when the conditioning changed
+            ins += tuple(kvs.values())
+            entry[3] = kvs if context_key is not None else None
+        return blocks.replay_graph(*entry[:3], ins)
 
     def _forward(self, x, timesteps, kvs, s_ctx, y=None):
         assert y is None, "must specify y if and only if the model is class-conditional"
@@ -385,14 +341,5 @@ class UNetModel(HipModule):
             e = ops.linear_f32(e, pr.te0_w, pr.te0_b)
             e = ops.linear_f32(e, pr.te2_w, pr.te2_b, silu_in=True)
             emb = ops.linear_f32(e, pr.emb_w, pr.emb_b, silu_in=True)  # every ResBlock's emb_layers at once
-            hs: List[torch.Tensor] = []
-            h = None
-            for seq in plan.input_blocks:
-                h = self._run_seq(pr, seq, h, None, emb, kvs, s_ctx, x_nchw=x)
-                hs.append(h)
-            h = self._run_seq(pr, plan.middle_block, h, None, emb, kvs, s_ctx)
-            for seq in plan.output_blocks:
-                h = self._run_seq(pr, seq, h, hs.pop(), emb, kvs, s_ctx)
-            hd = pr.head
-            aff = ops.gn_affine(h, hd["g"], hd["b"])
-            return ops.conv(h, hd["w"], hd["cb"], plan.out_channels, 9, aff=aff, silu=True, out_f32_nchw=True)
+            h = blocks.u_walk(plan, lambda seq, h, skip: self._run_seq(pr, seq, h, skip, emb, kvs, s_ctx, x_nchw=x))
+            return blocks.head(pr.head, h, plan.out_channels)

@@ -24,9 +24,9 @@ from typing import Dict, List, Tuple
 
 import torch
 
-from . import ops
+from . import blocks, ops
 from ._lib import AdmError
-from .unet import HipModule, _Prep
+from .unet import HipModule, _Prep, load_checked
 
 _ATTN_WIDTHS = (32, 48, 64, 80, 96, 128, 160, 192, 256, 512)   # adm_attention's head widths + adm_attention_1h512
 
@@ -173,16 +173,7 @@ class Decoder(HipModule):
         curr_res = resolution // 2 ** (len(plan.ch_mult) - 1)
         self.z_shape = (1, z_channels, curr_res, curr_res)
 
-    @staticmethod
-    def _init_param(name, shape, g):
-        # the reference zero-initialises nothing in this network; HipModule's rule would zero every proj_out
-        leaf = name.rsplit(".", 1)[-1]
-        if len(shape) >= 2:
-            fan_in = 1
-            for s in shape[1:]:
-                fan_in *= s
-            return (torch.rand(shape, generator=g) * 2 - 1) * (1.0 / fan_in) ** 0.5
-        return torch.ones(shape) if leaf == "weight" else torch.zeros(shape)
+    ZERO_INIT = ()   # the reference zero-initialises nothing in this network; HipModule's rule would zero every proj_out
 
     # ------------------------------------------------------------------ weight preparation
     def _prepare(self):
@@ -190,31 +181,22 @@ class Decoder(HipModule):
         if dev.type != "cuda":
             raise AdmError("VAE Decoder: parameters are on the CPU; call .to(device) first (no CPU fallback)")
         pr = _Prep()
-        f32 = lambda k: P[k].to(torch.float32).contiguous()  # noqa: E731
-        pack = lambda w: ops.pack_conv_weight(w, self.compute_dtype)  # noqa: E731
-        wpad = torch.zeros((plan.block_in, 32, 3, 3), dtype=torch.float32, device=dev)
-        wpad[:, :plan.z_channels] = P["conv_in.weight"].to(torch.float32)
-        pr.conv_in = dict(w=pack(wpad), b=f32("conv_in.bias"))
+        f32, pack = blocks.packers(P, self.compute_dtype)
+        pr.conv_in = blocks.stem_weights(P, f32, pack, "conv_in", plan.z_channels, plan.block_in)
         pr.blocks: Dict[str, dict] = {}
         for b in plan.seq:
             p = b.prefix
             if isinstance(b, VaeResSpec):
-                d = dict(g1=f32(f"{p}.norm1.weight"), b1=f32(f"{p}.norm1.bias"), w1=pack(P[f"{p}.conv1.weight"]),
-                         c1b=f32(f"{p}.conv1.bias"), g2=f32(f"{p}.norm2.weight"), b2=f32(f"{p}.norm2.bias"),
-                         w2=pack(P[f"{p}.conv2.weight"]), c2b=f32(f"{p}.conv2.bias"))
-                if b.cin != b.cout:
-                    d["ws"], d["wsb"] = pack(P[f"{p}.nin_shortcut.weight"]), f32(f"{p}.nin_shortcut.bias")
-                pr.blocks[p] = d
+                # fold=False: nin_shortcut has always been its own 1x1 launch here; folding it is a change of the launch sequence
+                pr.blocks[p] = blocks.resblock_weights(P, f32, pack, p, blocks.VAE_RES_KEYS, b.cin != b.cout, fold=False)
             elif isinstance(b, VaeAttnSpec):
                 pr.blocks[p] = dict(g=f32(f"{p}.norm.weight"), b=f32(f"{p}.norm.bias"),
                                     wqkv=pack(torch.cat([P[f"{p}.{k}.weight"].to(torch.float32) for k in "qkv"], 0)),
                                     bqkv=torch.cat([f32(f"{p}.{k}.bias") for k in "qkv"]).contiguous(),
-                                    wo=pack(P[f"{p}.proj_out.weight"]), bo=f32(f"{p}.proj_out.bias"))
+                                    wproj=pack(P[f"{p}.proj_out.weight"]), bproj=f32(f"{p}.proj_out.bias"))
             elif isinstance(b, VaeUpSpec):
-                pr.blocks[p] = {} if not b.with_conv else dict(
-                    w=pack(P[f"{p}.conv.weight"]), b=f32(f"{p}.conv.bias"),
-                    w_up=ops.pack_conv_weight_up(P[f"{p}.conv.weight"], self.compute_dtype))
-        pr.head = dict(g=f32("norm_out.weight"), b=f32("norm_out.bias"), w=pack(P["conv_out.weight"]), cb=f32("conv_out.bias"))
+                pr.blocks[p] = blocks.upsample_weights(P, f32, pack, f"{p}.conv", self.compute_dtype) if b.with_conv else {}
+        pr.head = blocks.head_weights(P, f32, pack, "norm_out", "conv_out")
         self._packed = pr
         return pr
 
@@ -225,15 +207,7 @@ class Decoder(HipModule):
         aff1 = ops.gn_affine(x, d["g1"], d["b1"], eps=self.GN_EPS)
         h = ops.conv(x, d["w1"], d["c1b"], s.cout, 9, aff=aff1, silu=True, want_stats=True)
         aff2 = ops.gn_affine(h, d["g2"], d["b2"], eps=self.GN_EPS)
-        res = x if s.cin == s.cout else ops.conv(x, d["ws"], d["wsb"], s.cout, 1)
-        return ops.conv(h, d["w2"], d["c2b"], s.cout, 9, aff=aff2, silu=True, res=res, want_stats=True)
-
-    def _attn(self, d, s: VaeAttnSpec, x):
-        n, hh, ww, c = x.shape
-        aff = ops.gn_affine(x, d["g"], d["b"], eps=self.GN_EPS)
-        qkv = ops.conv(x, d["wqkv"], d["bqkv"], 3 * c, 1, aff=aff, silu=False).view(n, hh * ww, 3 * c)
-        a = ops.attention(qkv, 1, True)   # one head: softmax(q k^T c^-1/2) v (model.py:186-198)
-        return ops.conv(a.view(n, hh, ww, c), d["wo"], d["bo"], c, 1, res=x, want_stats=True)
+        return blocks.resblock_tail(d, s.cout, h, aff2, x)
 
     def forward_nhwc(self, x):
         """x: 16-bit NHWC [N, H, W, 32] latent map (channels beyond z_channels zero) -> fp32 NCHW [N, out_ch, f H, f W]."""
@@ -250,15 +224,13 @@ class Decoder(HipModule):
                 d = pr.blocks[b.prefix]
                 if isinstance(b, VaeResSpec):
                     h = self._resblock(d, b, h)
-                elif isinstance(b, VaeAttnSpec):
-                    h = self._attn(d, b, h)
+                elif isinstance(b, VaeAttnSpec):   # one head: softmax(q k^T c^-1/2) v (model.py:186-198)
+                    h = blocks.attention(d, h, 1, True, eps=self.GN_EPS)
                 elif b.with_conv:
-                    h = ops.conv(h, d["w"], d["b"], b.channels, 9, in_up=True, want_stats=True, w_up=d["w_up"])
+                    h = blocks.upsample_conv(d, h, b.channels, True)
                 else:
                     h = ops.resample(h, "up")
-            hd = pr.head
-            aff = ops.gn_affine(h, hd["g"], hd["b"], eps=self.GN_EPS)
-            return ops.conv(h, hd["w"], hd["cb"], plan.out_ch, 9, aff=aff, silu=True, out_f32_nchw=True)
+            return blocks.head(pr.head, h, plan.out_ch, eps=self.GN_EPS)
 
     def forward(self, z):
         """z fp32 NCHW [N, z_channels, H, W] (the tensor the reference's Decoder takes) -> fp32 NCHW images."""
@@ -306,11 +278,7 @@ class AutoencoderKL:
             raise RuntimeError(f"Error(s) in loading state_dict for AutoencoderKL: missing keys {missing[:5]}... "
                                f"unexpected keys {([f'decoder.{k}' for k in bad] + unexpected)[:5]}...")
         self.decoder.load_state_dict(dec, strict=True)
-        for k, v in mine.items():
-            v = torch.as_tensor(v)
-            if tuple(v.shape) != tuple(self._params[k].shape):
-                raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._params[k].shape)}")
-            self._params[k] = v.detach().to(device=self._params[k].device, dtype=torch.float32).clone()
+        load_checked(self._params, mine)
         return [], unexpected
 
     def to(self, device):

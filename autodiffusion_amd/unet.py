@@ -21,13 +21,13 @@ conv1x1 [+residual].  The 36 emb_layers Linear projections run as ONE fp32 GEMM 
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, Optional, Sequence
 
 import os
 
 import torch
 
-from . import ops
+from . import blocks, ops
 from ._lib import AdmError
 from .arch import AttnSpec, HeadSpec, ResBlockSpec, ResampleSpec, StemSpec, UNetPlan
 
@@ -51,6 +51,17 @@ def warn_compute_dtype(what: str, flag: str):
            "bf16, 1.3e-3 in fp16 (the reference's own fp16 torso: 1.4e-3; tests/test_hip_fullsize.py)")
     logger.warn("WARNING: " + msg)
     warnings.warn(msg, stacklevel=3)
+
+
+def load_checked(params, sd):
+    """Copy the tensors of sd whose keys params has (fp32, on the parameter's device); a shape mismatch raises."""
+    for k, v in sd.items():
+        if k not in params:
+            continue
+        v = torch.as_tensor(v)
+        if tuple(v.shape) != tuple(params[k].shape):
+            raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(params[k].shape)}")
+        params[k] = v.detach().to(device=params[k].device, dtype=torch.float32).clone()
 
 
 class HipModule:
@@ -80,11 +91,13 @@ class HipModule:
         for name, shape in plan.param_shapes().items():
             self._params[name] = self._init_param(name, shape, g)
 
-    @staticmethod
-    def _init_param(name, shape, g):
+    ZERO_INIT = _ZERO_INIT_SUFFIXES   # zero_module (unet.py:224-226; openaimodel.py:224-226, 703; attention.py:241-245)
+
+    @classmethod
+    def _init_param(cls, name, shape, g):
         # zero_module'd tensors start at zero like the reference; the rest get a fan-in scaled
         # uniform draw (checkpoints overwrite everything; only the zero pattern is behavioural)
-        if name.endswith(_ZERO_INIT_SUFFIXES) or name in ("out.2.weight", "out.2.bias"):
+        if name.endswith(cls.ZERO_INIT) or name in ("out.2.weight", "out.2.bias"):
             return torch.zeros(shape)
         leaf = name.rsplit(".", 1)[-1]
         if len(shape) >= 2:
@@ -107,13 +120,7 @@ class HipModule:
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict: missing keys {missing[:5]}... "
                                f"unexpected keys {unexpected[:5]}...")
-        for k, v in sd.items():
-            if k not in self._params:
-                continue
-            v = torch.as_tensor(v)
-            if tuple(v.shape) != tuple(self._params[k].shape):
-                raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._params[k].shape)}")
-            self._params[k] = v.detach().to(device=self._params[k].device, dtype=torch.float32).clone()
+        load_checked(self._params, sd)
         self._packed = None
         return missing, unexpected
 
@@ -182,21 +189,6 @@ class HipModule:
 class _Prep:
     """Device-resident, kernel-ready parameters derived from the state dict."""
     pass
-
-
-def _graph_pool_bytes(graph, dev, reserved0, free0) -> int:
-    """Bytes of the private allocator pool a just-captured graph owns: the segments tagged with the graph's pool id in the caching
-    allocator's snapshot; if the snapshot does not tell (older / newer torch), the growth of reserved memory or the drop of free
-    device memory across the capture, whichever is larger."""
-    try:
-        pid = tuple(graph.pool())
-        got = sum(seg["total_size"] for seg in torch.cuda.memory_snapshot() if tuple(seg.get("segment_pool_id", (0, 0))) == pid
-                  and seg.get("device", dev.index) == dev.index)
-        if got > 0:
-            return int(got)
-    except Exception:
-        pass
-    return int(max(0, torch.cuda.memory_reserved(dev) - reserved0, free0 - torch.cuda.mem_get_info(dev)[0]))
 
 
 class AdmNet(HipModule):
@@ -292,40 +284,21 @@ class AdmNet(HipModule):
                                                                        self.upconv_phases, getattr(self, "fuse_gn_bwd", None))
         entry = graphs.get(key)
         if entry is None:
-            static_in = [t.clone() for t in inputs]
-            cur = torch.cuda.current_stream(dev)
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):  # first calls size per-kernel attributes; they must not land in the capture
-                for _ in range(2):
-                    fn(*static_in)
-            cur.wait_stream(side)
-            reserved0, free0 = torch.cuda.memory_reserved(dev), torch.cuda.mem_get_info(dev)[0]
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                out = fn(*static_in)
-            pool = _graph_pool_bytes(graph, dev, reserved0, free0)
+            entry = graphs[key] = blocks.capture_graph(fn, inputs)
+            pool = entry[3]
             self._pool_bytes_seen = max(self._pool_bytes_seen, pool)
-            entry = graphs[key] = (graph, static_in, out, pool)
             budget = self._graph_budget()
             while len(graphs) > 1 and (len(graphs) > self.GRAPH_CACHE or sum(e[3] for e in graphs.values()) > budget):
                 graphs.popitem(last=False)
             if self._planned_sets * pool > budget:
                 # this candidate's launch sequences do not fit together: replay this one, then go eager (plan_graphs logs why)
-                for s_, t in zip(static_in, inputs):
-                    s_.copy_(t)
-                graph.replay()
-                res = tuple(o.clone() for o in out) if isinstance(out, tuple) else out.clone()
+                res = blocks.replay_graph(*entry[:3], inputs)
                 graphs.pop(key, None)
                 self.plan_graphs(self._planned_sets)
                 return res
         else:
             graphs.move_to_end(key)
-        graph, static_in, out = entry[:3]
-        for s_, t in zip(static_in, inputs):
-            s_.copy_(t)
-        graph.replay()
-        return tuple(o.clone() for o in out) if isinstance(out, tuple) else out.clone()
+        return blocks.replay_graph(*entry[:3], inputs)
 
     # ------------------------------------------------------------------ weight preparation
     def _prepare(self):
@@ -336,9 +309,8 @@ class AdmNet(HipModule):
                            "(the HIP path has no CPU fallback)")
         pr = _Prep()
         cd = self.compute_dtype
-        pack = lambda w: ops.pack_conv_weight(w, cd)          # noqa: E731
+        f32, pack = blocks.packers(P, cd)
         pack_bwd = lambda w: ops.pack_conv_weight_bwd(w, cd)  # noqa: E731
-        f32 = lambda k: P[k].to(torch.float32).contiguous()  # noqa: E731
         pr.te0_w, pr.te0_b = f32("time_embed.0.weight"), f32("time_embed.0.bias")
         pr.te2_w, pr.te2_b = f32("time_embed.2.weight"), f32("time_embed.2.bias")
         pr.label = f32("label_emb.weight") if self.plan.num_classes is not None else None
@@ -349,37 +321,22 @@ class AdmNet(HipModule):
         for b in self.plan.all_blocks():
             p = b.prefix
             if isinstance(b, StemSpec):
-                # stem on the MFMA conv kernel: input channels zero-padded to one 32-channel chunk
-                w = P[f"{p}.weight"].to(torch.float32)
-                wpad = torch.zeros((b.cout, 32, 3, 3), dtype=torch.float32, device=dev)
-                wpad[:, :b.cin] = w
-                pr.blocks[p] = dict(w=pack(wpad), b=f32(f"{p}.bias"))
+                pr.blocks[p] = blocks.stem_weights(P, f32, pack, p, b.cin, b.cout)
             elif isinstance(b, ResBlockSpec):
                 ws.append(f32(f"{p}.emb_layers.1.weight"))
                 bs.append(f32(f"{p}.emb_layers.1.bias"))
                 pr.film_off[p] = off
                 off += (2 if b.scale_shift else 1) * b.cout   # (scale | shift), or the additive embedding of use_scale_shift_norm=False
-                d = dict(
-                    g1=f32(f"{p}.in_layers.0.weight"), b1=f32(f"{p}.in_layers.0.bias"),
-                    w1=pack(P[f"{p}.in_layers.2.weight"]), c1b=f32(f"{p}.in_layers.2.bias"),
-                    g2=f32(f"{p}.out_layers.0.weight"), b2=f32(f"{p}.out_layers.0.bias"),
-                    w2=pack(P[f"{p}.out_layers.3.weight"]), c2b=f32(f"{p}.out_layers.3.bias"),
-                )
-                if b.has_skip_conv:
-                    d["ws"] = pack(P[f"{p}.skip_connection.weight"])
-                    d["wsb"] = f32(f"{p}.skip_connection.bias")
-                    if self.fold_skip and not (b.up or b.down):   # skip_connection as extra K-steps of the out_layers conv (ops.conv(fold=))
-                        d["w2f"] = ops.fold_weights(d["w2"], d["ws"])
-                        d["c2fb"] = (d["c2b"] + d["wsb"]).contiguous()
-                elif b.up:   # up-ResBlock: the first conv reads a 2x upsample -> four 2x2-tap phase convs (ops.pack_conv_weight_up)
+                d = blocks.resblock_weights(P, f32, pack, p, blocks.ADM_RES_KEYS, b.has_skip_conv,
+                                            self.fold_skip and not (b.up or b.down))
+                if b.up and not b.has_skip_conv:   # up-ResBlock: the first conv reads a 2x upsample -> four 2x2-tap phase convs (ops.pack_conv_weight_up)
                     d["w1_up"] = ops.pack_conv_weight_up(P[f"{p}.in_layers.2.weight"], cd)
                 pr.blocks[p] = d
             elif isinstance(b, ResampleSpec):
                 if b.use_conv and b.down:     # 3x3 stride-2 conv at its own 9 taps per output pixel: the general conv2d kernel
                     pr.blocks[p] = dict(w2d=ops.pack_conv2d_weight(P[f"{p}.op.weight"], None, cd), b=f32(f"{p}.op.bias"))
                 elif b.use_conv:              # conv3x3(nearest 2x): the virtual-upsample conv, as four 2x2-tap phase convs
-                    pr.blocks[p] = dict(w=pack(P[f"{p}.conv.weight"]), b=f32(f"{p}.conv.bias"),
-                                        w_up=ops.pack_conv_weight_up(P[f"{p}.conv.weight"], cd))
+                    pr.blocks[p] = blocks.upsample_weights(P, f32, pack, f"{p}.conv", cd)
             elif isinstance(b, AttnSpec):
                 pr.blocks[p] = dict(
                     g=f32(f"{p}.norm.weight"), b=f32(f"{p}.norm.bias"),
@@ -413,11 +370,11 @@ class AdmNet(HipModule):
                     d["wproj_bwd"] = pack_bwd(P[f"{p}.proj_out.weight"])
                     zmax = max(zmax, 3 * b.channels)
             pr.zero_bias = torch.zeros(zmax, dtype=torch.float32, device=dev)
-        self._prepare_head(pr, P, f32)
+        self._prepare_head(pr, P, f32, pack)
         self._packed = pr
         return pr
 
-    def _prepare_head(self, pr, P, f32):
+    def _prepare_head(self, pr, P, f32, pack):
         pass
 
     # ------------------------------------------------------------------ blocks
@@ -469,14 +426,7 @@ class AdmNet(HipModule):
             aff2 = ops.gn_affine(h, d["g2"], d["b2"], add=film[:, off:off + s.cout])
         else:
             aff2 = ops.gn_affine(h, d["g2"], d["b2"], film=film[:, off:], film_stride=pr.film_total)
-        if s.has_skip_conv:
-            if "w2f" in d and mode is None and ops.fold_ok(h.shape[1], h.shape[2]):
-                # `self.skip_connection(x) + h` (reference unet.py:256) inside the out_layers conv: no 1x1 launch, no residual operand
-                return ops.conv(h, d["w2f"], d["c2fb"], s.cout, 9, aff=aff2, silu=True, fold=(xs, xs1), want_stats=True)
-            res = ops.conv(xs, d["ws"], d["wsb"], s.cout, 1, x1=xs1)
-        else:
-            res = xs
-        return ops.conv(h, d["w2"], d["c2b"], s.cout, 9, aff=aff2, silu=True, res=res, res_up=virtual_up, want_stats=True)
+        return blocks.resblock_tail(d, s.cout, h, aff2, xs, xs1, fold=mode is None, res_up=virtual_up)
 
     def _resample(self, pr, s: ResampleSpec, x):
         """Downsample / Upsample of a resblock_updown=False model (reference unet.py:78-141)."""
@@ -485,35 +435,27 @@ class AdmNet(HipModule):
         d = pr.blocks[s.prefix]
         if s.down:
             return ops.conv2d(x, d["w2d"], d["b"], 3, 3, stride=2, pad=(1, 1), relu=False)
-        if x.shape[1] >= 8 and x.shape[2] >= 8:
-            return ops.conv(x, d["w"], d["b"], s.channels, 9, in_up=True, want_stats=True,
-                            w_up=d["w_up"] if self.upconv_phases else None)
-        return ops.conv(ops.resample(x, "up"), d["w"], d["b"], s.channels, 9, want_stats=True)   # maps below 8x8: materialised
+        return blocks.upsample_conv(d, x, s.channels, self.upconv_phases)
 
     def _attention(self, pr, s: AttnSpec, x, skipped, tape=None):
         if skipped:  # dynamic_unet.py:316-318
             return x
         d = pr.blocks[s.prefix]
-        n, hh, ww, c = x.shape
-        if tape is not None:
-            a_, b_, st = ops.gn_affine(x, d["g"], d["b"], want_stats=True)
-            aff = (a_, b_)
-        else:
-            aff = ops.gn_affine(x, d["g"], d["b"])
+        if tape is None:
+            return blocks.attention(d, x, s.num_heads, s.new_order)
+        n, hh, ww, c = x.shape   # the same launches, keeping what the backward pass needs (statistics, qkv, log-sum-exp)
+        a_, b_, st = ops.gn_affine(x, d["g"], d["b"], want_stats=True)
+        aff = (a_, b_)
         qkv = ops.conv(x, d["wqkv"], d["bqkv"], 3 * c, 1, aff=aff, silu=False)
-        if tape is not None:
-            a, lse = ops.attention(qkv.view(n, hh * ww, 3 * c), s.num_heads, s.new_order, want_lse=True)
-            tape.append(("attn", s, dict(x=x, aff=aff, st=st, qkv=qkv, a=a, lse=lse)))
-        else:
-            a = ops.attention(qkv.view(n, hh * ww, 3 * c), s.num_heads, s.new_order)
+        a, lse = ops.attention(qkv.view(n, hh * ww, 3 * c), s.num_heads, s.new_order, want_lse=True)
+        tape.append(("attn", s, dict(x=x, aff=aff, st=st, qkv=qkv, a=a, lse=lse)))
         return ops.conv(a.view(n, hh, ww, c), d["wproj"], d["bproj"], c, 1, res=x, want_stats=True)
 
     def _run_seq(self, pr, seq, h, skip, film, skip_ids, x_nchw=None, tape=None):
         first = True
         for blk in seq:
             if isinstance(blk, StemSpec):
-                d = pr.blocks[blk.prefix]
-                h = ops.conv(ops.nchw_to_nhwc_pad(x_nchw, 32, self.compute_dtype), d["w"], d["b"], blk.cout, 9, want_stats=True)
+                h = blocks.stem(pr.blocks[blk.prefix], x_nchw, blk.cout, self.compute_dtype)
                 if tape is not None:
                     tape.append(("stem", blk, {}))
             elif isinstance(blk, ResBlockSpec):
@@ -549,10 +491,9 @@ class UNetModel(AdmNet):
             raise ValueError("use EncoderUNetModel for classifier plans")
         super().__init__(plan, use_fp16)
 
-    def _prepare_head(self, pr, P, f32):
+    def _prepare_head(self, pr, P, f32, pack):
         h = self.plan.head
-        pr.head = dict(g=f32(f"{h.prefix}.0.weight"), b=f32(f"{h.prefix}.0.bias"),
-                       w=ops.pack_conv_weight(P[f"{h.prefix}.2.weight"], self.compute_dtype), cb=f32(f"{h.prefix}.2.bias"))
+        pr.head = blocks.head_weights(P, f32, pack, f"{h.prefix}.0", f"{h.prefix}.2")
 
     def forward(self, x, timesteps, y=None, skip_layer: Sequence[int] = ()):
         """x fp32 [N,C,H,W], timesteps [N] (original-process timesteps), y int64 [N] or None."""
@@ -572,18 +513,8 @@ class UNetModel(AdmNet):
     def _forward(self, pr, x, timesteps, y, skip_ids):
         with torch.no_grad():
             film = self._embed(pr, timesteps, y)
-            hs: List[torch.Tensor] = []
-            h = None
-            for seq in self.plan.input_blocks:
-                h = self._run_seq(pr, seq, h, None, film, skip_ids, x_nchw=x)
-                hs.append(h)
-            h = self._run_seq(pr, self.plan.middle_block, h, None, film, skip_ids)
-            for seq in self.plan.output_blocks:
-                h = self._run_seq(pr, seq, h, hs.pop(), film, skip_ids)
-            hd = pr.head
-            aff = ops.gn_affine(h, hd["g"], hd["b"])
-            return ops.conv(h, hd["w"], hd["cb"], self.plan.out_channels, 9, aff=aff, silu=True,
-                            out_f32_nchw=True)
+            h = blocks.u_walk(self.plan, lambda seq, h, skip: self._run_seq(pr, seq, h, skip, film, skip_ids, x_nchw=x))
+            return blocks.head(pr.head, h, self.plan.out_channels)
 
 
 Dynamic_UNetModel = UNetModel  # the plan's `dynamic` flag carries the difference
