@@ -122,6 +122,10 @@ SIGNATURES = {
     "adm_attention_1h512": (_I, [_P, _P, _I, _I, _P]),
     "adm_vae_latent_in": (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P]),
     "adm_vae_image_out": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "adm_clip_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "adm_attention_causal": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "adm_quick_gelu": (_I, [_P, _P, C.c_int64, _I, _P]),
+    "adm_layernorm_f32out": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
 }
 
 _libs = {}

@@ -550,6 +550,75 @@ def geglu(u):
     return out
 
 
+# ------------------------------------------------------------------ CLIP text transformer (csrc/adm_clip.hip)
+def _act16(t, name):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype not in (BF16, F16):
+        raise AdmError(f"{name}: expected a bfloat16 or float16 device tensor (the HIP path has no CPU fallback)")
+    return t
+
+
+def clip_embed(ids, tok, pos, pitch: int, dtype=BF16):
+    """ids int64 [N, T], tok fp32 [V, C], pos fp32 [P, C] (T <= P) -> 16-bit [N, pitch, C]: rows < T = tok[ids] + pos[:T] (fp32
+    add, one rounding), rows >= T zero.  An id outside [0, V) raises here, before any launch (one host read of the ids)."""
+    if not torch.is_tensor(ids) or ids.dim() != 2 or ids.dtype != torch.int64:
+        raise AdmError("clip_embed: ids must be an int64 [N, T] tensor")
+    if tok.dim() != 2 or pos.dim() != 2 or tok.shape[1] != pos.shape[1]:
+        raise AdmError(f"clip_embed: token table {tuple(tok.shape)} / position table {tuple(pos.shape)} do not match")
+    n, t = ids.shape
+    (v, c), p = tok.shape, pos.shape[0]
+    if n < 1 or t < 1 or t > p or pitch < t:
+        raise AdmError(f"clip_embed: {n} x {t} ids with {p} positions and pitch {pitch}")
+    ip, tp, pp = _ptr(ids, torch.int64, "ids"), _ptr(tok, torch.float32, "tok"), _ptr(pos, torch.float32, "pos")
+    host = ids.cpu()   # N x T integers: the range check is host work, not a device reduction
+    lo, hi = int(host.min()), int(host.max())
+    if lo < 0 or hi >= v:
+        raise AdmError(f"clip_embed: token ids span [{lo}, {hi}], the vocabulary is [0, {v})")
+    out = torch.empty((n, pitch, c), dtype=dtype, device=ids.device)
+    check(_L(out).adm_clip_embed(ip, tp, pp, _ptr(out), n, t, pitch, c, v, p, _stream()), "adm_clip_embed")
+    return out
+
+
+def attention_causal(qkv, heads: int, t: int = None, out=None):
+    """qkv 16-bit [N, pitch, 3*H*64] (q | k | v thirds, head h at columns h*64 of each) -> 16-bit [N, pitch, H*64] =
+    softmax(q k^T / 8 + causal mask) v over the first t rows (default: all) of every prompt.  Rows >= t are neither read nor
+    written: a fresh output has them zeroed; `out` (same shape and type) keeps what it holds there."""
+    _act16(qkv, "attention_causal: qkv")
+    if qkv.dim() != 3 or heads < 1 or qkv.shape[2] != 3 * heads * 64:
+        raise AdmError(f"attention_causal: expected [N, pitch, {3 * heads * 64}] for {heads} heads of 64 channels, got {tuple(qkv.shape)}")
+    n, pitch, c3 = qkv.shape
+    t = pitch if t is None else int(t)
+    if not 1 <= t <= min(pitch, 256):
+        raise AdmError(f"attention_causal: t = {t} outside 1 .. min(pitch = {pitch}, 256)")
+    if out is None:
+        out = (torch.empty if t == pitch else torch.zeros)((n, pitch, c3 // 3), dtype=qkv.dtype, device=qkv.device)
+    elif tuple(out.shape) != (n, pitch, c3 // 3) or out.dtype != qkv.dtype:
+        raise AdmError(f"attention_causal: out {tuple(out.shape)} {out.dtype} does not match {(n, pitch, c3 // 3)} {qkv.dtype}")
+    check(_L(qkv).adm_attention_causal(_ptr(qkv, qkv.dtype, "qkv"), _ptr(out, qkv.dtype, "out"), n, t, pitch, heads, 64, _stream()),
+          "adm_attention_causal")
+    return out
+
+
+def quick_gelu(u):
+    """16-bit [..., I] -> u * sigmoid(1.702 u) (fp32 math), same type."""
+    _act16(u, "quick_gelu: u")
+    inner = u.shape[-1]
+    out = torch.empty_like(u)
+    check(_L(u).adm_quick_gelu(_ptr(u, u.dtype, "u"), _ptr(out), u.numel() // inner, inner, _stream()), "adm_quick_gelu")
+    return out
+
+
+def layernorm_f32out(x, t: int, gamma, beta, eps: float = 1e-5):
+    """16-bit [N, pitch, C] -> fp32 [N, t, C]: LayerNorm over C (fp32 statistics) of the first t rows of every prompt."""
+    _act16(x, "layernorm_f32out: x")
+    if x.dim() != 3 or not 1 <= t <= x.shape[1]:
+        raise AdmError(f"layernorm_f32out: expected [N, pitch >= t = {t}, C], got {tuple(x.shape)}")
+    n, pitch, c = x.shape
+    out = torch.empty((n, t, c), dtype=torch.float32, device=x.device)
+    check(_L(x).adm_layernorm_f32out(_ptr(x, x.dtype, "x"), _ptr(gamma, torch.float32, "gamma"), _ptr(beta, torch.float32, "beta"),
+                                     _ptr(out), n, t, pitch, c, float(eps), _stream()), "adm_layernorm_f32out")
+    return out
+
+
 # ------------------------------------------------------------------ backward-data (classifier guidance)
 def attention_bwd(qkv, out, dout, lse, heads: int, new_order: bool):
     n, t, c3 = qkv.shape

@@ -11,9 +11,13 @@ Kept from the reference: one sampler call per batch of the conditioning iterable
 (``calculate_fid(..., batch_size=320)``, :561); with ``opt.fixed_code`` one start code is drawn per call and reused for every
 batch (:506-508, :537); the ``sample_time`` / ``fid_time`` log line (:565).
 
-Different by design: the prompts arrive as precomputed ``(c, uc)`` embeddings (the CLIP text encoder is not built here), and the
-start noise always comes from a CPU generator seeded from (seed, candidate, batch index) and is passed as ``x_T`` -- a
-candidate's score does not depend on what was evaluated before it.
+The first line of the reference loop, ``c = model.get_learned_conditioning(prompts)`` (:520-526), runs here too when the evaluator
+is fed ``prompts=`` (``sd_clip.FrozenCLIPEmbedder`` as the model's cond stage); ``conditioning=`` keeps taking precomputed
+``(c, uc)`` embeddings.
+
+Different by design: the empty prompt of classifier-free guidance is encoded once per evaluator, not once per batch (the encoder
+is deterministic, so the value is the same), and the start noise always comes from a CPU generator seeded from (seed, candidate,
+batch index) and is passed as ``x_T`` -- a candidate's score does not depend on what was evaluated before it.
 """
 from __future__ import annotations
 
@@ -57,15 +61,22 @@ def inception_features(net, dims: int = 2048, allow_random: bool = False):
 
 
 class SDCandidateEvaluator:
-    def __init__(self, model, sampler, conditioning, ref_mu, ref_sigma, num_samples: int, *, features=None, inception=None,
-                 dims: int = 2048, allow_random_inception: bool = False, seed: int = 0, device=None, image_out=None,
-                 accumulator=None):
+    def __init__(self, model, sampler, conditioning=None, ref_mu=None, ref_sigma=None, num_samples: int = None, *, prompts=None,
+                 features=None, inception=None, dims: int = 2048, allow_random_inception: bool = False, seed: int = 0,
+                 device=None, image_out=None, accumulator=None):
         """model: ``sd_sampler.LatentDiffusion`` with a first stage (``decode_first_stage``); sampler: one of the
         ``sd_sampler`` samplers around it; conditioning: iterable of per-batch ``(c, uc)`` device tensors (``uc`` may be None
-        when ``opt.scale == 1``), re-iterated by every call; features: callable float [N, 3, H, W] in [0, 1] -> [N, dims]
+        when ``opt.scale == 1``), re-iterated by every call; prompts (instead of conditioning; the model then needs a cond
+        stage): iterable of per-batch prompts -- a list or tuple of strings, or an integer tensor [n_samples, T] of token ids --
+        encoded by ``model.get_learned_conditioning``; features: callable float [N, 3, H, W] in [0, 1] -> [N, dims]
         (default: ``inception`` -- an ``InceptionV3`` -- through ``inception_features``).
         image_out / accumulator: the clamp launch and the statistics sink, replaceable for host-only tests of the batch plan."""
-        self.model, self.sampler, self.conditioning = model, sampler, conditioning
+        if (conditioning is None) == (prompts is None):
+            raise ValueError("SDCandidateEvaluator: pass exactly one of conditioning= (precomputed (c, uc) batches) and prompts=")
+        if ref_mu is None or ref_sigma is None or num_samples is None:
+            raise ValueError("SDCandidateEvaluator: ref_mu, ref_sigma and num_samples are required")
+        self.model, self.sampler, self.conditioning, self.prompts = model, sampler, conditioning, prompts
+        self._uc = {}            # n_samples -> the encoded empty prompt
         self.ref_stats = FIDStatistics(np.asarray(ref_mu, dtype=np.float64), np.asarray(ref_sigma, dtype=np.float64))
         self.num_samples, self.seed, self.dims = int(num_samples), int(seed), int(dims)
         self.device = torch.device(device) if device is not None else getattr(model, "device", torch.device("cpu"))
@@ -88,6 +99,22 @@ class SDCandidateEvaluator:
         x = torch.randn([opt.n_samples, opt.C, opt.H // opt.f, opt.W // opt.f], generator=g, dtype=torch.float32)
         return x.to(self.device)
 
+    # ------------------------------------------------------------------ search_ea.py:520-526
+    def _batches(self, opt):
+        """Per-batch (c, uc): the conditioning iterable as it is, or the prompts through the model's cond stage."""
+        if self.prompts is None:
+            yield from self.conditioning
+            return
+        for prompts in self.prompts:
+            uc = None
+            if opt.scale != 1.0:
+                uc = self._uc.get(opt.n_samples)
+                if uc is None:
+                    uc = self._uc[opt.n_samples] = self.model.get_learned_conditioning(opt.n_samples * [""])
+            if isinstance(prompts, tuple):
+                prompts = list(prompts)
+            yield self.model.get_learned_conditioning(prompts), uc
+
     # ------------------------------------------------------------------ search_ea.py:504-566
     def get_cand_fid(self, cand=None, opt=None, device=None):
         t1 = time.time()
@@ -98,7 +125,7 @@ class SDCandidateEvaluator:
         acc = self._accumulator()
         stage, fill, count, plan = None, 0, 0, []
         with torch.no_grad():
-            for itr, (c, uc) in enumerate(self.conditioning):
+            for itr, (c, uc) in enumerate(self._batches(opt)):
                 if opt.scale == 1.0:
                     uc = None
                 seed = batch_seed(seed0, 0 if opt.fixed_code else itr)
@@ -128,7 +155,7 @@ class SDCandidateEvaluator:
             if fill:
                 acc.add(self.features(stage[:fill]))
         if count == 0:
-            raise AdmError("SDCandidateEvaluator: the conditioning iterable is empty")
+            raise AdmError("SDCandidateEvaluator: the conditioning / prompts iterable is empty")
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         sample_time = time.time() - t1

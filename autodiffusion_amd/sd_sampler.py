@@ -75,7 +75,7 @@ class LatentDiffusion:
     parameterization = "eps"
 
     def __init__(self, unet, timesteps=1000, beta_schedule="linear", linear_start=0.00085, linear_end=0.0120,
-                 cosine_s=8e-3, device=None, first_stage=None, scale_factor=0.18215):
+                 cosine_s=8e-3, device=None, first_stage=None, scale_factor=0.18215, cond_stage=None):
         betas = make_beta_schedule(beta_schedule, timesteps, linear_start=linear_start, linear_end=linear_end,
                                    cosine_s=cosine_s)
         ac = np.cumprod(1.0 - betas, axis=0)
@@ -87,6 +87,14 @@ class LatentDiffusion:
         self.model = unet
         self.first_stage_model = first_stage       # sd_vae.AutoencoderKL (None: latents only, as before)
         self.scale_factor = float(scale_factor)
+        self.cond_stage_model = cond_stage         # sd_clip.FrozenCLIPEmbedder (None: the caller brings embeddings, as before)
+
+    def get_learned_conditioning(self, c):
+        """ddpm.py:551-562, the ``encode`` branch: prompts (list of strings, or an integer tensor of token ids) -> fp32
+        [N, T, context_dim] device embeddings."""
+        if self.cond_stage_model is None:
+            raise AdmError("LatentDiffusion.get_learned_conditioning: constructed without cond_stage= (sd_clip.FrozenCLIPEmbedder)")
+        return self.cond_stage_model.encode(c)
 
     DECODE_CHUNK_64 = 8   # latents per decoder pass at 64 x 64 (peak: two 512 x 512 x 128 16-bit maps + the fp32 image per latent)
 
@@ -119,13 +127,15 @@ class LatentDiffusion:
 
     def load_state_dict(self, sd, strict=True):
         """A full latent-diffusion checkpoint's state dict: ``model.diffusion_model.*`` goes to the UNet, ``first_stage_model.*``
-        to the first stage (when one was given); everything else (``cond_stage_model.*``, ``model_ema.*``, the schedule buffers)
-        is not used on this path and is reported in one log line.  Returns {route: number of tensors}."""
+        to the first stage and ``cond_stage_model.*`` to the cond stage (each when one was given); everything else
+        (``model_ema.*``, the schedule buffers, the stages not given) is not used on this path and is reported in one log line.
+        Returns {route: number of tensors}; ``cond_stage_model`` is among the routes only when a cond stage was given."""
         from . import logger
-        parts = {attr: {} for _, attr in self._ROUTES}
+        routes = self._ROUTES + ((("cond_stage_model.", "cond_stage_model"),) if self.cond_stage_model is not None else ())
+        parts = {attr: {} for _, attr in routes}
         other = {}
         for k, v in sd.items():
-            for prefix, attr in self._ROUTES:
+            for prefix, attr in routes:
                 if k.startswith(prefix):
                     parts[attr][k[len(prefix):]] = v
                     break
@@ -137,10 +147,17 @@ class LatentDiffusion:
             self.first_stage_model.load_state_dict(parts["first_stage_model"], strict=strict)
         elif parts["first_stage_model"]:
             other["first_stage_model"] = len(parts["first_stage_model"])
-        logger.log("LatentDiffusion.load_state_dict: %d UNet tensors, %d first-stage tensors; not used on this path: %s"
-                   % (len(parts["model"]), len(parts["first_stage_model"]) if self.first_stage_model is not None else 0,
+        cond = ""
+        if self.cond_stage_model is not None:
+            self.cond_stage_model.load_state_dict(parts["cond_stage_model"], strict=strict)
+            cond = ", %d cond-stage tensors" % len(parts["cond_stage_model"])
+        logger.log("LatentDiffusion.load_state_dict: %d UNet tensors, %d first-stage tensors%s; not used on this path: %s"
+                   % (len(parts["model"]), len(parts["first_stage_model"]) if self.first_stage_model is not None else 0, cond,
                       ", ".join(f"{k} ({v})" for k, v in sorted(other.items())) or "none"))
-        return {"model": len(parts["model"]), "first_stage_model": len(parts["first_stage_model"]), "ignored": other}
+        out = {"model": len(parts["model"]), "first_stage_model": len(parts["first_stage_model"]), "ignored": other}
+        if self.cond_stage_model is not None:
+            out["cond_stage_model"] = len(parts["cond_stage_model"])
+        return out
 
     def apply_model(self, x_noisy, t, cond, context_key=None):
         if context_key is not None and getattr(self.model, "accepts_context_key", False):

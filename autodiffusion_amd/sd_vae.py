@@ -14,7 +14,7 @@ Engine: 16-bit NHWC activations, every op a libadm_hip.so launch (ops.py).  Per 
   Upsample (:53-57)              conv3x3 reading its input through the virtual nearest 2x upsample (four 2x2-tap phase convs
                                  from 16x16 sources up), or ops.resample(x, "up") without the conv
   head                           gn -> conv3x3[affine+SiLU] with the fp32 NCHW epilogue
-The encoder, the CLIP text encoder and non-square latents are not built.
+The encoder and non-square latents are not built (the CLIP text encoder is sd_clip.py).
 """
 from __future__ import annotations
 

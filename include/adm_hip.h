@@ -430,6 +430,27 @@ int adm_vae_latent_in(const float* z, const float* w, const float* b, float inv_
                       int w_, void* stream);
 int adm_vae_image_out(const float* x, float* unit, uint8_t* u8, int n, int h, int w, void* stream);
 
+/* ---------------------------------------------------------------- CLIP text transformer (K15: Stable Diffusion cond stage)
+ * FrozenCLIPEmbedder (ldm/modules/encoders/modules.py:137-162) = transformers' CLIPTextModel: pre-LN layers of causal
+ * self-attention and a quick_gelu MLP.  The projections are adm_conv 1x1 launches over the token rows of a prompt laid out as a
+ * pixel map of `pitch` >= t rows, the inner LayerNorms adm_layernorm; these are the four pieces those do not cover.
+ *   adm_clip_embed        out 16-bit [n][pitch][c]: row r < t of prompt i = tok[ids[i][r]] + pos[r] (fp32 add, one rounding), rows
+ *                         t .. pitch-1 = 0.  ids int64 [n][t], tok fp32 [vocab][c], pos fp32 [positions][c], t <= positions,
+ *                         c % 8 == 0.  An id outside [0, vocab) is the caller's error; the kernel clamps it into the table.
+ *   adm_attention_causal  qkv 16-bit [n][pitch][3*heads*64], q | k | v thirds with head h at columns h*64 of each -> out 16-bit
+ *                         [n][pitch][heads*64], rows < t only: softmax(q k^T * 64^-1/2 + causal mask) v, key j visible to query i
+ *                         iff j <= i.  d must be 64, 1 <= t <= 256.  fp32 logits and online softmax; masked weights are exactly 0;
+ *                         rows >= t of qkv are never read and rows >= t of out never written; a prompt's result does not depend
+ *                         on n.
+ *   adm_quick_gelu        16-bit [rows][inner] -> u * sigmoid(1.702 u) in fp32, same type (inner % 8 == 0)
+ *   adm_layernorm_f32out  LayerNorm (fp32 two-pass statistics) of rows < t of x 16-bit [n][pitch][c] -> fp32 [n][t][c]        */
+int adm_clip_embed(const int64_t* ids, const float* tok, const float* pos, adm_bf16* out, int n, int t, int pitch, int c, int vocab,
+                   int positions, void* stream);
+int adm_attention_causal(const adm_bf16* qkv, adm_bf16* out, int n, int t, int pitch, int heads, int d, void* stream);
+int adm_quick_gelu(const adm_bf16* u, adm_bf16* out, int64_t rows, int inner, void* stream);
+int adm_layernorm_f32out(const adm_bf16* x, const float* gamma, const float* beta, float* out, int n, int t, int pitch, int c,
+                         float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

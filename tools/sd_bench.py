@@ -6,7 +6,10 @@ SAMPLER=ddim|plms|dpm additionally times BASELINE config 4's candidate evaluatio
 classifier-free guidance 7.5, N_SAMPLES latents per batch (default 6) -> finished latents/s.
 --decode times the first stage instead: `decode_first_stage` of 6 latents of 64 x 64 through the v1 KL-f8 decoder per torso (ms per
 latent, model TFLOP/s from the plan's algorithmic FLOPs) and `adm_attention_1h512` alone at n = 6, T = 4096 next to a
-torch-composed 16-bit bmm-softmax-bmm, alternating, median of 5."""
+torch-composed 16-bit bmm-softmax-bmm, alternating, median of 5.
+--encode times the cond stage: `FrozenCLIPEmbedder.encode` of 6 and 12 prompts of 77 tokens through the ViT-L/14 text transformer
+per torso (ms per call, launches per call, model TFLOP/s from the plan's algorithmic FLOPs) next to the same transformer composed
+from torch's own 16-bit ops on the same weights, alternating, median of 5 windows of 20 calls."""
 import os
 import sys
 import time
@@ -110,6 +113,68 @@ def decode_bench():
         del vae, ld
 
 
+def _torch_clip(P, plan, dt):
+    """The text transformer composed from torch's 16-bit ops on the same parameters: ids -> fp32 [N, T, C]."""
+    import torch.nn.functional as F
+    W = {k[len("text_model."):]: v.to(dt) for k, v in P.items()}
+    c, heads, eps = plan.hidden_size, plan.num_attention_heads, plan.layer_norm_eps
+
+    def run(ids):
+        n, t = ids.shape
+        x = (P["text_model.embeddings.token_embedding.weight"][ids] + P["text_model.embeddings.position_embedding.weight"][:t]).to(dt)
+        mask = torch.full((t, t), float("-inf"), device=ids.device, dtype=dt).triu(1)
+        for l in range(plan.num_hidden_layers):
+            p = f"encoder.layers.{l}"
+            h = F.layer_norm(x, (c,), W[f"{p}.layer_norm1.weight"], W[f"{p}.layer_norm1.bias"], eps)
+            q, k, v = (F.linear(h, W[f"{p}.self_attn.{a}_proj.weight"], W[f"{p}.self_attn.{a}_proj.bias"])
+                       .view(n, t, heads, 64).transpose(1, 2) for a in "qkv")
+            w = torch.softmax(torch.matmul(q, k.transpose(-1, -2)) * 0.125 + mask, dim=-1)
+            a = torch.matmul(w, v).transpose(1, 2).reshape(n, t, c)
+            x = x + F.linear(a, W[f"{p}.self_attn.out_proj.weight"], W[f"{p}.self_attn.out_proj.bias"])
+            h = F.layer_norm(x, (c,), W[f"{p}.layer_norm2.weight"], W[f"{p}.layer_norm2.bias"], eps)
+            u = F.linear(h, W[f"{p}.mlp.fc1.weight"], W[f"{p}.mlp.fc1.bias"])
+            x = x + F.linear(u * torch.sigmoid(1.702 * u), W[f"{p}.mlp.fc2.weight"], W[f"{p}.mlp.fc2.bias"])
+        return F.layer_norm(x.float(), (c,), P["text_model.final_layer_norm.weight"], P["text_model.final_layer_norm.bias"], eps)
+    return run
+
+
+def encode_bench():
+    import statistics
+    from autodiffusion_amd.sd_clip import FrozenCLIPEmbedder
+    t, reps = 77, int(os.environ.get("REPS", "20"))
+    for torso in ("bf16", "fp16"):
+        emb = FrozenCLIPEmbedder(device="cpu").set_torso(torso).randomize_(2468).to(DEV)
+        plan = emb.transformer.plan
+        composed = _torch_clip(emb.transformer.state_dict(), plan, emb.compute_dtype)
+        for n in (6, 12):
+            ids = torch.randint(0, plan.vocab_size, (n, t), device=DEV, generator=torch.Generator(device=DEV).manual_seed(n))
+            for _ in range(3):
+                a, b = emb.encode(ids), composed(ids)
+            torch.cuda.synchronize()
+            assert a.shape == (n, t, plan.hidden_size) and torch.isfinite(a).all()
+            err = float((a - b).norm() / b.norm())
+            launches = []   # one entry per libadm_hip.so launch of a call
+            names = ("clip_embed", "layernorm", "conv", "attention_causal", "quick_gelu", "layernorm_f32out")
+            saved = {k: getattr(ops, k) for k in names}
+            for k, fn in saved.items():
+                setattr(ops, k, (lambda fn, k: lambda *a_, **kw: launches.append(k) or fn(*a_, **kw))(fn, k))
+            try:
+                emb.encode(ids)
+            finally:
+                for k, fn in saved.items():
+                    setattr(ops, k, fn)
+            ta, tb = [], []
+            for _ in range(5):
+                ta.append(_timed(lambda: emb.encode(ids), reps))
+                tb.append(_timed(lambda: composed(ids), reps))
+            ma, mb = statistics.median(ta), statistics.median(tb)
+            fl = n * plan.flops(t)
+            print(f"CLIP ViT-L/14 text encode [{torso}] {n} prompts x {t} tokens: HIP path {ma:.3f} ms / call ({len(launches)} launches, "
+                  f"{fl / ma / 1e9:.1f} model TFLOP/s; windows {min(ta):.3f} .. {max(ta):.3f}), torch-composed 16-bit {mb:.3f} ms / call "
+                  f"({fl / mb / 1e9:.1f} TFLOP/s; windows {min(tb):.3f} .. {max(tb):.3f}); rel diff of the two {err:.2g}")
+        del emb, composed
+
+
 def sampler_bench(m):
     from autodiffusion_amd.sd_sampler import DDIMSampler, DPMSolverSampler, LatentDiffusion, PLMSSampler
     kind = os.environ["SAMPLER"]
@@ -143,5 +208,7 @@ def sampler_bench(m):
 if __name__ == "__main__":
     if "--decode" in sys.argv[1:]:
         decode_bench()
+    elif "--encode" in sys.argv[1:]:
+        encode_bench()
     else:
         main()
