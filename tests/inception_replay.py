@@ -87,6 +87,20 @@ def _slice_of(out, c):
     return cs, off
 
 
+def conv2d_record(cin_cache: dict, x, w_packed, bias, kh, kw, stride, pad, relu, out) -> tuple:
+    """The record of one ops.conv2d call (also taken by launch_replay.Recorder for the UNets' stride-2 convs); cin_cache keeps
+    each weight's cin: the last input channel with a non-zero weight."""
+    n, h, w, _ = x.shape
+    cout, taps, cin_pad = w_packed.shape
+    key = (w_packed.data_ptr(), tuple(w_packed.shape))
+    if key not in cin_cache:
+        cin_cache[key] = int((w_packed != 0).any(0).any(0).nonzero().max()) + 1
+    os_, off = _slice_of(out, cout)
+    return _rec("conv2d", DTYPE_KIND[x.dtype], dict(
+        n=n, h=h, w=w, in_stride=x.stride(2), cin=cin_cache[key], cin_pad=cin_pad, cout=cout, kh=kh, kw=kw, stride=stride,
+        ph=pad[0], pw=pad[1], relu=bool(relu), has_bias=bias is not None, out_stride=os_, out_off=off))
+
+
 class Recorder:
     """Patches the four Inception entry points of ops.  records: the distinct launches; calls (keep=True): every call's
     (op, record, tensors) in order."""
@@ -98,15 +112,7 @@ class Recorder:
         o_conv, o_pool, o_resize, o_gap = ops.conv2d, ops.pool2d, ops.resize_bilinear, ops.global_avgpool_f32
 
         def conv2d(x, w_packed, bias, kh, kw, stride=1, pad=(0, 0), relu=True, out=None):
-            n, h, w, _ = x.shape
-            cout, taps, cin_pad = w_packed.shape
-            key = (w_packed.data_ptr(), tuple(w_packed.shape))
-            if key not in self._cin:   # the layer's cin: the last input channel with a non-zero weight
-                self._cin[key] = int((w_packed != 0).any(0).any(0).nonzero().max()) + 1
-            os_, off = _slice_of(out, cout)
-            rec = _rec("conv2d", DTYPE_KIND[x.dtype], dict(
-                n=n, h=h, w=w, in_stride=x.stride(2), cin=self._cin[key], cin_pad=cin_pad, cout=cout, kh=kh, kw=kw, stride=stride,
-                ph=pad[0], pw=pad[1], relu=bool(relu), has_bias=bias is not None, out_stride=os_, out_off=off))
+            rec = conv2d_record(self._cin, x, w_packed, bias, kh, kw, stride, pad, relu, out)
             res = o_conv(x, w_packed, bias, kh, kw, stride, pad, relu, out)
             self._add(rec, x=x, w_packed=w_packed, bias=bias, out=res)
             return res

@@ -1,7 +1,13 @@
 """Launch recorder, float64 restatements and per-element error bounds for tests/test_hip_launch_replay.py.
 
-Recording: every adm_conv call (on both loaded libraries) is captured as a copy of its adm_conv_args without the pointers, plus
-which optional pointers were set (those are flags); attention and GroupNorm calls are captured at the ops level by shape and flags.
+Recording, at two levels.  Census: every exported symbol of autodiffusion_amd/_lib.SIGNATURES whose last argument is the stream
+pointer is a launch (launch_symbols; the adm_stream_* calls manage streams and launch nothing); each is wrapped on both loaded
+libraries and notes (symbol, library) -- nothing more.  SYMBOL_COVERAGE maps every launch symbol to the record kind(s) that replay
+it here or to the test that holds it elsewhere, so "every launch" is checked, not assumed.  Records: every adm_conv call is
+captured as a copy of its adm_conv_args without the pointers, plus which optional pointers were set (those are flags); the
+attention, GroupNorm, token (LayerNorm, GEGLU, quick-GELU, embedding), resample, layout, VAE entry / exit and stride-2 conv2d calls
+are captured at the ops level by shape and flags.  The sampler-step kernels (adm_ddim_step, adm_ddpm_step, adm_sd_step,
+adm_dpm_step) are not launched by a model evaluation: they stay with their oracle goldens.
 
 Restatement: the op in float64 on the operands exactly as the kernel sees them -- 16-bit inputs, weights and residuals; the
 GroupNorm affine (+ SiLU) prologue in fp32, rounded once to the 16-bit type T.
@@ -19,6 +25,8 @@ Per-element bounds, u = 2^-8 (bf16) or 2^-11 (fp16), ulp_T(v) = 2u * 2^floor(log
              bound below is the tight check on those launches.
   attention  |got - ref| <= ulp_T(|ref|) + C_ATTN u max_j |v_j| + fp32 terms (logits, PV accumulation; fp16: underflow of P)
              C_ATTN = 2: P is rounded to T before the PV product (numerator) and the row sum (denominator) -- u each.
+  causal     adm_attention_causal: the same bound with the logits above the diagonal at -inf; the key count and max_j |v_j| are
+             taken over the keys j <= query.  Rows >= t of `out` and a guard behind it keep their sentinel.
   attn bwd   dq / dk: ulp_T(|ref|) + 4 u scale Σ_j P_j (|dP_j| + |δ|) |k_j| (resp. |q_i|); dv: ulp_T(|ref|) + 2 u Σ_i P_i |do_i|
              -- P and dS = P (dP - δ) are rounded to T before their products (u each, and dS inherits P's), fp32 terms far below.
   lse        log2-domain log-sum-exp of the scaled logits: |got - ref| <= u / ln 2 + 2^-18 (1 + |ref| + max_j |s_j c|): the row sum
@@ -27,9 +35,33 @@ Per-element bounds, u = 2^-8 (bf16) or 2^-11 (fp16), ulp_T(v) = 2u * 2^floor(log
              E1 / E0 the fp32 slab sums' worst case (hw 2^-24 Σ|terms|) carried through k1 / k0.
   gn_affine  y = a x + b against float64 GroupNorm (+ FiLM / + add) of the stored tensor: u / 8 (1 + |y|), well below the
              rounding to T that the consuming conv's prologue applies next.
+  "half ulp" below is one round-to-nearest of an fp32 value v to T: |got - ref| <= ulp_T(|ref|) / 2 + |v - ref|; where v and ref
+             lie on the two sides of a binade edge the result is the edge itself, within the lower binade's half ulp of ref.
+  layernorm  y = ŷ γ + β, ŷ = (x - mean) rstd, two-pass as the kernel: ulp_T(|ref|) / 2 + k rstd |γ| mean|x| + (k + 2^-21) |ŷ γ|
+             + 2^-23 |ref|, k = (8 SEGS + 8) 2^-24, SEGS = ceil(c / 512): a lane adds its 8 SEGS values and six butterfly steps
+             follow, for the mean (times the fp32 1 / c: k mean|x| on the mean, carried by rstd |γ|) and again for the variance
+             (relative k on rstd, with rsqrt, the subtraction and the two multiplies inside 2^-21); 2^-23 |ref| is the final
+             multiply-add.  Frobenius <= fro_bound(1, u).  layernorm_f32out: the same without the ulp_T / 2 term, on the rows < t
+             of every prompt; the rows >= t are fed NaN and must not be read.
+  geglu      v gelu_erf(g) on T values: ulp_T(|ref|) / 2 + SILU_REL (|ref| + |v|), the last term of the fused GEGLU bound.
+  quick_gelu a sigmoid(1.702 a): ulp_T(|ref|) / 2 + SILU_REL (1 + |1.702 a|) |ref|: the fp32 product in front of exp2 has a
+             relative error 2^-24 of an argument that grows with |a|, and d log sigmoid(z) / dz <= 1.
+  clip_embed round_T(tok[ids] + pos[:t]) with the add in fp32, pad rows zero: bitwise.
+  resample   'up' / 'stride2' / 'zero2' without the affine are copies and zeros: bitwise.  'down' is the mean of four taps:
+             ulp_T(|ref|) / 2 + 4 x 2^-24 mean|x| (three fp32 adds, an exact 1 / 4).  With the affine the taps are
+             s = silu(a x + b): the mean (the tap) of SILU_REL |s| + 2^-23 (|a x| + |b|) is added -- approximate exp / rcp, and
+             the fp32 multiply-add in front through silu' <= 1.1.
+  nchw_to_nhwc_pad   round_T(x) transposed, pad channels zero: bitwise.
+  vae_latent_in      Σ_j w_cj (inv z_j) + b_c: ulp_T(|ref|) / 2 + (e + 3) 2^-24 (Σ_j |w_cj inv z_j| + |b_c|): the product inv z_j, e
+             multiply-adds and the bias add.  Pad channels exactly zero.
+  vae_image_out      clamp((x + 1) / 2, 0, 1) in fp32 and trunc(255 unit): bitwise.
+  conv2d     the UNets' stride-2 convs on adm_conv2d: inception_replay's restatement, bound and comparison, imported.
   Frobenius  ||got - ref|| / ||ref|| <= FRO_U u sqrt(r), FRO_U = 0.6: one rounding to T has an RMS relative error of at most
              u / sqrt(3) ~ 0.58 u; r roundings in sequence (A, then A + residual; dz, then dz SiLU'; P, then the output) add in
              quadrature.
+
+Elementwise and row-wise records are compared on every element; above 2^25 elements, on every element of the first, the last
+and one seeded image (a condition, not a tolerance: these kernels index by flat element, so no tile position goes unvisited).
 """
 from __future__ import annotations
 
@@ -39,6 +71,7 @@ import torch
 
 U = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
 KIND_DTYPE = {"bf16": torch.bfloat16, "f16": torch.float16}
+KIND_OF_DTYPE = {v: k for k, v in KIND_DTYPE.items()}
 PRO_ULPS = 8
 C_ATTN = 2.0
 FRO_U = 0.6
@@ -74,14 +107,120 @@ def record_dict(rec: tuple) -> dict:
     return dict(rec[2:])
 
 
+def launch_symbols() -> list:
+    """The exported symbols that launch: the last argument is the stream pointer.  The adm_stream_* calls (create / resize /
+    destroy / probe a stream) end in a pointer too; they are stream management, not launches."""
+    from autodiffusion_amd import _lib
+    return [name for name, (_, args) in _lib.SIGNATURES.items()
+            if args and args[-1] is _lib._P and not name.startswith("adm_stream_")]
+
+
+def _e(test: str) -> tuple:
+    return ("elsewhere", test)
+
+
+# launch symbol -> the record kinds that replay it here, or ("elsewhere", "tests/<file>.py::<test>") for what stays where it is:
+# the fp32 vector kernels of the classifier head, the fp32 embedding / linear kernels, the weight packers (every conv replay
+# compares against round_t(w), so a mis-packed weight fails there too), the sampler steps, and the evaluation-side kernels of
+# the Inception replay and the FID / precision-recall tests.
+SYMBOL_COVERAGE = {
+    "adm_conv": ("conv",),
+    "adm_attention_lse": ("attention",),
+    "adm_attention_1h512": ("attention",),
+    "adm_attention_cross": ("attention_cross",),
+    "adm_attention_bwd": ("attention_bwd",),
+    "adm_gn_partial": ("gn_affine",),
+    "adm_gn_finalize": ("gn_affine",),
+    "adm_gn_finalize2": ("gn_affine",),
+    "adm_gn_finalize_add": ("gn_affine",),
+    "adm_gn_bwd_partial": ("gn_bwd",),
+    "adm_gn_bwd_finalize": ("gn_bwd",),
+    "adm_gn_bwd_apply": ("gn_bwd",),
+    "adm_layernorm": ("layernorm",),
+    "adm_layernorm_f32out": ("layernorm_f32out",),
+    "adm_geglu": ("geglu",),
+    "adm_quick_gelu": ("quick_gelu",),
+    "adm_attention_causal": ("attention_causal",),
+    "adm_clip_embed": ("clip_embed",),
+    "adm_resample": ("resample",),
+    "adm_nchw_to_nhwc_pad": ("nchw_to_nhwc_pad",),
+    "adm_vae_latent_in": ("vae_latent_in",),
+    "adm_vae_image_out": ("vae_image_out",),
+    "adm_conv2d": ("conv2d",),
+    # the classifier head's fp32 vector kernels and its attention pool
+    "adm_vec_act": _e("tests/test_hip_classifier.py::test_pool_head_kernels_match_torch"),
+    "adm_vec_gn": _e("tests/test_hip_classifier.py::test_pool_head_kernels_match_torch"),
+    "adm_vec_gn_bwd": _e("tests/test_hip_classifier.py::test_pool_head_kernels_match_torch"),
+    "adm_channel_mean": _e("tests/test_hip_classifier.py::test_pool_head_kernels_match_torch"),
+    "adm_bcast_add": _e("tests/test_hip_classifier.py::test_pool_head_kernels_match_torch"),
+    "adm_pool_prep": _e("tests/test_hip_classifier.py::test_classifier_logits_and_guidance_gradient_golden"),
+    "adm_pool_attn_fwd": _e("tests/test_hip_classifier.py::test_classifier_logits_and_guidance_gradient_golden"),
+    "adm_pool_attn_bwd": _e("tests/test_hip_classifier.py::test_classifier_logits_and_guidance_gradient_golden"),
+    "adm_pool_prep_bwd": _e("tests/test_hip_classifier.py::test_classifier_logits_and_guidance_gradient_golden"),
+    "adm_grad_add": _e("tests/test_hip_classifier.py::test_classifier_logits_and_guidance_gradient_golden"),
+    "adm_logsoftmax_grad": _e("tests/test_hip_classifier.py::test_logsoftmax_grad"),
+    # fp32 embedding path and the direct stem
+    "adm_linear_f32": _e("tests/test_hip_kernels.py::test_linear_f32"),
+    "adm_timestep_embedding": _e("tests/test_hip_kernels.py::test_timestep_embedding"),
+    "adm_stem_conv3x3": _e("tests/test_hip_kernels.py::test_stem_conv"),
+    # weight packers
+    "adm_pack_conv_weight": _e("tests/test_hip_kernels.py::test_conv_fused"),
+    "adm_pack_conv_weight32": _e("tests/test_hip_kernels.py::test_conv_fused"),
+    "adm_pack_conv_weight_bwd": _e("tests/test_hip_classifier.py::test_conv_backward_data_weights"),
+    "adm_pack_conv2d_weight": _e("tests/test_hip_inception_replay.py::test_conv_launches_match_float64"),
+    # sampler steps: not launched by a model evaluation
+    "adm_ddim_step": _e("tests/test_hip_kernels.py::test_sampler_steps_match_oracle"),
+    "adm_ddpm_step": _e("tests/test_hip_kernels.py::test_sampler_steps_match_oracle"),
+    "adm_pack_u8_nhwc": _e("tests/test_hip_kernels.py::test_pack_u8_bit_exact_and_odd_sizes"),
+    "adm_sd_step": _e("tests/test_hip_sd.py::test_ddim_step_with_noise_matches_the_oracle_formula"),
+    "adm_dpm_step": _e("tests/test_hip_sd.py::test_dpm_solver_sampler_matches_reference_goldens"),
+    # evaluation side
+    "adm_pool2d": _e("tests/test_hip_inception_replay.py::test_pool_launches_match_float64"),
+    "adm_global_avgpool_f32": _e("tests/test_hip_inception_replay.py::test_global_avgpool_launches_match_float64"),
+    "adm_resize_bilinear": _e("tests/test_hip_inception_replay.py::test_resize_launches_match_float64"),
+    "adm_fid_accumulate": _e("tests/test_fid.py::test_gram_kernel_ragged_shapes_and_symmetry"),
+    "adm_knn_smallest": _e("tests/test_hip_evaluator.py::test_radii_match_the_restatement"),
+    "adm_knn_cover": _e("tests/test_hip_evaluator.py::test_precision_recall_exactly_the_restatement"),
+    # no caller in the package (ops.attention always asks adm_attention_lse): only its export is held
+    "adm_attention": _e("tests/test_cabi.py::test_library_loads_and_exports_every_symbol"),
+}
+
+
+def coverage_gaps(census, records, replayed) -> list:
+    """What the coverage guard reports: census symbols missing from SYMBOL_COVERAGE, and symbols mapped to record kinds of which
+    none was recorded (on the library that made the call) or which the replay does not take."""
+    have = {(r[0], r[1]) for r in records}
+    gaps = []
+    for sym, kind in sorted(census):
+        cov = SYMBOL_COVERAGE.get(sym)
+        if cov is None:
+            gaps.append(f"{sym} ({kind}) is launched but has no entry in SYMBOL_COVERAGE")
+        elif cov[0] != "elsewhere":
+            if not any((k, kind) in have for k in cov):
+                gaps.append(f"{sym} ({kind}) was launched but no {' / '.join(cov)} record was taken")
+            if not set(cov) <= set(replayed):
+                gaps.append(f"{sym}: record kinds {sorted(set(cov) - set(replayed))} are not replayed")
+    return gaps
+
+
+def kind_of(t) -> str:
+    return "f16" if t.dtype == torch.float16 else "bf16"
+
+
+RESAMPLE_MODES = {"down": 1, "up": 2, "stride2": 3, "zero2": 4}
+
+
 class Recorder:
-    """Patches (through pytest's monkeypatch) adm_conv on both libraries and the attention / GroupNorm wrappers of ops."""
+    """Patches (through pytest's monkeypatch) every launch symbol on both libraries -- the census, and adm_conv's record -- and
+    the attention / GroupNorm / token / resample / layout / VAE / conv2d wrappers of ops (the other records)."""
 
     def __init__(self, monkeypatch):
         from autodiffusion_amd import _lib, ops
         self.records = set()
         self.counts = {}
         self.orig = {}
+        self.census = set()
+        self._cin = {}
         for kind in ("bf16", "f16"):
             lib = _lib.load(kind)
             fn = lib.adm_conv
@@ -89,12 +228,18 @@ class Recorder:
 
             def wrapped(args, stream, _fn=fn, _kind=kind):
                 a = args._obj if hasattr(args, "_obj") else args.contents
+                self.census.add(("adm_conv", _kind))
                 self._add(conv_record(_kind, _lib.ConvArgs.from_buffer_copy(a)))
                 return _fn(args, stream)
             monkeypatch.setattr(lib, "adm_conv", wrapped)
+            for name in launch_symbols():
+                if name == "adm_conv":
+                    continue
 
-        def kind_of(t):
-            return "f16" if t.dtype == torch.float16 else "bf16"
+                def noted(*args, _fn=getattr(lib, name), _key=(name, kind)):
+                    self.census.add(_key)
+                    return _fn(*args)
+                monkeypatch.setattr(lib, name, noted)
 
         o_att, o_cross, o_bwd, o_gn, o_gnb = ops.attention, ops.attention_cross, ops.attention_bwd, ops.gn_affine, ops.gn_bwd
 
@@ -125,8 +270,69 @@ class Recorder:
                        partial is not None, norm_add is not None))
             return o_gnb(x, dy, aff, stats, silu, dy_half, add, add_half, partial, norm_add)
 
+        o_ln, o_lnf, o_gg, o_qg, o_cau, o_emb = (ops.layernorm, ops.layernorm_f32out, ops.geglu, ops.quick_gelu, ops.attention_causal,
+                                                 ops.clip_embed)
+        o_res, o_pad, o_lat, o_img, o_c2d = ops.resample, ops.nchw_to_nhwc_pad, ops.vae_latent_in, ops.vae_image_out, ops.conv2d
+
+        def layernorm(x, gamma, beta, eps=1e-5):
+            c = x.shape[-1]
+            self._add(("layernorm", kind_of(x), x.numel() // c, c, float(eps)))
+            return o_ln(x, gamma, beta, eps)
+
+        def layernorm_f32out(x, t, gamma, beta, eps=1e-5):
+            n, pitch, c = x.shape
+            self._add(("layernorm_f32out", kind_of(x), n, int(t), pitch, c, float(eps)))
+            return o_lnf(x, t, gamma, beta, eps)
+
+        def geglu(u):
+            inner = u.shape[-1] // 2
+            self._add(("geglu", kind_of(u), u.numel() // (2 * inner), inner))
+            return o_gg(u)
+
+        def quick_gelu(u):
+            inner = u.shape[-1]
+            self._add(("quick_gelu", kind_of(u), u.numel() // inner, inner))
+            return o_qg(u)
+
+        def attention_causal(qkv, heads, t=None, out=None):
+            n, pitch, _ = qkv.shape
+            self._add(("attention_causal", kind_of(qkv), n, pitch if t is None else int(t), pitch, heads))
+            return o_cau(qkv, heads, t, out)
+
+        def clip_embed(ids, tok, pos, pitch, dtype=torch.bfloat16):
+            self._add(("clip_embed", KIND_OF_DTYPE[dtype], ids.shape[0], ids.shape[1], int(pitch), tok.shape[1], tok.shape[0], pos.shape[0]))
+            return o_emb(ids, tok, pos, pitch, dtype)
+
+        def resample(x, mode, aff=None):
+            n, h, w, c = x.shape
+            self._add(("resample", kind_of(x), n, h, w, c, RESAMPLE_MODES[mode], aff is not None))
+            return o_res(x, mode, aff)
+
+        def nchw_to_nhwc_pad(x_nchw, cpad=32, dtype=torch.bfloat16):
+            n, c, h, w = x_nchw.shape
+            self._add(("nchw_to_nhwc_pad", KIND_OF_DTYPE[dtype], n, c, h, w, int(cpad)))
+            return o_pad(x_nchw, cpad, dtype)
+
+        def vae_latent_in(z, w, b, inv_scale=1.0, dtype=torch.bfloat16):
+            n, e, h, wd = z.shape
+            self._add(("vae_latent_in", KIND_OF_DTYPE[dtype], n, w.shape[0], e, h, wd))
+            return o_lat(z, w, b, inv_scale, dtype)
+
+        def vae_image_out(x, want_unit=True, want_u8=False, unit_out=None):
+            n, _, h, w = x.shape   # one fp32 kernel, launched from the bf16 library whatever the torso
+            self._add(("vae_image_out", "bf16", n, h, w, bool(want_unit) or unit_out is not None, bool(want_u8)))
+            return o_img(x, want_unit, want_u8, unit_out)
+
+        def conv2d(x, w_packed, bias, kh, kw, stride=1, pad=(0, 0), relu=True, out=None):
+            import inception_replay as ir
+            self._add(ir.conv2d_record(self._cin, x, w_packed, bias, kh, kw, stride, pad, relu, out))
+            return o_c2d(x, w_packed, bias, kh, kw, stride, pad, relu, out)
+
         for name, fn in (("attention", attention), ("attention_cross", attention_cross), ("attention_bwd", attention_bwd),
-                         ("gn_affine", gn_affine), ("gn_bwd", gn_bwd)):
+                         ("gn_affine", gn_affine), ("gn_bwd", gn_bwd), ("layernorm", layernorm), ("layernorm_f32out", layernorm_f32out),
+                         ("geglu", geglu), ("quick_gelu", quick_gelu), ("attention_causal", attention_causal), ("clip_embed", clip_embed),
+                         ("resample", resample), ("nchw_to_nhwc_pad", nchw_to_nhwc_pad), ("vae_latent_in", vae_latent_in),
+                         ("vae_image_out", vae_image_out), ("conv2d", conv2d)):
             monkeypatch.setattr(ops, name, fn)
 
     def _add(self, rec):
@@ -154,7 +360,10 @@ def families(rec: tuple) -> set:
             out.add("geglu")
         if d["out_mode"] == 1:
             out.add("out_mode 1 + out_scale" if d["out_scale"] != 0.0 else "out_mode 1")
-        out.add("8x8 map" if d["h"] * d["w"] <= 64 else ">= 16x16 map")
+        if d["h"] != d["w"]:
+            out.add("non-square map")   # the CLIP text transformer's 8x16 token map
+        else:
+            out.add("8x8 map" if d["h"] * d["w"] <= 64 else ">= 16x16 map")
     elif op == "attention":
         _, _, n, t, c3, heads, new_order, lse = rec
         out.add(f"attention d {c3 // 3 // heads}")
@@ -171,7 +380,25 @@ REQUIRED_FAMILIES = (["variant 3", "variant 5", "variant 6", "variant 10", "kspl
                       "prologue 3", "geglu", "out_mode 1", "out_mode 1 + out_scale", "8x8 map", ">= 16x16 map"]
                      + [f"attention d {d}" for d in (64, 128, 192, 256)]
                      + [f"attention_cross d {d} ({k})" for d in (48, 80, 160) for k in ("self", "cross")]
-                     + ["attention_bwd", "gn_bwd"])
+                     + ["attention_bwd", "gn_bwd"]
+                     + ["attention d 512", "non-square map"]
+                     + ["layernorm", "layernorm_f32out", "geglu", "quick_gelu", "attention_causal", "clip_embed", "resample",
+                        "nchw_to_nhwc_pad", "vae_latent_in", "vae_image_out", "conv2d"])
+# families one library alone reaches: the 2^10 gradient scale is the fp16 classifier's; adm_vae_image_out is an fp32 kernel that
+# ops launches from the bf16 library whatever the torso
+ONE_LIBRARY_FAMILIES = {"out_mode 1 + out_scale": "f16", "vae_image_out": "bf16"}
+NEW_KINDS = ("layernorm", "layernorm_f32out", "geglu", "quick_gelu", "attention_causal", "clip_embed", "resample",
+             "nchw_to_nhwc_pad", "vae_latent_in", "vae_image_out", "conv2d")
+REPLAYED = {"conv", "attention", "attention_cross", "attention_bwd", "gn_bwd", "gn_affine"} | set(NEW_KINDS)
+
+
+def missing_families(records) -> list:
+    """The (library, family) pairs of REQUIRED_FAMILIES that no record belongs to."""
+    fams = set()
+    for r in records:
+        fams |= families(r)
+    return [(k, f) for k in ("bf16", "f16") for f in REQUIRED_FAMILIES
+            if (k, f) not in fams and ONE_LIBRARY_FAMILIES.get(f, k) == k]
 
 
 # ------------------------------------------------------------------ arithmetic helpers
@@ -317,18 +544,29 @@ def conv_restate(d: dict, dtype, t: dict, img, oy, ox):
 
 
 # ------------------------------------------------------------------ attention restatement
-def attention_restate(q, k, v, scale: float, dtype):
-    """float64 softmax(q k^T scale) v for q [B, tq, d], k / v [B, tk, d] holding T values -> (ref, bound) [B, tq, d]."""
+def attention_restate(q, k, v, scale: float, dtype, causal: bool = False):
+    """float64 softmax(q k^T scale) v for q [B, tq, d], k / v [B, tk, d] holding T values -> (ref, bound) [B, tq, d].
+    causal (tq == tk): the logits above the diagonal are -inf; the bound's key count and max_j |v_j| run over the keys j <= query."""
     q, k, v = q.double(), k.double(), v.double()
     s = (q @ k.transpose(1, 2)) * scale
+    tk, d = k.shape[1], q.shape[2]
+    ds = (d + 2) * 2.0 ** -24 * (q.abs() @ k.abs().transpose(1, 2)) * scale + 2.0 ** -22 * s.abs()
+    if causal:
+        if q.shape[1] != tk:
+            raise NotImplementedError("causal attention: one query per key")
+        above = torch.ones(tk, tk, dtype=torch.bool, device=q.device).triu(1)
+        s = s.masked_fill(above, float("-inf"))
+        ds = ds.masked_fill(above, 0.0)
+        vmax = torch.cummax(v.abs(), 1).values                        # [B, tq, d]: max over the keys <= query
+        keys = torch.arange(1, tk + 1, dtype=torch.float64, device=q.device)[None, :, None]
+    else:
+        vmax = v.abs().amax(1, keepdim=True)                             # [B, 1, d]
+        keys = float(tk)
     p = torch.softmax(s, -1)
     ref = p @ v
-    tk, d = k.shape[1], q.shape[2]
-    vmax = v.abs().amax(1, keepdim=True)                             # [B, 1, d]
-    ds = (d + 2) * 2.0 ** -24 * (q.abs() @ k.abs().transpose(1, 2)) * scale + 2.0 ** -22 * s.abs()
-    bound = ulp_t(ref, dtype) + (C_ATTN * U[dtype] + 2.0 * ds.amax(-1, keepdim=True) + (tk + 2) * 2.0 ** -24) * vmax
+    bound = ulp_t(ref, dtype) + (C_ATTN * U[dtype] + 2.0 * ds.amax(-1, keepdim=True) + (keys + 2) * 2.0 ** -24) * vmax
     if dtype == torch.float16:
-        bound = bound + tk * 2.0 ** -25 * vmax                        # P below fp16's normal range: absolute spacing 2^-24
+        bound = bound + keys * 2.0 ** -25 * vmax                      # P below fp16's normal range: absolute spacing 2^-24
     return ref, bound
 
 
@@ -423,3 +661,131 @@ def gn_affine_restate(x, gamma, beta, eps: float, film=None, add=None):
     if film is not None:
         y = y * (1 + film[:, None, None, :c].double()) + film[:, None, None, c:2 * c].double()
     return y, mean, rstd
+
+
+# ------------------------------------------------------------------ token, resample, layout and VAE entry / exit restatements
+def half_ulp(ref, dtype):
+    return 0.5 * ulp_t(ref, dtype)
+
+
+def layernorm_restate(x, gamma, beta, eps: float, dtype, f32out: bool = False):
+    """float64 two-pass LayerNorm over the last dimension of x [rows, c] holding T values -> (ref, bound); f32out: the kernel
+    stores fp32, so no rounding to T."""
+    x, g, b = x.double(), gamma.double(), beta.double()
+    c = x.shape[-1]
+    mean = x.mean(-1, keepdim=True)
+    xc = x - mean
+    rstd = 1.0 / torch.sqrt((xc * xc).mean(-1, keepdim=True) + eps)
+    yg = xc * rstd * g
+    ref = yg + b
+    k = (8 * ((c + 511) // 512) + 8) * 2.0 ** -24
+    bound = k * rstd * g.abs() * x.abs().mean(-1, keepdim=True) + (k + 2.0 ** -21) * yg.abs() + 2.0 ** -23 * ref.abs()
+    return ref, (bound if f32out else bound + half_ulp(ref, dtype))
+
+
+def gelu_erf(g):
+    return 0.5 * g * (1 + torch.erf(g / math.sqrt(2.0)))
+
+
+def geglu_restate(u, dtype):
+    """u [rows, 2 inner] holding T values (values, then gates) -> (v gelu_erf(g), bound) [rows, inner]."""
+    inner = u.shape[-1] // 2
+    v, g = u[..., :inner].double(), u[..., inner:].double()
+    ref = v * gelu_erf(g)
+    return ref, half_ulp(ref, dtype) + SILU_REL * (ref.abs() + v.abs())
+
+
+def quick_gelu_restate(a, dtype):
+    a = a.double()
+    ref = a * torch.sigmoid(1.702 * a)
+    return ref, half_ulp(ref, dtype) + SILU_REL * (1 + (1.702 * a).abs()) * ref.abs()
+
+
+def clip_embed_restate(ids, tok, pos, pitch: int, dtype):
+    """round_T(tok[ids] + pos[:t]) with the add in fp32, rows t .. pitch zero -> [n, pitch, c] of T (compared bitwise)."""
+    n, t = ids.shape
+    out = torch.zeros((n, pitch, tok.shape[1]), dtype=dtype, device=tok.device)
+    out[:, :t] = (tok.float()[ids] + pos.float()[:t]).to(dtype)
+    return out
+
+
+def resample_restate(x, mode: int, aff, dtype):
+    """x [n, h, w, c] holding T values; mode 1 AvgPool2d(2), 2 nearest x2, 3 every second pixel, 4 zero-insert x2; aff = (a, b)
+    fp32 [n, c]: silu(a x + b) first -> (ref, bound); the bound is None where the result is a copy (compared bitwise)."""
+    n, h, w, c = x.shape
+    s = x.double()
+    e = None
+    if aff is not None:
+        a, b = aff[0].double()[:, None, None, :], aff[1].double()[:, None, None, :]
+        z = a * s + b
+        e = 2.0 ** -23 * ((a * s).abs() + b.abs())
+        s = z * torch.sigmoid(z)
+        e = e + SILU_REL * s.abs()
+    if mode == 1:
+        def pool(t):
+            return t.reshape(n, h // 2, 2, w // 2, 2, c).mean((2, 4))
+        ref = pool(s)
+        bound = half_ulp(ref, dtype) + 4 * 2.0 ** -24 * pool(s.abs())
+        return ref, (bound if e is None else bound + pool(e))
+    if mode == 2:
+        ref = s.repeat_interleave(2, 1).repeat_interleave(2, 2)
+        e = None if e is None else e.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    elif mode == 3:
+        ref = s[:, ::2, ::2]
+        e = None if e is None else e[:, ::2, ::2]
+    elif mode == 4:
+        if aff is not None:
+            raise NotImplementedError("zero-insert takes no affine")
+        ref = torch.zeros((n, 2 * h, 2 * w, c), dtype=s.dtype, device=s.device)
+        ref[:, ::2, ::2] = s
+    else:
+        raise NotImplementedError(f"resample mode {mode}")
+    return ref, (None if e is None else half_ulp(ref, dtype) + e)
+
+
+def nchw_to_nhwc_pad_restate(x, cpad: int, dtype):
+    n, c, h, w = x.shape
+    out = torch.zeros((n, h, w, cpad), dtype=dtype, device=x.device)
+    out[..., :c] = x.float().permute(0, 2, 3, 1).to(dtype)
+    return out
+
+
+def vae_latent_in_restate(z, w, b, inv_scale: float, dtype):
+    """z fp32 [n, e, h, w], w [zc, e], b [zc], inv_scale as the fp32 value the kernel is passed -> (ref, bound) [n, h, w, zc]."""
+    e = z.shape[1]
+    zs = z.double().permute(0, 2, 3, 1) * float(inv_scale)                  # [n, h, w, e]
+    wd = w.double().reshape(w.shape[0], e)
+    ref = zs @ wd.T + b.double()
+    mag = zs.abs() @ wd.abs().T + b.double().abs()
+    return ref, half_ulp(ref, dtype) + (e + 3) * 2.0 ** -24 * mag
+
+
+def vae_image_out_restate(x):
+    """x fp32 NCHW -> (unit fp32 NCHW = clamp((x + 1) / 2, 0, 1) in fp32, uint8 NHWC = trunc(255 unit)); compared bitwise."""
+    unit = torch.clamp((x.float() + 1.0) / 2.0, min=0.0, max=1.0)
+    return unit, (255.0 * unit).permute(0, 2, 3, 1).to(torch.uint8)
+
+
+IMAGE_OUT_SPECIALS = (1.0, -1.0, 0.0, -0.0, 3.0e38, -3.0e38, 1e-45, -1e-45, 0.9999999, -0.9999999, 1.0000001, 0.003921569)
+QUICK_GELU_SPECIALS = (-12.0, 12.0, 0.0, -0.0, 1e-3, -1e-3, 1.0, -1.0)
+BIG = 1 << 25
+
+
+def compared_images(n: int, numel: int, seed: int) -> list:
+    """The images (first index) of an elementwise record to compare: all of them up to 2^25 elements, else the first, the last
+    and one seeded image."""
+    if numel <= BIG:
+        return list(range(n))
+    g = torch.Generator().manual_seed(seed)
+    return sorted({0, n - 1, int(torch.randint(0, n, (1,), generator=g))})
+
+
+def worst_ratio(got, ref, bound):
+    """(worst err / bound, sum err^2, sum ref^2, report of the worst element) of one compared block."""
+    err = (got.double() - ref).abs()
+    r = err / bound
+    r = torch.where(torch.isfinite(got.double()) & ~torch.isnan(r), r, torch.full_like(r, float("inf")))
+    j = int(r.argmax())
+    idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(j), r.shape))
+    rep = f"index {idx}: got {got.double().flatten()[j].item():.8g} ref {ref.flatten()[j].item():.8g} bound {bound.expand_as(r).flatten()[j].item():.4g}"
+    return r.flatten()[j].item(), (err ** 2).sum().item(), (ref ** 2).sum().item(), rep

@@ -1,13 +1,16 @@
 """Every (kernel, shape, flags) launch the shipped models make, replayed against float64 in both torsos.
 
-The models (built as tests/test_hip_fullsize.py builds them; the weights' values do not matter, only the launch list does) run
-eagerly at the batches bench.py uses and at batch 1-2, in the bf16 and the fp16 torso, under tests/launch_replay.Recorder.  Each
-distinct record is then launched again through the same C entry point with fresh seeded operands and compared element by element
-with the float64 restatement of tests/launch_replay.py, within the per-element bounds derived there (and tested on the host by
-tests/test_launch_replay_host.py).  Large maps are compared at the corners of every 16x16 (8x8) output tile of every image plus
-seeded random pixels, all channels.  A coverage guard fails if a family of launches the models are known to reach is missing.
+The models (built as tests/test_hip_fullsize.py, tests/test_hip_sd_vae.py and tests/test_hip_clip.py build them; the weights'
+values do not matter, only the launch list does) run eagerly at the batches bench.py uses and at batch 1-2, in the bf16 and the
+fp16 torso, under tests/launch_replay.Recorder: ADM-64 / 128 / 256, the classifiers, the SD latent UNet, the KL-f8 VAE decoder
+(with the image exit that follows it) and the CLIP text encoder.  Each distinct record is then launched again through the same
+entry point with fresh seeded operands and compared element by element with the float64 restatement of tests/launch_replay.py,
+within the per-element bounds derived there (and tested on the host by tests/test_launch_replay_host.py).  Large conv maps are
+compared at the corners of every 16x16 (8x8) output tile of every image plus seeded random pixels, all channels.  A coverage
+guard fails if a family of launches the models are known to reach is missing, if a launch symbol the models called has no entry
+in launch_replay.SYMBOL_COVERAGE, or if a symbol mapped to a record kind left no record of that kind.
 
-Also here: GroupNorm statistics at a large |mean| / std (fused conv statistics, the `add` form, adm_gn_partial).
+Also here: GroupNorm statistics and LayerNorm at a large |mean| / std, and the causal attention at the tile edges of its schedule.
 """
 import ctypes as C
 import time
@@ -89,6 +92,46 @@ def _run_models(torso):
                   torch.randn(n, 77, 768, generator=g).to(DEV))
         del m
     torch.cuda.empty_cache()
+    _run_vae_and_clip(torso)
+
+
+_FILLS = {}   # host fills of the VAE / CLIP state dicts, shared by the two torsos and dropped by the fixture
+TINY_CLIP_256 = dict(vocab_size=512, hidden_size=128, intermediate_size=256, num_hidden_layers=1, num_attention_heads=2,
+                     max_position_embeddings=256)
+
+
+def _fill(key, prefix, shapes):
+    from oracle.fill import fill_array
+    if key not in _FILLS:
+        _FILLS[key] = {k: torch.from_numpy(fill_array(prefix + k, tuple(shape))) for k, shape in shapes.items()}
+    return _FILLS[key]
+
+
+def _run_vae_and_clip(torso):
+    """The KL-f8 decoder at the shipped 64x64 latent map (batch 1: the 512x512 launches) and at 8x8 (batch 2), each followed by
+    the image exit as sd_evaluate calls it; the CLIP text encoder at 77 tokens (8x16 map, 51 dead rows), 20 tokens (8x8 map) and
+    a one-layer 256-position config at 200 tokens (16x16 map, the causal attention's LDS above 64 KB)."""
+    from autodiffusion_amd import ops as hip_ops
+    from autodiffusion_amd.sd_clip import CLIP_VIT_L14_TEXT, CLIPTextPlan, FrozenCLIPEmbedder
+    from autodiffusion_amd.sd_vae import SD_V1_VAE, AutoencoderKL
+    g = torch.Generator().manual_seed(7)
+    vae = AutoencoderKL(**SD_V1_VAE)
+    vae.load_state_dict(_fill("vae", "first_stage_model.", {k: v.shape for k, v in vae.state_dict().items()}))
+    vae.set_torso(torso).to(DEV)
+    for shape in ((1, 4, 64, 64), (2, 4, 8, 8)):
+        x = vae.decode(torch.randn(shape, generator=g).to(DEV))
+        hip_ops.vae_image_out(x, want_unit=True, want_u8=True)
+    del vae, x
+    torch.cuda.empty_cache()
+    for name, cfg, prompts in (("vitl14", CLIP_VIT_L14_TEXT, ((3, 77), (1, 20))), ("tiny256", TINY_CLIP_256, ((2, 200),))):
+        emb = FrozenCLIPEmbedder(device="cpu", max_length=cfg["max_position_embeddings"], config=cfg)
+        fill = _fill(name, "cond_stage_model.transformer.", CLIPTextPlan(**cfg).param_shapes())
+        emb.load_state_dict({"transformer." + k: v for k, v in fill.items()})
+        emb.set_torso(torso).to(DEV)
+        for n, t in prompts:
+            emb(torch.randint(0, cfg["vocab_size"], (n, t), generator=g).to(DEV))
+        del emb
+        torch.cuda.empty_cache()
 
 
 @pytest.fixture(scope="module")
@@ -98,6 +141,7 @@ def recorded(ops):
         rec = lr.Recorder(mp)
         for torso in ("bf16", "fp16"):
             _run_models(torso)
+    _FILLS.clear()
     torch.cuda.synchronize()
     print(f"\nrecorded {sum(rec.counts.values())} calls ({rec.counts}), {len(rec.records)} distinct, in {time.time() - t0:.0f} s")
     return rec
@@ -111,14 +155,22 @@ def test_recorded_launches_cover_every_known_family(recorded):
     for kind in ("bf16", "f16"):
         have = sorted(f for k, f in fams if k == kind)
         print(f"{kind}: {len([r for r in recorded.records if r[1] == kind])} distinct launches; families {have}")
-    missing = [(k, f) for k in ("bf16", "f16") for f in lr.REQUIRED_FAMILIES if (k, f) not in fams
-               and not (k == "bf16" and f == "out_mode 1 + out_scale")]   # the 2^10 gradient scale is the fp16 classifier's only
+        print(f"{kind}: launch symbols called: {sorted(s for s, k in recorded.census if k == kind)}")
+        print(f"{kind}: distinct launches per new kind: "
+              f"{ {op: sum(1 for r in recorded.records if r[0] == op and r[1] == kind) for op in lr.NEW_KINDS} }")
+    missing = lr.missing_families(recorded.records)
     assert not missing, f"the models no longer reach (or the recorder missed) {missing}"
     # every kind of record is replayed below: a new kind must get a restatement, not be dropped
     assert {r[0] for r in recorded.records} <= REPLAYED, {r[0] for r in recorded.records} - REPLAYED
+    # the census: every launch symbol the models called is accounted for, and one that is replayed here left a record
+    assert {s for s, _ in recorded.census} <= set(lr.SYMBOL_COVERAGE), {s for s, _ in recorded.census} - set(lr.SYMBOL_COVERAGE)
+    gaps = lr.coverage_gaps(recorded.census, recorded.records, REPLAYED)
+    assert not gaps, gaps
+    here = sorted({s for s, _ in recorded.census if lr.SYMBOL_COVERAGE[s][0] != "elsewhere"})
+    print(f"census: {len({s for s, _ in recorded.census})} launch symbols called, {len(here)} replayed here: {here}")
 
 
-REPLAYED = {"conv", "attention", "attention_cross", "attention_bwd", "gn_bwd", "gn_affine"}
+REPLAYED = lr.REPLAYED
 
 
 # ------------------------------------------------------------------ conv replay
@@ -439,6 +491,257 @@ def test_groupnorm_affine_launches_match_float64(ops, recorded):
     _report("gn_affine", recs, results)
 
 
+# ------------------------------------------------------------------ token, resample, layout, VAE entry / exit, stride-2 conv
+SEEDS = {k: 6000 + 1000 * i for i, k in enumerate(lr.NEW_KINDS)}
+
+
+def _replay_kind(name, recorded, replay, roundings=1):
+    """replay(rec, T, seed) -> (worst err / bound, relative Frobenius error | None, report); bitwise kinds return 0 or inf."""
+    t0 = time.time()
+    recs = sorted(r for r in recorded.records if r[0] == name)
+    assert recs, f"the recorder captured no {name} launch"
+    results, fails = [], []
+    for i, rec in enumerate(recs):
+        T = lr.KIND_DTYPE[rec[1]]
+        torch.manual_seed(SEEDS[name] + i)
+        worst, fro, report = replay(rec, T, SEEDS[name] + i)
+        torch.cuda.synchronize()
+        u = lr.U[T]
+        ok = worst <= 1.0 and (fro is None or fro <= lr.fro_bound(roundings, u))
+        print(f"{rec}: worst err/bound {worst:.3f}" + ("" if fro is None else f", fro/u {fro / u:.3f}") + ("" if ok else f"  FAIL {report}"))
+        results.append(worst)
+        if not ok:
+            fails.append((rec, worst, None if fro is None else fro / u, report))
+    for k in ("bf16", "f16"):
+        ws = [w for r, w in zip(recs, results) if r[1] == k]
+        print(f"worst err/bound ('{k}', '{name}'): {max(ws) if ws else float('nan'):.3f} over {len(ws)} distinct launches")
+    print(f"{name} replay: {len(results)} launches, {time.time() - t0:.0f} s")
+    assert len(results) == len(recs)
+    assert not fails, fails
+
+
+def _bitwise(got, ref, what):
+    """0.0 where got and ref hold the same bit patterns, else inf with the count and the first mismatch."""
+    assert got.shape == ref.shape and got.dtype == ref.dtype, (what, got.shape, ref.shape, got.dtype, ref.dtype)
+    view = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[got.element_size()]
+    bad = got.contiguous().view(view) != ref.contiguous().view(view)
+    if not bool(bad.any()):
+        return 0.0, ""
+    j = int(bad.flatten().nonzero()[0])
+    return float("inf"), f"{what}: {int(bad.sum())} of {bad.numel()} differ, first at flat index {j}: got {got.flatten()[j].item()!r} ref {ref.flatten()[j].item()!r}"
+
+
+def _rows_limit(rec, numel):
+    if numel > lr.BIG:
+        raise NotImplementedError(f"the row-wise comparison does not subsample: {rec} has {numel} elements")
+
+
+def _gamma_beta(c):
+    return 1 + 0.2 * torch.randn(c, device=DEV), 0.1 * torch.randn(c, device=DEV)
+
+
+def test_layernorm_launches_match_float64(ops, recorded):
+    def replay(rec, T, seed):
+        _, _, rows, c, eps = rec
+        _rows_limit(rec, rows * c)
+        x = (torch.randn(rows, c, device=DEV) * 2 + 0.5).to(T)
+        gamma, beta = _gamma_beta(c)
+        got = ops.layernorm(x, gamma, beta, eps)
+        ref, bound = lr.layernorm_restate(x, gamma, beta, eps, T)
+        w, e2, r2, rep = lr.worst_ratio(got, ref, bound)
+        return w, (e2 / r2) ** 0.5, rep
+    _replay_kind("layernorm", recorded, replay)
+
+
+def test_layernorm_f32out_launches_match_float64(ops, recorded):
+    def replay(rec, T, seed):
+        _, _, n, t, pitch, c, eps = rec
+        _rows_limit(rec, n * t * c)
+        x = (torch.randn(n, pitch, c, device=DEV) * 3 + 0.5).to(T)
+        x[:, t:] = float("nan")   # the pad rows are never read
+        gamma, beta = _gamma_beta(c)
+        got = ops.layernorm_f32out(x, t, gamma, beta, eps)
+        assert got.shape == (n, t, c) and got.dtype == torch.float32
+        ref, bound = lr.layernorm_restate(x[:, :t], gamma, beta, eps, T, f32out=True)
+        w, _, _, rep = lr.worst_ratio(got, ref, bound)
+        return w, None, rep
+    _replay_kind("layernorm_f32out", recorded, replay)
+
+
+def test_geglu_launches_match_float64(ops, recorded):
+    def replay(rec, T, seed):
+        _, _, rows, inner = rec
+        _rows_limit(rec, rows * inner)
+        u = (torch.randn(rows, 2 * inner, device=DEV) * 1.5).to(T)
+        got = ops.geglu(u)
+        ref, bound = lr.geglu_restate(u, T)
+        w, e2, r2, rep = lr.worst_ratio(got, ref, bound)
+        return w, (e2 / r2) ** 0.5, rep
+    _replay_kind("geglu", recorded, replay)
+
+
+def test_quick_gelu_launches_match_float64(ops, recorded):
+    def replay(rec, T, seed):
+        _, _, rows, inner = rec
+        _rows_limit(rec, rows * inner)
+        u = torch.randn(rows, inner, device=DEV) * 4.0    # the fc1 outputs reach about +-12
+        u.view(-1)[:8] = torch.tensor(lr.QUICK_GELU_SPECIALS, device=DEV)
+        u = u.to(T)
+        got = ops.quick_gelu(u)
+        ref, bound = lr.quick_gelu_restate(u, T)
+        w, e2, r2, rep = lr.worst_ratio(got, ref, bound)
+        return w, (e2 / r2) ** 0.5, rep
+    _replay_kind("quick_gelu", recorded, replay)
+
+
+SENTINEL = -7.0
+
+
+def _causal_launch(qkv, heads, t, guard=4096):
+    """adm_attention_causal on a sentinel-filled `out` with a sentinel-filled guard behind it -> out [n, pitch, C]; the rows >= t
+    and the guard must keep the sentinel."""
+    from autodiffusion_amd import _lib
+    n, pitch, c3 = qkv.shape
+    c = c3 // 3
+    lib = _lib.load(lr.kind_of(qkv))
+    buf = torch.full((n * pitch * c + guard,), SENTINEL, dtype=qkv.dtype, device=qkv.device)
+    _lib.check(lib.adm_attention_causal(qkv.data_ptr(), buf.data_ptr(), n, t, pitch, heads, 64, torch.cuda.current_stream().cuda_stream),
+               "adm_attention_causal (replay)")
+    torch.cuda.synchronize()
+    out = buf[:n * pitch * c].view(n, pitch, c)
+    assert bool((buf[n * pitch * c:] == SENTINEL).all()), "the guard behind out was written"
+    assert bool((out[:, t:] == SENTINEL).all()), "out rows >= t were written"
+    return out
+
+
+def _causal_compare(qkv, out, heads, t, T, images):
+    worst, num, den, report = 0.0, 0.0, 0.0, ""
+    c = heads * 64
+    for j in images:
+        q, k, v = (qkv[j, :t, i * c:(i + 1) * c].reshape(t, heads, 64).permute(1, 0, 2) for i in range(3))
+        ref, bound = lr.attention_restate(q, k, v, 0.125, T, causal=True)
+        got = out[j, :t].reshape(t, heads, 64).permute(1, 0, 2)
+        w, e2, r2, rep = lr.worst_ratio(got, ref, bound)
+        if w > worst:
+            worst, report = w, f"prompt {j} (head, row, channel) {rep}"
+        num, den = num + e2, den + r2
+    return worst, (num / den) ** 0.5, report
+
+
+def _causal_qkv(n, t, pitch, heads, T):
+    qkv = torch.full((n, pitch, 3 * heads * 64), float("nan"), device=DEV)   # rows >= t are never read
+    qkv[:, :t] = torch.randn(n, t, 3 * heads * 64, device=DEV)
+    return qkv.to(T)
+
+
+def test_attention_causal_launches_match_float64(ops, recorded):
+    def replay(rec, T, seed):
+        _, _, n, t, pitch, heads = rec
+        qkv = _causal_qkv(n, t, pitch, heads, T)
+        out = _causal_launch(qkv, heads, t)
+        return _causal_compare(qkv, out, heads, t, T, sorted({0, n - 1, int(torch.randint(0, n, (1,)).item())}))
+    _replay_kind("attention_causal", recorded, replay, roundings=2)
+
+
+def test_clip_embed_launches_are_bit_exact(ops, recorded):
+    def replay(rec, T, seed):
+        _, _, n, t, pitch, c, vocab, positions = rec
+        tok, pos = torch.randn(vocab, c, device=DEV), 0.3 * torch.randn(positions, c, device=DEV)
+        ids = torch.randint(0, vocab, (n, t), device=DEV)
+        ids[0, 0], ids[-1, -1] = 0, vocab - 1
+        got = ops.clip_embed(ids, tok, pos, pitch, T)
+        w, rep = _bitwise(got, lr.clip_embed_restate(ids, tok, pos, pitch, T), "clip_embed")
+        return w, None, rep
+    _replay_kind("clip_embed", recorded, replay)
+
+
+def test_resample_launches_match_float64(ops, recorded):
+    names = {v: k for k, v in lr.RESAMPLE_MODES.items()}
+
+    def replay(rec, T, seed):
+        _, _, n, h, w, c, mode, has_aff = rec
+        x = torch.randn(n, h, w, c, device=DEV).to(T)
+        aff = (1 + 0.2 * torch.randn(n, c, device=DEV), 0.2 * torch.randn(n, c, device=DEV)) if has_aff else None
+        got = ops.resample(x, names[mode], aff)
+        torch.cuda.synchronize()
+        worst, num, den, report = 0.0, 0.0, 0.0, ""
+        for j in lr.compared_images(n, max(x.numel(), got.numel()), seed):
+            ref, bound = lr.resample_restate(x[j:j + 1], mode, None if aff is None else (aff[0][j:j + 1], aff[1][j:j + 1]), T)
+            if bound is None:   # a copy: bitwise
+                wj, rep = _bitwise(got[j:j + 1], ref.to(T), f"image {j}")
+            else:
+                wj, e2, r2, rep = lr.worst_ratio(got[j:j + 1], ref, bound)
+                num, den = num + e2, den + r2
+            if wj > worst:
+                worst, report = wj, f"image {j} {rep}"
+        return worst, ((num / den) ** 0.5 if den else None), report
+    _replay_kind("resample", recorded, replay)
+
+
+def test_nchw_to_nhwc_pad_launches_are_bit_exact(ops, recorded):
+    def replay(rec, T, seed):
+        _, _, n, c, h, w, cpad = rec
+        x = torch.randn(n, c, h, w, device=DEV) * 1.5
+        got = ops.nchw_to_nhwc_pad(x, cpad, T)
+        worst, report = 0.0, ""
+        for j in lr.compared_images(n, got.numel(), seed):
+            wj, rep = _bitwise(got[j:j + 1], lr.nchw_to_nhwc_pad_restate(x[j:j + 1], cpad, T), f"image {j}")
+            if wj > worst:
+                worst, report = wj, rep
+        return worst, None, report
+    _replay_kind("nchw_to_nhwc_pad", recorded, replay)
+
+
+def test_vae_latent_in_launches_match_float64(ops, recorded):
+    import numpy as np
+    inv = float(np.float32(1.0 / 0.18215))   # LatentDiffusion's 1 / scale_factor, as the kernel receives it
+
+    def replay(rec, T, seed):
+        _, _, n, zc, e, h, w = rec
+        z = torch.randn(n, e, h, w, device=DEV) * 4 * 0.18215
+        wt, b = torch.randn(zc, e, 1, 1, device=DEV) * 0.5, torch.randn(zc, device=DEV) * 0.1
+        got = ops.vae_latent_in(z, wt, b, inv, T)
+        assert got.shape == (n, h, w, 32)
+        if bool((got[..., zc:] != 0).any()):
+            return float("inf"), None, "a pad channel is not zero"
+        ref, bound = lr.vae_latent_in_restate(z, wt, b, inv, T)
+        wst, e2, r2, rep = lr.worst_ratio(got[..., :zc], ref, bound)
+        return wst, (e2 / r2) ** 0.5, rep
+    _replay_kind("vae_latent_in", recorded, replay)
+
+
+def test_vae_image_out_launches_are_bit_exact(ops, recorded):
+    def replay(rec, T, seed):
+        _, _, n, h, w, want_unit, want_u8 = rec
+        x = torch.randn(n, 3, h, w, generator=torch.Generator().manual_seed(seed)) * 1.2
+        x.view(-1)[:len(lr.IMAGE_OUT_SPECIALS)] = torch.tensor(lr.IMAGE_OUT_SPECIALS)
+        x.view(-1)[-len(lr.IMAGE_OUT_SPECIALS):] = torch.tensor(lr.IMAGE_OUT_SPECIALS)
+        unit_ref, u8_ref = lr.vae_image_out_restate(x)   # on the host, as tests/test_hip_sd_vae.py::test_image_out_is_bit_exact
+        unit, u8 = ops.vae_image_out(x.to(DEV), want_unit=want_unit, want_u8=want_u8)
+        if (unit is None) != (not want_unit) or (u8 is None) != (not want_u8):
+            return float("inf"), None, "the outputs asked for were not returned"
+        worst, report = 0.0, ""
+        for got, ref, what in ((unit, unit_ref, "unit"), (u8, u8_ref, "u8")):
+            if got is not None:
+                wj, rep = _bitwise(got.cpu(), ref.contiguous(), what)
+                if wj > worst:
+                    worst, report = wj, rep
+        return worst, None, report
+    _replay_kind("vae_image_out", recorded, replay)
+
+
+def test_stride2_conv2d_launches_match_float64(ops, recorded):
+    """The UNets' stride-2 convs on adm_conv2d, at shapes the Inception replay never sees: inception_replay's own restatement,
+    bound and comparison."""
+    import inception_replay as ir
+
+    def replay(rec, T, seed):
+        worst, fro, report = ir.replay_conv(ops, rec, seed, DEV)
+        print(f"  conv2d {ir.conv_label(rec)}")
+        return worst, fro, report
+    _replay_kind("conv2d", recorded, replay)
+
+
 # ------------------------------------------------------------------ fp16 range
 @pytest.mark.parametrize("case", ["one pass 3x3", "split-K 3x3", "resident 1x1", "fp32 NCHW head"])
 def test_fp16_conv_outputs_beyond_the_range_become_signed_inf(ops, case):
@@ -519,3 +822,48 @@ def test_groupnorm_statistics_at_a_large_mean(ops, dtype):
         passing[form] = best
     print(f"GroupNorm {dtype}: largest |mean|/std within the bound: {passing}")
     assert all(v is not None and v >= 16 for v in passing.values()), passing
+
+
+# ------------------------------------------------------------------ LayerNorm at a large mean
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_layernorm_at_a_large_mean(ops, dtype):
+    """adm_layernorm and adm_layernorm_f32out against the float64 LayerNorm of the same 16-bit rows at |mean| / std in RATIOS, within
+    launch_replay's LayerNorm bound: c = 320 and 768, 64 rows.  Must hold up to a ratio of 16, what GroupNorm is held to above; the
+    largest passing ratio is printed."""
+    rows = 64
+    passing = {}
+    torch.manual_seed(9)
+    for c in (320, 768):
+        gamma, beta = _gamma_beta(c)
+        for form in ("layernorm", "layernorm_f32out"):
+            best = None
+            for r in RATIOS:
+                x = (torch.randn(rows, c, device=DEV) + r).to(dtype)
+                if form == "layernorm":
+                    got = ops.layernorm(x, gamma, beta, 1e-5)
+                else:
+                    got = ops.layernorm_f32out(x.view(2, rows // 2, c), rows // 2, gamma, beta, 1e-5).view(rows, c)
+                ref, bound = lr.layernorm_restate(x, gamma, beta, 1e-5, dtype, f32out=form != "layernorm")
+                ratio, _, _, rep = lr.worst_ratio(got, ref, bound)
+                print(f"LayerNorm {dtype} {form} c {c} |mean|/std {r}: worst err/bound {ratio:.3f}" + ("" if ratio <= 1.0 else f"  ({rep})"))
+                if ratio <= 1.0 and (best is None or best == RATIOS[RATIOS.index(r) - 1]):
+                    best = r
+            passing[(form, c)] = best
+    print(f"LayerNorm {dtype}: largest |mean|/std within the bound: {passing}")
+    assert all(v is not None and v >= 16 for v in passing.values()), passing
+
+
+# ------------------------------------------------------------------ causal attention at the tile edges of its schedule
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("t", [1, 16, 17, 32, 33, 77, 192, 193, 256])
+def test_attention_causal_at_tile_edges(ops, t, dtype):
+    """The 16-query and 32-key tile boundaries and the LDS size switch above T = 192: 2 heads, 2 prompts, every element against the
+    causal restatement; nothing beyond row t - 1 is written."""
+    n, heads = 2, 2
+    torch.manual_seed(100 + t)
+    qkv = _causal_qkv(n, t, t, heads, dtype)
+    out = _causal_launch(qkv, heads, t)
+    worst, fro, report = _causal_compare(qkv, out, heads, t, dtype, range(n))
+    u = lr.U[dtype]
+    print(f"attention_causal T {t} {dtype}: worst err/bound {worst:.3f}, fro/u {fro / u:.3f}")
+    assert worst <= 1.0 and fro <= lr.fro_bound(2, u), (worst, fro / u, report)

@@ -37,23 +37,33 @@ def bf(x):
     return x.to(torch.bfloat16)
 
 
-@pytest.mark.parametrize("rows,c", [(7, 64), (1024, 320), (300, 640), (130, 1280), (5, 2048)])
-def test_layernorm(rows, c):
+def _both_torsos(cases):
+    """Every case in bf16 (under the id it has always had) and in fp16."""
+    return dict(argvalues=[c + (t,) for t in (torch.bfloat16, torch.float16) for c in cases],
+                ids=[p + "-".join(map(str, c)) for p in ("", "fp16-") for c in cases])
+
+
+@pytest.mark.parametrize("rows,c,dtype", **_both_torsos([(7, 64), (1024, 320), (300, 640), (130, 1280), (5, 2048)]))
+def test_layernorm(rows, c, dtype):
     from autodiffusion_amd import ops
     g = torch.Generator().manual_seed(rows + c)
-    x = bf(torch.randn(rows, c, generator=g) * 2 + 0.5).to(DEV)
+    x = (torch.randn(rows, c, generator=g) * 2 + 0.5).to(dtype).to(DEV)
     gamma, beta = (1 + 0.2 * torch.randn(c, generator=g)).to(DEV), (0.1 * torch.randn(c, generator=g)).to(DEV)
     ref = F.layer_norm(x.float(), (c,), gamma, beta, eps=1e-5)
-    check(ops.layernorm(x, gamma, beta), ref.cpu(), f"layernorm {rows}x{c}", 5e-3, 2e-2)
+    got = ops.layernorm(x, gamma, beta)
+    assert got.dtype == dtype
+    check(got, ref.cpu(), f"layernorm {rows}x{c} {dtype}", 5e-3, 2e-2)
 
 
-@pytest.mark.parametrize("rows,inner", [(9, 256), (4096, 1280)])
-def test_geglu(rows, inner):
+@pytest.mark.parametrize("rows,inner,dtype", **_both_torsos([(9, 256), (4096, 1280)]))
+def test_geglu(rows, inner, dtype):
     from autodiffusion_amd import ops
     g = torch.Generator().manual_seed(rows)
-    u = bf(torch.randn(rows, 2 * inner, generator=g) * 1.5).to(DEV)
+    u = (torch.randn(rows, 2 * inner, generator=g) * 1.5).to(dtype).to(DEV)
     a, gate = u.float().chunk(2, dim=-1)
-    check(ops.geglu(u), (a * F.gelu(gate)).cpu(), f"geglu {rows}x{inner}", 5e-3, 2e-2)
+    got = ops.geglu(u)
+    assert got.dtype == dtype
+    check(got, (a * F.gelu(gate)).cpu(), f"geglu {rows}x{inner} {dtype}", 5e-3, 2e-2)
 
 
 @pytest.mark.parametrize("n,hw,c,dtype", [(2, 32, 320, torch.bfloat16), (1, 64, 320, torch.float16), (3, 16, 640, torch.bfloat16),
