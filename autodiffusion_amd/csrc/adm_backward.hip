@@ -457,6 +457,7 @@ extern "C" int adm_grad_add(const adm_bf16* a, const adm_bf16* b, adm_bf16* out,
                             void* stream) {
   ADM_REQUIRE(a && b && out, ADM_E_ARG, "adm_grad_add: null pointer");
   ADM_REQUIRE(n > 0 && h > 0 && w > 0 && c % 8 == 0, ADM_E_SHAPE, "adm_grad_add: bad shape");
+  ADM_REQUIRE(!b_half || (h % 2 == 0 && w % 2 == 0), ADM_E_SHAPE, "adm_grad_add: odd size with a half-resolution operand");
   ADM_REQUIRE(adm_aligned16(a) && adm_aligned16(b) && adm_aligned16(out), ADM_E_ALIGN, "adm_grad_add: unaligned pointer");
   hipLaunchKernelGGL(add_kernel, dim3(grid_for((long long)n * h * w * (c / 8))), dim3(256), 0, (hipStream_t)stream, a, b,
                      out, n, h, w, c, b_half);

@@ -272,6 +272,9 @@ extern "C" int adm_stem_conv3x3(const float* x, const float* w, const float* bia
               "adm_stem_conv3x3: cin=%d cout=%d unsupported (cin<=8, cout%%8==0, cout<=512)", cin, cout);
   ADM_REQUIRE(adm_aligned16(out), ADM_E_ALIGN, "adm_stem_conv3x3: out not 16-byte aligned");
   const size_t smem = (size_t)(cin * 9 + 1) * cout * sizeof(float);
+  // the weights and the bias sit in dynamic LDS and the kernel does not opt in above the 64 KB default
+  ADM_REQUIRE(smem <= 64 * 1024, ADM_E_SHAPE,
+              "adm_stem_conv3x3: cin=%d cout=%d needs %zu bytes of LDS, above the 64 KB the kernel is launched with", cin, cout, smem);
   const long long items = (long long)n * h * wd * (cout / 8);
   int blocks = (int)((items + 255) / 256);
   if (blocks > 2048) blocks = 2048;

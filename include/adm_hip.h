@@ -109,7 +109,10 @@ int adm_linear_f32(const float* in, const float* w, const float* bias, const flo
                    const int64_t* idx, float* out, int n, int k, int o, int silu_in, void* stream);
 
 /* ---------------------------------------------------------------- stem (A5, first conv)
- * input_blocks.0.0: conv3x3 pad 1 on the fp32 NCHW image -> bf16 NHWC (unet.py:480-483, 656-658). */
+ * input_blocks.0.0: conv3x3 pad 1 on the fp32 NCHW image -> bf16 NHWC (unet.py:480-483, 656-658).
+ * cin <= 8, cout % 8 == 0, cout <= 512, and the weights and bias must fit the 64 KB of dynamic LDS the
+ * kernel is launched with: (cin * 9 + 1) * cout * 4 <= 65536 (cin 3: any cout; cin 8: cout <= 224);
+ * a larger shape is refused with ADM_E_SHAPE before the launch.                                    */
 int adm_stem_conv3x3(const float* x_nchw, const float* w /*[Cout,Cin,3,3]*/, const float* bias,
                      adm_bf16* out_nhwc, int n, int cin, int h, int w_, int cout, void* stream);
 
@@ -314,7 +317,8 @@ int adm_gn_bwd_finalize(const float* partial, const float* aff_a, const float* s
 int adm_gn_bwd_apply(const adm_bf16* x, const adm_bf16* dy, const float* aff_a, const float* aff_b,
                      const float* k1, const float* k0, const adm_bf16* add, adm_bf16* out,
                      int n, int h, int w, int c, int silu, int dy_half, int add_half, void* stream);
-/* out = a + (b_half ? 0.25 * b[y/2, x/2] : b): gradient accumulation at a fan-out.             */
+/* out = a + (b_half ? 0.25 * b[y/2, x/2] : b): gradient accumulation at a fan-out; with b_half,
+ * b is [n, h/2, w/2, c] and h, w must be even (ADM_E_SHAPE otherwise).                          */
 int adm_grad_add(const adm_bf16* a, const adm_bf16* b, adm_bf16* out, int n, int h, int w, int c,
                  int b_half, void* stream);
 

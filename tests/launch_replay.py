@@ -6,7 +6,9 @@ libraries and notes (symbol, library) -- nothing more.  SYMBOL_COVERAGE maps eve
 it here or to the test that holds it elsewhere, so "every launch" is checked, not assumed.  Records: every adm_conv call is
 captured as a copy of its adm_conv_args without the pointers, plus which optional pointers were set (those are flags); the
 attention, GroupNorm, token (LayerNorm, GEGLU, quick-GELU, embedding), resample, layout, VAE entry / exit and stride-2 conv2d calls
-are captured at the ops level by shape and flags.  The sampler-step kernels (adm_ddim_step, adm_ddpm_step, adm_sd_step,
+are captured at the ops level by shape and flags, and so are the classifier heads: the attention pool's four kernels, the
+adaptive / spatial / spatial_v2 heads' channel mean, broadcast add, vector activation and vector GroupNorm, and the loss
+gradient.  The sampler-step kernels (adm_ddim_step, adm_ddpm_step, adm_sd_step,
 adm_dpm_step) are not launched by a model evaluation: they stay with their oracle goldens.
 
 Restatement: the op in float64 on the operands exactly as the kernel sees them -- 16-bit inputs, weights and residuals; the
@@ -56,6 +58,44 @@ Per-element bounds, u = 2^-8 (bf16) or 2^-11 (fp16), ulp_T(v) = 2u * 2^floor(log
              multiply-adds and the bias add.  Pad channels exactly zero.
   vae_image_out      clamp((x + 1) / 2, 0, 1) in fp32 and trunc(255 unit): bitwise.
   conv2d     the UNets' stride-2 convs on adm_conv2d: inception_replay's restatement, bound and comparison, imported.
+  The classifier heads, e = 2^-24 (one fp32 add or multiply, relative to the summed magnitudes); SILU_REL also stands for one
+             library expf / logf / rsqrtf / sqrtf / division; F32_MIN = 2^-126 is added where a result may leave fp32's normal
+             range.  E_s = 2 e (|a h| + |b|) + SILU_REL (1 + |z|) |s| is the error of s = adm_silu(z), z = a h + b: the
+             multiply-add in front (SiLU' <= 1.1) and an exp2 whose argument carries a relative e, so a relative |z| e on it.
+  pool_prep  rows 1 + p: ulp_T(|ref|) / 2 + E_s + e (|s| + |pos|); row 0: ulp_T(|ref|) / 2 + mean_p E_s + (hw + 2) e mean_p |s|
+             + SILU_REL |mean s| + e (|mean s| + |pos_0|) -- hw sequential adds, the division by hw, the add of pos.  Rows
+             hw + 1 .. tpad: exactly zero.
+  pool_attn_fwd   logit_j: δ_j = (d + c1) e Σ |q k_j| / sqrt(d), c1 = 4 (d multiply-adds, the product with the scale, rsqrtf
+             of d within an ulp = 2 e); w_j relative: 2 max_j δ_j (its own logit and the sum's) + e (span_j + Σ w span), span_j
+             = max logit - logit_j (the subtraction in front of expf, for w_j and for the sum) + 3 SILU_REL (expf of w_j, of
+             the sum's terms, the division) + (ceil(T / 64) + 7) e (a lane's adds, six butterfly steps, of positive terms) --
+             plus F32_MIN: a weight below fp32's range is 0.  wts[t:tpad] exactly zero.  a0: Σ_s bound(w_s) |v_s| +
+             (T + c2) e Σ_s w_s |v_s|, c2 = 1: T sequential multiply-adds.
+  pool_attn_bwd   on the stored fp32 weights w.  dw_s = Σ_j da_j v_sj: E_dw = (d + 1) e Σ_j |da_j v_sj|; δ = Σ_s w_s dw_s:
+             E_δ = Σ_s w_s E_dw_s + (ceil(T / 64) + 7) e Σ_s w_s |dw_s|; dlogit_s = w_s (dw_s - δ) / sqrt(d): E_dl =
+             w_s / sqrt(d) (E_dw_s + E_δ + 5 e (|dw_s| + |δ|)) -- the subtraction cancels, so its operands' errors and
+             roundings are carried at |dw| + |δ|.  dK = round_T(dlogit q): ulp_T(|ref|) / 2 + |q| E_dl + e |ref|; dV =
+             round_T(w da): ulp_T(|ref|) / 2 + e |ref|; dQ row 0 = round_T(Σ_s dlogit_s k_s): ulp_T(|ref|) / 2 +
+             Σ_s E_dl_s |k_s| + (T + 1) e Σ_s |dlogit_s k_s|.  dQ rows > 0 and every row >= T: exactly zero.
+  pool_prep_bwd   round_T(dtok[1 + p] + dtok[0] / hw): ulp_T(|ref|) / 2 + SILU_REL |dtok_0 / hw| + e (|dtok[1 + p]| + |dtok_0 / hw|).
+  channel_mean    fp32: (ceil(hw / 4) + 3) e mean |v| (a lane's adds, three adds of the four lanes) + SILU_REL |ref| (the
+             division) + mean E_s with the affine.
+  bcast_add  without add: round_T of the fp32 product v scale, bitwise.  With add: ulp_T(|ref|) / 2 + e (2 |v scale| + |add|).
+  vec_act    SiLU: SILU_REL |ref| + F32_MIN (expf, an add, a division; below z = -88.7 expf overflows and the result is -0).
+             SiLU': dy s (1 + z (1 - s)): SILU_REL |dy| s (1 + |z|) + F32_MIN -- 1 - s cancels for large z, absolute e there.
+             ReLU and ReLU': exact, ReLU'(0) = 0.
+  vec_gn     k = (ceil(cpg / 8) + 3) e, cpg = c / 32: a lane's adds and three butterfly steps.  E_m = k mean|x| + SILU_REL
+             |mean|; d = x - mean carries E_m + e |d|, so E_v = 2 mean|d| E_m + E_m^2 + (k + 4 e + SILU_REL) var and rstd is
+             relative rel_r = E_v / (2 (var + eps)) + e + 2 SILU_REL (the add of eps, sqrtf, the division).  y: |γ| rstd E_m +
+             |γ d rstd| (rel_r + 4 e) + e |y|.  mean: E_m; rstd: rstd rel_r.  cpg = 1: y = β exactly.
+  vec_gn_bwd on the stored (mean, rstd): g = γ dz, xh = (x - mean) rstd, s1 = mean g, s2 = mean g xh: E_1 = (k + e) mean|g| +
+             SILU_REL |s1|, E_2 = (k + 4 e) mean|g xh| + SILU_REL |s2|; dx = rstd (g - s1 - xh s2): rstd (E_1 + |xh| E_2 +
+             4 e (|g| + |s1| + |xh s2|)) + e |ref|.  cpg = 1: dx = 0 exactly.
+  logsoftmax_grad   softmax_i relative: e dist_i (dist = max - logit, the subtraction) + 3 SILU_REL (expf, the sum's expf,
+             the division) + (ceil(k / 256) + 8) e (a thread's adds, the eight steps of the block tree) + e Σ softmax dist;
+             dl = scale (onehot - softmax): |scale| (rel softmax + F32_MIN) + 2 e |ref|.  logp_sel = l_y - max - logf(sum):
+             e dist_y + SILU_REL (1 + |log sum|) + the sum's relative error + 2 e |ref|.
+  grad_add   round_T(a + s b), s = 1 or an exact 1 / 4: ulp_T(|ref|) / 2 + e (|a| + |s b|).
   Frobenius  ||got - ref|| / ||ref|| <= FRO_U u sqrt(r), FRO_U = 0.6: one rounding to T has an RMS relative error of at most
              u / sqrt(3) ~ 0.58 u; r roundings in sequence (A, then A + residual; dz, then dz SiLU'; P, then the output) add in
              quadrature.
@@ -120,7 +160,7 @@ def _e(test: str) -> tuple:
 
 
 # launch symbol -> the record kinds that replay it here, or ("elsewhere", "tests/<file>.py::<test>") for what stays where it is:
-# the fp32 vector kernels of the classifier head, the fp32 embedding / linear kernels, the weight packers (every conv replay
+# the fp32 embedding / linear kernels, the weight packers (every conv replay
 # compares against round_t(w), so a mis-packed weight fails there too), the sampler steps, and the evaluation-side kernels of
 # the Inception replay and the FID / precision-recall tests.
 SYMBOL_COVERAGE = {
@@ -147,18 +187,19 @@ SYMBOL_COVERAGE = {
     "adm_vae_latent_in": ("vae_latent_in",),
     "adm_vae_image_out": ("vae_image_out",),
     "adm_conv2d": ("conv2d",),
-    # the classifier head's fp32 vector kernels and its attention pool
-    "adm_vec_act": _e("tests/test_hip_classifier.py::test_pool_head_kernels_match_torch"),
-    "adm_vec_gn": _e("tests/test_hip_classifier.py::test_pool_head_kernels_match_torch"),
-    "adm_vec_gn_bwd": _e("tests/test_hip_classifier.py::test_pool_head_kernels_match_torch"),
-    "adm_channel_mean": _e("tests/test_hip_classifier.py::test_pool_head_kernels_match_torch"),
-    "adm_bcast_add": _e("tests/test_hip_classifier.py::test_pool_head_kernels_match_torch"),
-    "adm_pool_prep": _e("tests/test_hip_classifier.py::test_classifier_logits_and_guidance_gradient_golden"),
-    "adm_pool_attn_fwd": _e("tests/test_hip_classifier.py::test_classifier_logits_and_guidance_gradient_golden"),
-    "adm_pool_attn_bwd": _e("tests/test_hip_classifier.py::test_classifier_logits_and_guidance_gradient_golden"),
-    "adm_pool_prep_bwd": _e("tests/test_hip_classifier.py::test_classifier_logits_and_guidance_gradient_golden"),
-    "adm_grad_add": _e("tests/test_hip_classifier.py::test_classifier_logits_and_guidance_gradient_golden"),
-    "adm_logsoftmax_grad": _e("tests/test_hip_classifier.py::test_logsoftmax_grad"),
+    # the classifier's heads: the attention pool, the fp32 vector kernels of the other three, the loss gradient
+    "adm_pool_prep": ("pool_prep",),
+    "adm_pool_attn_fwd": ("pool_attn_fwd",),
+    "adm_pool_attn_bwd": ("pool_attn_bwd",),
+    "adm_pool_prep_bwd": ("pool_prep_bwd",),
+    "adm_channel_mean": ("channel_mean",),
+    "adm_bcast_add": ("bcast_add",),
+    "adm_vec_act": ("vec_act",),
+    "adm_vec_gn": ("vec_gn",),
+    "adm_vec_gn_bwd": ("vec_gn_bwd",),
+    "adm_logsoftmax_grad": ("logsoftmax_grad",),
+    # no caller in the package: held by its direct test
+    "adm_grad_add": _e("tests/test_hip_launch_replay.py::test_grad_add_at_edges"),
     # fp32 embedding path and the direct stem
     "adm_linear_f32": _e("tests/test_hip_kernels.py::test_linear_f32"),
     "adm_timestep_embedding": _e("tests/test_hip_kernels.py::test_timestep_embedding"),
@@ -212,7 +253,7 @@ RESAMPLE_MODES = {"down": 1, "up": 2, "stride2": 3, "zero2": 4}
 
 class Recorder:
     """Patches (through pytest's monkeypatch) every launch symbol on both libraries -- the census, and adm_conv's record -- and
-    the attention / GroupNorm / token / resample / layout / VAE / conv2d wrappers of ops (the other records)."""
+    the attention / GroupNorm / token / resample / layout / VAE / conv2d / classifier-head wrappers of ops (the other records)."""
 
     def __init__(self, monkeypatch):
         from autodiffusion_amd import _lib, ops
@@ -328,11 +369,65 @@ class Recorder:
             self._add(ir.conv2d_record(self._cin, x, w_packed, bias, kh, kw, stride, pad, relu, out))
             return o_c2d(x, w_packed, bias, kh, kw, stride, pad, relu, out)
 
+        o_pp, o_pf, o_pb, o_ppb = ops.pool_prep, ops.pool_attn_fwd, ops.pool_attn_bwd, ops.pool_prep_bwd
+        o_cm, o_ba, o_va, o_vg, o_vgb, o_lsg = ops.channel_mean, ops.bcast_add, ops.vec_act, ops.vec_gn, ops.vec_gn_bwd, ops.logsoftmax_grad
+
+        def pool_prep(h, aff, pos, tpad):
+            n, hh, ww, c = h.shape
+            self._add(("pool_prep", kind_of(h), n, hh * ww, c, int(tpad)))
+            return o_pp(h, aff, pos, tpad)
+
+        def pool_attn_fwd(qkv, t, heads):
+            n, tpad, c3 = qkv.shape
+            self._add(("pool_attn_fwd", kind_of(qkv), n, int(t), tpad, heads, c3 // 3 // heads))
+            return o_pf(qkv, t, heads)
+
+        def pool_attn_bwd(qkv, wts, da0, t, heads):
+            n, tpad, c3 = qkv.shape
+            self._add(("pool_attn_bwd", kind_of(qkv), n, int(t), tpad, heads, c3 // 3 // heads))
+            return o_pb(qkv, wts, da0, t, heads)
+
+        def pool_prep_bwd(dtok, hh, ww):
+            n, tpad, c = dtok.shape
+            self._add(("pool_prep_bwd", kind_of(dtok), n, hh * ww, c, tpad))
+            return o_ppb(dtok, hh, ww)
+
+        def channel_mean(h, aff=None, out=None, col=0):
+            n, hh, ww, c = h.shape
+            self._add(("channel_mean", kind_of(h), n, hh * ww, c, aff is not None, int(col) if out is not None else 0,
+                       c if out is None else out.shape[1]))
+            return o_cm(h, aff, out, col)
+
+        def bcast_add(v, shape, dtype, scale, add=None, col=0):
+            n, hh, ww, c = shape
+            self._add(("bcast_add", KIND_OF_DTYPE[dtype], n, hh * ww, c, add is not None, int(col), v.shape[1]))
+            return o_ba(v, shape, dtype, scale, add, col)
+
+        # the four below are fp32 kernels that ops launches from the bf16 library whatever the torso
+        def vec_act(x, mode, dy=None):
+            self._add(("vec_act", "bf16", x.numel(), VEC_ACT_MODES[mode], dy is not None))
+            return o_va(x, mode, dy)
+
+        def vec_gn(x, gamma, beta, eps=ops.GN_EPS):
+            self._add(("vec_gn", "bf16", x.shape[0], x.shape[1], float(eps)))
+            return o_vg(x, gamma, beta, eps)
+
+        def vec_gn_bwd(x, gamma, stats, dz):
+            self._add(("vec_gn_bwd", "bf16", x.shape[0], x.shape[1]))
+            return o_vgb(x, gamma, stats, dz)
+
+        def logsoftmax_grad(logits, y, scale):
+            self._add(("logsoftmax_grad", "bf16", logits.shape[0], logits.shape[1], float(scale)))
+            return o_lsg(logits, y, scale)
+
         for name, fn in (("attention", attention), ("attention_cross", attention_cross), ("attention_bwd", attention_bwd),
                          ("gn_affine", gn_affine), ("gn_bwd", gn_bwd), ("layernorm", layernorm), ("layernorm_f32out", layernorm_f32out),
                          ("geglu", geglu), ("quick_gelu", quick_gelu), ("attention_causal", attention_causal), ("clip_embed", clip_embed),
                          ("resample", resample), ("nchw_to_nhwc_pad", nchw_to_nhwc_pad), ("vae_latent_in", vae_latent_in),
-                         ("vae_image_out", vae_image_out), ("conv2d", conv2d)):
+                         ("vae_image_out", vae_image_out), ("conv2d", conv2d), ("pool_prep", pool_prep),
+                         ("pool_attn_fwd", pool_attn_fwd), ("pool_attn_bwd", pool_attn_bwd), ("pool_prep_bwd", pool_prep_bwd),
+                         ("channel_mean", channel_mean), ("bcast_add", bcast_add), ("vec_act", vec_act), ("vec_gn", vec_gn),
+                         ("vec_gn_bwd", vec_gn_bwd), ("logsoftmax_grad", logsoftmax_grad)):
             monkeypatch.setattr(ops, name, fn)
 
     def _add(self, rec):
@@ -384,11 +479,17 @@ REQUIRED_FAMILIES = (["variant 3", "variant 5", "variant 6", "variant 10", "kspl
                      + ["attention d 512", "non-square map"]
                      + ["layernorm", "layernorm_f32out", "geglu", "quick_gelu", "attention_causal", "clip_embed", "resample",
                         "nchw_to_nhwc_pad", "vae_latent_in", "vae_image_out", "conv2d"])
-# families one library alone reaches: the 2^10 gradient scale is the fp16 classifier's; adm_vae_image_out is an fp32 kernel that
-# ops launches from the bf16 library whatever the torso
-ONE_LIBRARY_FAMILIES = {"out_mode 1 + out_scale": "f16", "vae_image_out": "bf16"}
-NEW_KINDS = ("layernorm", "layernorm_f32out", "geglu", "quick_gelu", "attention_causal", "clip_embed", "resample",
-             "nchw_to_nhwc_pad", "vae_latent_in", "vae_image_out", "conv2d")
+# families one library alone reaches: the 2^10 gradient scale is the fp16 classifier's; adm_vae_image_out, the vector kernels of
+# the classifier heads and the loss gradient are fp32 kernels that ops launches from the bf16 library whatever the torso
+ONE_LIBRARY_FAMILIES = {"out_mode 1 + out_scale": "f16", "vae_image_out": "bf16", "vec_act": "bf16", "vec_gn": "bf16",
+                        "vec_gn_bwd": "bf16", "logsoftmax_grad": "bf16"}
+TOKEN_KINDS = ("layernorm", "layernorm_f32out", "geglu", "quick_gelu", "attention_causal", "clip_embed", "resample",
+               "nchw_to_nhwc_pad", "vae_latent_in", "vae_image_out", "conv2d")
+# the classifier heads: the attention pool (every shipped classifier), the adaptive / spatial / spatial_v2 heads, the loss gradient
+HEAD_KINDS = ("pool_prep", "pool_attn_fwd", "pool_attn_bwd", "pool_prep_bwd", "channel_mean", "bcast_add", "vec_act", "vec_gn",
+              "vec_gn_bwd", "logsoftmax_grad")
+NEW_KINDS = TOKEN_KINDS + HEAD_KINDS
+REQUIRED_FAMILIES += list(HEAD_KINDS)
 REPLAYED = {"conv", "attention", "attention_cross", "attention_bwd", "gn_bwd", "gn_affine"} | set(NEW_KINDS)
 
 
@@ -789,3 +890,216 @@ def worst_ratio(got, ref, bound):
     idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(j), r.shape))
     rep = f"index {idx}: got {got.double().flatten()[j].item():.8g} ref {ref.flatten()[j].item():.8g} bound {bound.expand_as(r).flatten()[j].item():.4g}"
     return r.flatten()[j].item(), (err ** 2).sum().item(), (ref ** 2).sum().item(), rep
+
+
+# ------------------------------------------------------------------ classifier heads and gradient helpers
+F32_MIN = 2.0 ** -126   # below fp32's normal range a result may be flushed or lose bits: an absolute floor, not a tolerance
+E24 = 2.0 ** -24
+
+
+def f32c(x: float) -> float:
+    """The fp32 value a C `float` argument receives."""
+    return float(torch.tensor(x, dtype=torch.float32))
+
+
+def silu_terms(h, a, b):
+    """float64 s = SiLU(a h + b) of T values h through the fp32 affine (a, b) and the error of the kernels' adm_silu."""
+    ah = a.double() * h.double()
+    z = ah + b.double()
+    s = z * torch.sigmoid(z)
+    return s, 2.0 ** -23 * (ah.abs() + b.double().abs()) + SILU_REL * (1 + z.abs()) * s.abs()
+
+
+def pool_prep_restate(h, a, b, pos, tpad: int, dtype):
+    """h [n, hw, c] of T, a / b fp32 [n, c], pos fp32 [c, hw + 1] -> (ref, bound) [n, hw + 1, c]; rows hw + 1 .. tpad are zero."""
+    n, hw, c = h.shape
+    s, e = silu_terms(h, a[:, None, :], b[:, None, :])
+    p = pos.double().t()                                                   # [T, c]
+    m = s.mean(1, keepdim=True)
+    ref = torch.cat([m + p[None, :1], s + p[None, 1:]], 1)
+    b0 = (e.mean(1, keepdim=True) + (hw + 2) * E24 * s.abs().mean(1, keepdim=True) + SILU_REL * m.abs()
+          + E24 * (m.abs() + p[None, :1].abs()))
+    b1 = e + E24 * (s.abs() + p[None, 1:].abs())
+    return ref, half_ulp(ref, dtype) + torch.cat([b0, b1], 1)
+
+
+def pool_split(qkv, t: int, heads: int):
+    """qkv [n, tpad, 3 C] ([q | k | v], heads inside each) -> q0 [n, H, d], k / v [n, H, t, d] in float64."""
+    n, _, c3 = qkv.shape
+    c = c3 // 3
+    d = c // heads
+    x = qkv[:, :t].double().reshape(n, t, 3, heads, d)
+    return x[:, 0, 0], x[:, :, 1].permute(0, 2, 1, 3), x[:, :, 2].permute(0, 2, 1, 3)
+
+
+POOL_C1, POOL_C2 = 4, 1
+
+
+def pool_attn_fwd_restate(qkv, t: int, heads: int):
+    """Attention of token 0 over the first t rows -> ((wts [n, H, t], a0 [n, C]), (bound_w, bound_a))."""
+    q0, k, v = pool_split(qkv, t, heads)
+    n, _, d = q0.shape
+    scale = d ** -0.5
+    s = torch.einsum("nhd,nhtd->nht", q0, k) * scale
+    ds = (d + POOL_C1) * E24 * torch.einsum("nhd,nhtd->nht", q0.abs(), k.abs()) * scale
+    w = torch.softmax(s, -1)
+    span = s.amax(-1, keepdim=True) - s
+    rel = (2 * ds.amax(-1, keepdim=True) + E24 * (span + (w * span).sum(-1, keepdim=True)) + 3 * SILU_REL
+           + ((t + 63) // 64 + 7) * E24)
+    bw = rel * w + F32_MIN
+    a0 = torch.einsum("nht,nhtd->nhd", w, v)
+    ba = torch.einsum("nht,nhtd->nhd", bw, v.abs()) + (t + POOL_C2) * E24 * torch.einsum("nht,nhtd->nhd", w, v.abs())
+    return (w, a0.reshape(n, heads * d)), (bw, ba.reshape(n, heads * d))
+
+
+def pool_attn_bwd_restate(qkv, wts, da0, t: int, heads: int, dtype):
+    """Backward of the above with the stored weights wts [n, H, tpad] and da0 fp32 [n, C] -> (ref, bound) [n, t, 3 C]: dQ on
+    row 0 only (the rows above are zero), dK, dV on the rows < t."""
+    q0, k, v = pool_split(qkv, t, heads)
+    n, _, d = q0.shape
+    scale = d ** -0.5
+    w = wts[:, :, :t].double()
+    da = da0.double().reshape(n, heads, d)
+    dw = torch.einsum("nhd,nhtd->nht", da, v)
+    e_dw = (d + 1) * E24 * torch.einsum("nhd,nhtd->nht", da.abs(), v.abs())
+    delta = (w * dw).sum(-1, keepdim=True)
+    e_delta = (w * e_dw).sum(-1, keepdim=True) + ((t + 63) // 64 + 7) * E24 * (w * dw.abs()).sum(-1, keepdim=True)
+    dlg = w * (dw - delta) * scale
+    e_dlg = w * scale * (e_dw + e_delta + 5 * E24 * (dw.abs() + delta.abs()))
+    dk = dlg[..., None] * q0[:, :, None, :]
+    bk = e_dlg[..., None] * q0.abs()[:, :, None, :] + E24 * dk.abs()
+    dv = w[..., None] * da[:, :, None, :]
+    bv = E24 * dv.abs()
+    dq = torch.zeros_like(dk)
+    bq = torch.zeros_like(dk)
+    dq[:, :, 0] = torch.einsum("nht,nhtd->nhd", dlg, k)
+    bq[:, :, 0] = (torch.einsum("nht,nhtd->nhd", e_dlg, k.abs())
+                   + (t + 1) * E24 * torch.einsum("nht,nhtd->nhd", dlg.abs(), k.abs()))
+    ref = torch.stack([dq, dk, dv], 1)                                     # [n, 3, H, t, d]
+    bound = torch.stack([bq, bk, bv], 1)
+    ref = ref.permute(0, 3, 1, 2, 4).reshape(n, t, 3 * heads * d)
+    bound = bound.permute(0, 3, 1, 2, 4).reshape(n, t, 3 * heads * d)
+    return ref, half_ulp(ref, dtype) + bound
+
+
+def pool_prep_bwd_restate(dtok, hw: int, dtype):
+    """dtok [n, tpad, c] of T -> d_act [n, hw, c] = dtok[:, 1 + p] + dtok[:, 0] / hw."""
+    x = dtok.double()
+    m = x[:, :1] / hw
+    ref = x[:, 1:hw + 1] + m
+    return ref, half_ulp(ref, dtype) + SILU_REL * m.abs() + E24 * (x[:, 1:hw + 1].abs() + m.abs())
+
+
+def channel_mean_restate(h, aff):
+    """h [n, hw, c] of T; aff = (a, b) fp32 [n, c] or None -> fp32 mean over the pixels (ref, bound) [n, c]."""
+    hw = h.shape[1]
+    if aff is None:
+        v, e = h.double(), None
+    else:
+        v, e = silu_terms(h, aff[0][:, None, :], aff[1][:, None, :])
+    ref = v.mean(1)
+    bound = ((hw + 3) // 4 + 3) * E24 * v.abs().mean(1) + SILU_REL * ref.abs() + F32_MIN
+    return ref, (bound if e is None else bound + e.mean(1))
+
+
+def bcast_add_restate(v, scale: float, add, hw: int, dtype):
+    """v fp32 [n, c] (the column window), add [n, hw, c] of T or None -> (ref, bound) [n, hw, c]; bound None without add: the
+    result is round_T of the fp32 product, compared bitwise."""
+    if add is None:
+        return (v.float() * torch.tensor(scale, dtype=torch.float32)).to(dtype)[:, None, :].expand(-1, hw, -1).contiguous(), None
+    vs = v.double()[:, None, :] * f32c(scale)
+    ref = add.double() + vs
+    return ref, half_ulp(ref, dtype) + E24 * (2 * vs.abs() + add.double().abs())
+
+
+VEC_ACT_MODES = {"silu": 1, "relu": 2}
+
+
+def vec_act_restate(x, mode: int, dy=None):
+    """fp32 x (and dy): act(x) or dy act'(x) -> (ref, bound); ReLU is exact (bound None: equal as values), ReLU'(0) = 0."""
+    z = x.double()
+    if mode == 2:
+        return (torch.clamp(z, min=0.0) if dy is None else dy.double() * (z > 0).double()), None
+    s = torch.sigmoid(z)
+    if dy is None:
+        ref = z * s
+        return ref, SILU_REL * ref.abs() + F32_MIN
+    ref = dy.double() * s * (1 + z * (1 - s))
+    return ref, SILU_REL * dy.double().abs() * s * (1 + z.abs()) + F32_MIN
+
+
+def _vec_k(c: int) -> float:
+    cpg = c // 32
+    return ((cpg + 7) // 8 + 3) * E24     # a lane's adds and the three butterfly steps
+
+
+def vec_gn_restate(x, gamma, beta, eps: float):
+    """GroupNorm32 of fp32 rows x [n, c] -> ((y, mean [n, 32], rstd), (bound_y, bound_mean, bound_rstd))."""
+    n, c = x.shape
+    cpg = c // 32
+    k = _vec_k(c)
+    g = x.double().reshape(n, 32, cpg)
+    mean = g.mean(-1, keepdim=True)
+    e_m = k * g.abs().mean(-1, keepdim=True) + SILU_REL * mean.abs()
+    d = g - mean
+    var = (d * d).mean(-1, keepdim=True)
+    e_v = 2 * d.abs().mean(-1, keepdim=True) * e_m + e_m * e_m + (k + 4 * E24 + SILU_REL) * var
+    eps = f32c(eps)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    rel_r = e_v / (2 * (var + eps)) + E24 + 2 * SILU_REL
+    gm, bt = gamma.double().reshape(1, 32, cpg), beta.double().reshape(1, 32, cpg)
+    yg = gm * d * rstd
+    y = yg + bt
+    by = gm.abs() * rstd * e_m + yg.abs() * (rel_r + 4 * E24) + E24 * y.abs() + F32_MIN
+    return (y.reshape(n, c), mean[..., 0], rstd[..., 0]), (by.reshape(n, c), (e_m + F32_MIN)[..., 0], (rstd * rel_r)[..., 0])
+
+
+def vec_gn_bwd_restate(x, gamma, stats, dz):
+    """dx = rstd (g - mean_g(g) - xhat mean_g(g xhat)), g = gamma dz, xhat = (x - mean) rstd with the stored stats [n, 32, 2]."""
+    n, c = x.shape
+    cpg = c // 32
+    k = _vec_k(c)
+    mean, rstd = stats[..., :1].double(), stats[..., 1:].double()
+    g = (gamma.double()[None] * dz.double()).reshape(n, 32, cpg)
+    xh = (x.double().reshape(n, 32, cpg) - mean) * rstd
+    s1, s2 = g.mean(-1, keepdim=True), (g * xh).mean(-1, keepdim=True)
+    e1 = (k + E24) * g.abs().mean(-1, keepdim=True) + SILU_REL * s1.abs()
+    e2 = (k + 4 * E24) * (g * xh).abs().mean(-1, keepdim=True) + SILU_REL * s2.abs()
+    ref = rstd * (g - s1 - xh * s2)
+    bound = rstd * (e1 + xh.abs() * e2 + 4 * E24 * (g.abs() + s1.abs() + (xh * s2).abs())) + E24 * ref.abs() + F32_MIN
+    return ref.reshape(n, c), bound.reshape(n, c)
+
+
+def logsoftmax_grad_restate(logits, y, scale: float):
+    """scale (onehot(y) - softmax(logits)) and log_softmax[n, y_n] -> ((dl [n, k], logp [n]), (bound_dl, bound_logp))."""
+    n, k = logits.shape
+    l = logits.double()
+    sc = f32c(scale)
+    lsm = torch.log_softmax(l, -1)
+    sm = lsm.exp()
+    one = torch.zeros_like(sm)
+    one[torch.arange(n, device=l.device), y] = 1.0
+    dist = l.amax(-1, keepdim=True) - l
+    tree = ((k + 255) // 256 + 8) * E24
+    rel = E24 * dist + 3 * SILU_REL + tree + (sm * dist).sum(-1, keepdim=True) * E24
+    ref = sc * (one - sm)
+    bound = abs(sc) * (rel * sm + F32_MIN) + 2 * E24 * ref.abs()
+    logp = lsm[torch.arange(n, device=l.device), y]
+    dy = dist[torch.arange(n, device=l.device), y]
+    logsum = torch.logsumexp(l - l.amax(-1, keepdim=True), -1)
+    bl = E24 * dy + SILU_REL * (1 + logsum.abs()) + tree + (sm * dist).sum(-1) * E24 + 2 * E24 * logp.abs() + F32_MIN
+    return (ref, logp), (bound, bl)
+
+
+def grad_add_restate(a, b, b_half: bool, dtype):
+    """a [n, h, w, c], b the same or [n, h/2, w/2, c] read through the nearest 2x upsample times 1/4 -> (ref, bound)."""
+    n, h, w, c = a.shape
+    sb = _half_up(b.double(), h, w) if b_half else b.double()
+    ref = a.double() + sb
+    return ref, half_ulp(ref, dtype) + E24 * (a.double().abs() + sb.abs())
+
+
+def pool_zero_rows_ok(dqkv, t: int) -> bool:
+    """adm_pool_attn_bwd's zeros: the rows >= t, and the dQ columns of the rows 1 .. t, hold only zero bit patterns."""
+    c = dqkv.shape[2] // 3
+    return not bool(dqkv[:, t:].contiguous().view(torch.int16).any()) and not bool(dqkv[:, 1:t, :c].contiguous().view(torch.int16).any())

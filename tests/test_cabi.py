@@ -68,6 +68,18 @@ def test_conv_rejects_out_scale_without_the_fp32_output(kind):
     assert b"out_scale" in lib.adm_last_error() and b"out_mode" in lib.adm_last_error()
 
 
+@pytest.mark.parametrize("kind", ["bf16", "f16"])
+def test_grad_add_rejects_an_odd_size_at_half_resolution(kind):
+    """With b_half the kernel reads b[y / 2, x / 2] of an [h / 2, w / 2] operand: an odd h or w indexes past its end, so the
+    library refuses it before the launch.  The placeholder pointers are unaligned on purpose: should the odd-size check ever go,
+    the alignment check that follows still refuses the call before anything launches."""
+    lib = _lib.load(kind)
+    for h, w in ((5, 8), (8, 7)):
+        assert lib.adm_grad_add(0x1008, 0x1008, 0x1008, 1, h, w, 8, 1, None) != 0
+        assert b"adm_grad_add: odd size" in lib.adm_last_error()
+    assert lib.adm_grad_add(0x1008, 0x1008, 0x1008, 1, 8, 8, 8, 1, None) != 0 and b"unaligned" in lib.adm_last_error()
+
+
 def test_header_is_plain_c_and_links_from_a_c_client(tmp_path):
     """include/adm_hip.h compiles as C99 (-pedantic: no C++isms, no torch types) and a C program links against the library."""
     import shutil

@@ -145,6 +145,17 @@ def test_stem_conv(ops):
     assert_close_bf16(got, F.conv2d(x, w, b, padding=1), "stem")
 
 
+def test_stem_conv_lds_limit(ops):
+    """The weights and the bias sit in (cin 9 + 1) cout 4 bytes of dynamic LDS and the kernel does not opt in above 64 KB: cin 3 with
+    cout 512 (55 KB) runs, cin 8 with cout 512 (149 KB) is refused before the launch."""
+    from autodiffusion_amd._lib import AdmError
+    x, w, b = rnd((2, 3, 16, 16), 4), rnd((512, 3, 3, 3), 5, 0.2), rnd((512,), 6, 0.1)
+    got = nchw_cpu(ops.stem_conv3x3(x.to(DEV), w.to(DEV), b.to(DEV)))
+    assert_close_bf16(got, F.conv2d(x, w, b, padding=1), "stem cout 512")
+    with pytest.raises(AdmError, match="LDS"):
+        ops.stem_conv3x3(rnd((1, 8, 8, 8), 7).to(DEV), rnd((512, 8, 3, 3), 8, 0.2).to(DEV), b.to(DEV))
+
+
 @pytest.mark.parametrize("c0,c1,hw", [(64, 0, 8), (192, 0, 64), (768, 576, 8), (32, 32, 16), (1536, 0, 8)])
 def test_gn_affine_matches_group_norm(ops, c0, c1, hw):
     n = 3

@@ -2,7 +2,8 @@
 
 The models (built as tests/test_hip_fullsize.py, tests/test_hip_sd_vae.py and tests/test_hip_clip.py build them; the weights'
 values do not matter, only the launch list does) run eagerly at the batches bench.py uses and at batch 1-2, in the bf16 and the
-fp16 torso, under tests/launch_replay.Recorder: ADM-64 / 128 / 256, the classifiers, the SD latent UNet, the KL-f8 VAE decoder
+fp16 torso, under tests/launch_replay.Recorder: ADM-64 / 128 / 256, the classifiers (the shipped attention-pool ones, and the
+adaptive / spatial / spatial_v2 heads at width 64), the SD latent UNet, the KL-f8 VAE decoder
 (with the image exit that follows it) and the CLIP text encoder.  Each distinct record is then launched again through the same
 entry point with fresh seeded operands and compared element by element with the float64 restatement of tests/launch_replay.py,
 within the per-element bounds derived there (and tested on the host by tests/test_launch_replay_host.py).  Large conv maps are
@@ -10,7 +11,9 @@ compared at the corners of every 16x16 (8x8) output tile of every image plus see
 guard fails if a family of launches the models are known to reach is missing, if a launch symbol the models called has no entry
 in launch_replay.SYMBOL_COVERAGE, or if a symbol mapped to a record kind left no record of that kind.
 
-Also here: GroupNorm statistics and LayerNorm at a large |mean| / std, and the causal attention at the tile edges of its schedule.
+Also here: GroupNorm statistics and LayerNorm at a large |mean| / std, the causal attention at the tile edges of its schedule,
+and the classifier heads' kernels, the loss gradient and adm_grad_add at the smallest shapes that can still go wrong, each launched
+through the library symbol on NaN-filled outputs with a guard block behind them.
 """
 import ctypes as C
 import time
@@ -95,6 +98,22 @@ def _run_models(torso):
     _run_vae_and_clip(torso)
 
 
+def _run_pool_head_classifiers(torso):
+    """The adaptive, spatial and spatial_v2 heads (csrc/adm_clfhead.hip) at the smallest plan of tests/test_variants.py: width 64,
+    a 64x64 input, batch 2."""
+    from helpers import filled
+    from test_variants import clf_plan_of
+    from autodiffusion_amd.classifier import EncoderUNetModel
+    for tag in ("adaptive_noss_convres", "spatial", "spatialv2_noss"):
+        plan = clf_plan_of(tag)
+        c = EncoderUNetModel(plan)
+        c.load_state_dict({k: torch.from_numpy(v) for k, v in filled(plan).items()})
+        c.to(DEV).eval().set_torso(torso)
+        c.log_prob_grad(*_inputs(64, 2, True, 8), 1.0)
+        del c
+    torch.cuda.empty_cache()
+
+
 _FILLS = {}   # host fills of the VAE / CLIP state dicts, shared by the two torsos and dropped by the fixture
 TINY_CLIP_256 = dict(vocab_size=512, hidden_size=128, intermediate_size=256, num_hidden_layers=1, num_attention_heads=2,
                      max_position_embeddings=256)
@@ -137,13 +156,20 @@ def _run_vae_and_clip(torso):
 @pytest.fixture(scope="module")
 def recorded(ops):
     t0 = time.time()
+    heads_s = 0.0
     with pytest.MonkeyPatch.context() as mp:
         rec = lr.Recorder(mp)
         for torso in ("bf16", "fp16"):
             _run_models(torso)
+            torch.cuda.synchronize()
+            t1 = time.time()
+            _run_pool_head_classifiers(torso)
+            torch.cuda.synchronize()
+            heads_s += time.time() - t1
     _FILLS.clear()
     torch.cuda.synchronize()
-    print(f"\nrecorded {sum(rec.counts.values())} calls ({rec.counts}), {len(rec.records)} distinct, in {time.time() - t0:.0f} s")
+    print(f"\nrecorded {sum(rec.counts.values())} calls ({rec.counts}), {len(rec.records)} distinct, in {time.time() - t0:.0f} s "
+          f"({heads_s:.1f} s of it the adaptive / spatial / spatial_v2 classifiers)")
     return rec
 
 
@@ -867,3 +893,415 @@ def test_attention_causal_at_tile_edges(ops, t, dtype):
     u = lr.U[dtype]
     print(f"attention_causal T {t} {dtype}: worst err/bound {worst:.3f}, fro/u {fro / u:.3f}")
     assert worst <= 1.0 and fro <= lr.fro_bound(2, u), (worst, fro / u, report)
+
+
+# ------------------------------------------------------------------ classifier heads, loss gradient, gradient add
+GUARD = 4096
+
+
+def _owned(shape, dtype, fill=float("nan")):
+    """A test-owned output: `shape` elements of NaN (every one must be written) and GUARD sentinel elements behind them."""
+    numel = 1
+    for s_ in shape:
+        numel *= s_
+    buf = torch.full((numel + GUARD,), fill, dtype=dtype, device=DEV)
+    buf[numel:] = SENTINEL
+    return buf, buf[:numel].view(shape)
+
+
+def _guard_ok(buf, what):
+    assert bool((buf[-GUARD:] == SENTINEL).all()), f"{what}: the guard behind the output was written"
+
+
+def _call(kind, name, *args):
+    from autodiffusion_amd import _lib
+    _lib.check(getattr(_lib.load(kind), name)(*args, torch.cuda.current_stream().cuda_stream), name + " (replay)")
+    torch.cuda.synchronize()
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _fro(e2, r2):
+    return (e2 / r2) ** 0.5 if r2 > 0 else None
+
+
+def _affine(n, c):
+    return 1 + 0.2 * torch.randn(n, c, device=DEV), 0.2 * torch.randn(n, c, device=DEV)
+
+
+def _check_pool_prep(n, hw, c, tpad, T):
+    h = torch.randn(n, hw, c, device=DEV).to(T)
+    a, b = _affine(n, c)
+    t = hw + 1
+    pos = torch.randn(c, t, device=DEV) * c ** -0.5 + 0.01 * torch.arange(c * t, device=DEV).reshape(c, t) / (c * t)   # distinct
+    buf, tok = _owned((n, tpad, c), T)
+    _call(lr.KIND_OF_DTYPE[T], "adm_pool_prep", _p(h), _p(a), _p(b), _p(pos), _p(buf), n, hw, c, tpad)
+    _guard_ok(buf, "adm_pool_prep")
+    ref, bound = lr.pool_prep_restate(h, a, b, pos, tpad, T)
+    w, e2, r2, rep = lr.worst_ratio(tok[:, :t], ref, bound)
+    if bool(tok[:, t:].contiguous().view(torch.int16).any()):
+        return float("inf"), None, "a pad row of tok is not zero"
+    return w, _fro(e2, r2), rep
+
+
+def _pool_qkv(n, t, tpad, heads, d, T, qk=1.0):
+    qkv = torch.full((n, tpad, 3 * heads * d), float("nan"), device=DEV)   # the rows >= t are never read
+    qkv[:, :t] = torch.randn(n, t, 3 * heads * d, device=DEV)
+    qkv[:, :t, :2 * heads * d] *= qk
+    return qkv.to(T)
+
+
+def _launch_pool_fwd(qkv, t, heads):
+    n, tpad, c3 = qkv.shape
+    c = c3 // 3
+    ba, a0 = _owned((n, c), torch.float32)
+    bw, wts = _owned((n, heads, tpad), torch.float32)
+    _call(lr.kind_of(qkv), "adm_pool_attn_fwd", _p(qkv), _p(ba), _p(bw), n, t, tpad, heads, c // heads)
+    _guard_ok(ba, "adm_pool_attn_fwd a0")
+    _guard_ok(bw, "adm_pool_attn_fwd wts")
+    return a0, wts
+
+
+def _check_pool_attn_fwd(n, t, tpad, heads, d, T, qk=1.0):
+    qkv = _pool_qkv(n, t, tpad, heads, d, T, qk)
+    a0, wts = _launch_pool_fwd(qkv, t, heads)
+    (w, a), (bw, ba) = lr.pool_attn_fwd_restate(qkv, t, heads)
+    r1, _, _, rep1 = lr.worst_ratio(wts[..., :t], w, bw)
+    r2, _, _, rep2 = lr.worst_ratio(a0, a, ba)
+    if bool(wts[..., t:].contiguous().view(torch.int32).any()):
+        return float("inf"), None, "wts[t:tpad] is not zero"
+    one = ((wts[..., :t].double().sum(-1) - 1).abs() / bw.sum(-1)).max().item()     # the weights sum to 1 within their bounds
+    q, k, _ = lr.pool_split(qkv, t, heads)
+    s = torch.einsum("nhd,nhtd->nht", q, k) * d ** -0.5
+    print(f"  pool_attn_fwd logits {s.min().item():.1f} .. {s.max().item():.1f}: weights {r1:.3f}, a0 {r2:.3f}, |sum - 1| {one:.3f} of the bound")
+    return max(r1, r2, one), None, f"weights {rep1}; a0 {rep2}"
+
+
+def _check_pool_attn_bwd(n, t, tpad, heads, d, T, mag):
+    qkv = _pool_qkv(n, t, tpad, heads, d, T)
+    _, wts = _launch_pool_fwd(qkv, t, heads)
+    c = heads * d
+    da0 = torch.randn(n, c, device=DEV) * mag
+    buf, dqkv = _owned((n, tpad, 3 * c), T)
+    _call(lr.kind_of(qkv), "adm_pool_attn_bwd", _p(qkv), _p(wts), _p(da0), _p(buf), n, t, tpad, heads, d)
+    _guard_ok(buf, "adm_pool_attn_bwd")
+    ref, bound = lr.pool_attn_bwd_restate(qkv, wts, da0, t, heads, T)
+    w, _, _, rep = lr.worst_ratio(dqkv[:, :t], ref, bound)
+    if not lr.pool_zero_rows_ok(dqkv, t):
+        return float("inf"), None, "a pad row or a dQ row above token 0 is not zero"
+    under = float(((dqkv[:, :t, c:2 * c] == 0) & (ref[:, :, c:2 * c] != 0)).float().mean())
+    print(f"  pool_attn_bwd {T} |da0| {mag:g}: dK elements flushed to zero {under:.2%}")
+    if t == 1 and not bool((dqkv[:, 0, :2 * c] == 0).all()):
+        return float("inf"), None, "a single key: dQ and dK must be zero"
+    return w, None, rep
+
+
+def _check_pool_prep_bwd(n, hw, c, tpad, T):
+    dtok = torch.full((n, tpad, c), float("nan"), device=DEV)               # the rows above hw are never read
+    dtok[:, :hw + 1] = torch.randn(n, hw + 1, c, device=DEV)
+    dtok = dtok.to(T)
+    buf, dact = _owned((n, hw, c), T)
+    _call(lr.KIND_OF_DTYPE[T], "adm_pool_prep_bwd", _p(dtok), _p(buf), n, hw, c, tpad)
+    _guard_ok(buf, "adm_pool_prep_bwd")
+    ref, bound = lr.pool_prep_bwd_restate(dtok, hw, T)
+    w, e2, r2, rep = lr.worst_ratio(dact, ref, bound)
+    return w, _fro(e2, r2), rep
+
+
+def _check_channel_mean(n, hw, c, affine, col, cols, T):
+    h = torch.randn(n, hw, c, device=DEV).to(T)
+    aff = _affine(n, c) if affine else None
+    buf, out = _owned((n, cols), torch.float32, SENTINEL)
+    out[:, col:col + c] = float("nan")
+    _call(lr.KIND_OF_DTYPE[T], "adm_channel_mean", _p(h), _p(aff[0]) if affine else None, _p(aff[1]) if affine else None,
+          buf.data_ptr() + 4 * col, cols, n, hw, c)
+    _guard_ok(buf, "adm_channel_mean")
+    if not (bool((out[:, :col] == SENTINEL).all()) and bool((out[:, col + c:] == SENTINEL).all())):
+        return float("inf"), None, "a column outside the window was written"
+    ref, bound = lr.channel_mean_restate(h, aff)
+    w, _, _, rep = lr.worst_ratio(out[:, col:col + c], ref, bound)
+    return w, None, rep
+
+
+def _check_bcast_add(n, hw, c, with_add, col, vcols, T):
+    v = torch.randn(n, vcols, device=DEV)
+    scale = 1.0 / hw
+    add = torch.randn(n, hw, c, device=DEV).to(T) if with_add else None
+    buf, out = _owned((n, hw, c), T)
+    _call(lr.KIND_OF_DTYPE[T], "adm_bcast_add", v.data_ptr() + 4 * col, vcols, scale, _p(add), _p(buf), n, hw, c)
+    _guard_ok(buf, "adm_bcast_add")
+    ref, bound = lr.bcast_add_restate(v[:, col:col + c], scale, add, hw, T)
+    if bound is None:
+        w, rep = _bitwise(out, ref, "bcast_add without add")
+        return w, None, rep
+    w, e2, r2, rep = lr.worst_ratio(out, ref, bound)
+    return w, _fro(e2, r2), rep
+
+
+VEC_SPECIALS = (0.0, -0.0, 88.0, -88.0, 104.0, -104.0, 1e-3, -1.2784645)
+
+
+def _check_vec_act(items, mode, backward):
+    x = torch.randn(items, device=DEV) * 3
+    k = min(items, len(VEC_SPECIALS))
+    x[:k] = torch.tensor(VEC_SPECIALS[:k], device=DEV)
+    dy = torch.randn(items, device=DEV) if backward else None
+    buf, out = _owned((items,), torch.float32)
+    _call("bf16", "adm_vec_act", _p(x), _p(dy), _p(buf), items, mode)
+    _guard_ok(buf, "adm_vec_act")
+    if bool(torch.isnan(out).any()):
+        return float("inf"), None, "NaN in the output"
+    ref, bound = lr.vec_act_restate(x, mode, dy)
+    if bound is None:   # ReLU: equal as values, ReLU'(0) = 0
+        bad = out.double() != ref
+        return (float("inf"), None, f"{int(bad.sum())} elements differ") if bool(bad.any()) else (0.0, None, "")
+    w, _, _, rep = lr.worst_ratio(out, ref, bound)
+    return w, None, rep
+
+
+def _vec_rows(n, c, offset=0.0, std=1.0):
+    return torch.randn(n, c, device=DEV) * std + offset, 1 + 0.2 * torch.randn(c, device=DEV), 0.1 * torch.randn(c, device=DEV)
+
+
+def _launch_vec_gn(x, gamma, beta, eps):
+    n, c = x.shape
+    by, y = _owned((n, c), torch.float32)
+    bs, st = _owned((n, 32, 2), torch.float32)
+    _call("bf16", "adm_vec_gn", _p(x), _p(gamma), _p(beta), _p(by), _p(bs), n, c, eps)
+    _guard_ok(by, "adm_vec_gn y")
+    _guard_ok(bs, "adm_vec_gn stats")
+    return y, st
+
+
+def _check_vec_gn(n, c, eps, offset=0.0, std=1.0):
+    x, gamma, beta = _vec_rows(n, c, offset, std)
+    y, st = _launch_vec_gn(x, gamma, beta, eps)
+    (ry, rm, rr), (by, bm, br) = lr.vec_gn_restate(x, gamma, beta, eps)
+    res = [lr.worst_ratio(g, r, b) for g, r, b in ((y, ry, by), (st[..., 0], rm, bm), (st[..., 1], rr, br))]
+    if c == 32 and not torch.equal(y, beta[None].expand(n, -1)):
+        return float("inf"), None, "one value per group: y must be beta exactly"
+    return max(r[0] for r in res), None, "; ".join(r[3] for r in res)
+
+
+def _check_vec_gn_bwd(n, c, offset=0.0, std=1.0):
+    x, gamma, beta = _vec_rows(n, c, offset, std)
+    _, st = _launch_vec_gn(x, gamma, beta, 1e-5)
+    dz = torch.randn(n, c, device=DEV)
+    buf, dx = _owned((n, c), torch.float32)
+    _call("bf16", "adm_vec_gn_bwd", _p(x), _p(gamma), _p(st), _p(dz), _p(buf), n, c)
+    _guard_ok(buf, "adm_vec_gn_bwd")
+    ref, bound = lr.vec_gn_bwd_restate(x, gamma, st, dz)
+    if c == 32 and not bool((dx == 0).all()):
+        return float("inf"), None, "one value per group: dx must be zero exactly"
+    w, _, _, rep = lr.worst_ratio(dx, ref, bound)
+    return w, None, rep
+
+
+def _check_logsoftmax_grad(n, k, scale, spread=False):
+    logits = torch.randn(n, k, device=DEV) * 3
+    if spread and k > 1:
+        logits[-1] = torch.linspace(-1e4, 1e4, k, device=DEV)[torch.randperm(k, device=DEV)]
+    y = torch.randint(0, k, (n,), device=DEV)
+    y[0], y[-1] = 0, k - 1
+    bd, dl = _owned((n, k), torch.float32)
+    bl, lp = _owned((n,), torch.float32)
+    _call("bf16", "adm_logsoftmax_grad", _p(logits), _p(y), _p(bd), _p(bl), n, k, scale)
+    _guard_ok(bd, "adm_logsoftmax_grad dlogits")
+    _guard_ok(bl, "adm_logsoftmax_grad logp_sel")
+    (rd, rl), (bnd, bnl) = lr.logsoftmax_grad_restate(logits, y, scale)
+    torch.testing.assert_close(rl, torch.log_softmax(logits.double(), -1)[torch.arange(n, device=DEV), y], rtol=1e-12, atol=1e-12)
+    w1, _, _, rep1 = lr.worst_ratio(dl, rd, bnd)
+    w2, _, _, rep2 = lr.worst_ratio(lp, rl, bnl)
+    return max(w1, w2), None, f"dlogits {rep1}; logp_sel {rep2}"
+
+
+def _replay_head(name, recorded, check, roundings=1):
+    def replay(rec, T, seed):
+        return check(*rec[2:], T) if name in ("pool_prep", "pool_attn_fwd", "pool_prep_bwd", "channel_mean", "bcast_add") else check(*rec[2:])
+    _replay_kind(name, recorded, replay, roundings)
+
+
+def test_pool_prep_launches_match_float64(ops, recorded):
+    _replay_head("pool_prep", recorded, _check_pool_prep)
+
+
+def test_pool_attn_fwd_launches_match_float64(ops, recorded):
+    _replay_head("pool_attn_fwd", recorded, _check_pool_attn_fwd)
+
+
+def test_pool_attn_bwd_launches_match_float64(ops, recorded):
+    def replay(rec, T, seed):   # d a0 of the unscaled bf16 network is ~ 1e-3; the fp16 classifier carries it times 2^10
+        return _check_pool_attn_bwd(*rec[2:], T, 1e-3 * (1024 if T == torch.float16 else 1))
+    _replay_kind("pool_attn_bwd", recorded, replay)
+
+
+def test_pool_prep_bwd_launches_match_float64(ops, recorded):
+    _replay_head("pool_prep_bwd", recorded, _check_pool_prep_bwd)
+
+
+def test_channel_mean_launches_match_float64(ops, recorded):
+    _replay_head("channel_mean", recorded, _check_channel_mean)
+
+
+def test_bcast_add_launches_match_float64(ops, recorded):
+    _replay_head("bcast_add", recorded, _check_bcast_add)
+
+
+def test_vec_act_launches_match_float64(ops, recorded):
+    _replay_head("vec_act", recorded, _check_vec_act)
+
+
+def test_vec_gn_launches_match_float64(ops, recorded):
+    _replay_head("vec_gn", recorded, _check_vec_gn)
+
+
+def test_vec_gn_bwd_launches_match_float64(ops, recorded):
+    _replay_head("vec_gn_bwd", recorded, _check_vec_gn_bwd)
+
+
+def test_logsoftmax_grad_launches_match_float64(ops, recorded):
+    _replay_head("logsoftmax_grad", recorded, _check_logsoftmax_grad)
+
+
+# ------------------------------------------------------------------ the same kernels at the smallest shapes that can still go wrong
+TORSOS = [torch.bfloat16, torch.float16]
+
+
+def _edge(what, res, T=None, roundings=1):
+    worst, fro, report = res
+    u = lr.U[T] if T is not None else None
+    print(f"{what}: worst err/bound {worst:.3f}" + ("" if fro is None or u is None else f", fro/u {fro / u:.3f}"))
+    assert worst <= 1.0, (what, worst, report)
+    if fro is not None and u is not None:
+        assert fro <= lr.fro_bound(roundings, u), (what, fro / u)
+
+
+POOL_PREP_SHAPES = [(2, 64, 256, 128), (1, 64, 512, 128), (3, 1, 8, 2), (2, 9, 72, 16), (1, 16, 264, 17)]
+
+
+@pytest.mark.parametrize("dtype", TORSOS)
+@pytest.mark.parametrize("n,hw,c,tpad", POOL_PREP_SHAPES)
+def test_pool_prep_at_edges(ops, n, hw, c, tpad, dtype):
+    """The channel loop's second trip (c > 256), one pixel, an odd map, no pad row; pos distinct per (channel, token)."""
+    torch.manual_seed(200 + hw + c)
+    _edge(f"pool_prep {(n, hw, c, tpad)} {dtype}", _check_pool_prep(n, hw, c, tpad, dtype), dtype)
+
+
+POOL_ATTN_SHAPES = [(2, 4, 64, 65, 128), (1, 8, 64, 65, 128), (3, 1, 32, 1, 64), (2, 2, 64, 64, 64), (1, 3, 32, 130, 192), (2, 1, 8, 17, 24)]
+
+
+@pytest.mark.parametrize("dtype", TORSOS)
+@pytest.mark.parametrize("n,heads,d,t,tpad", POOL_ATTN_SHAPES)
+def test_pool_attn_fwd_at_edges(ops, n, heads, d, t, tpad, dtype):
+    """A single key, no pad row, three trips of the 64-lane key loop (the last with two lanes), the smallest d."""
+    torch.manual_seed(300 + t + d)
+    _edge(f"pool_attn_fwd {(n, heads, d, t, tpad)} {dtype}", _check_pool_attn_fwd(n, t, tpad, heads, d, dtype))
+
+
+@pytest.mark.parametrize("dtype", TORSOS)
+def test_pool_attn_fwd_at_logits_of_sixty(ops, dtype):
+    """q and k scaled so that the logits span about +-60: the weights stay finite, within their bound, and sum to 1 within it."""
+    torch.manual_seed(360)
+    _edge(f"pool_attn_fwd logits +-60 {dtype}", _check_pool_attn_fwd(2, 65, 128, 4, 64, dtype, qk=4.3))
+
+
+@pytest.mark.parametrize("dtype", TORSOS)
+@pytest.mark.parametrize("mag", [1e-3, 1.024])
+@pytest.mark.parametrize("n,heads,d,t,tpad", POOL_ATTN_SHAPES)
+def test_pool_attn_bwd_at_edges(ops, n, heads, d, t, tpad, mag, dtype):
+    """d a0 at the magnitude of the unscaled bf16 network (1e-3) and times 1024: the bound carries fp16's subnormal spacing, so it
+    holds for both; the share of fp16's dK that underflows in the first is printed."""
+    torch.manual_seed(400 + t + d)
+    _edge(f"pool_attn_bwd {(n, heads, d, t, tpad)} |da0| {mag:g} {dtype}", _check_pool_attn_bwd(n, t, tpad, heads, d, dtype, mag))
+
+
+@pytest.mark.parametrize("dtype", TORSOS)
+@pytest.mark.parametrize("n,hw,c,tpad", POOL_PREP_SHAPES + [(33, 64, 512, 128)])
+def test_pool_prep_bwd_at_edges(ops, n, hw, c, tpad, dtype):
+    """The shapes of pool_prep, and 1 081 344 items: past the 4096 x 256 grid."""
+    torch.manual_seed(500 + hw + c)
+    _edge(f"pool_prep_bwd {(n, hw, c, tpad)} {dtype}", _check_pool_prep_bwd(n, hw, c, tpad, dtype), dtype)
+
+
+@pytest.mark.parametrize("dtype", TORSOS)
+@pytest.mark.parametrize("affine", [False, True])
+@pytest.mark.parametrize("n,hw,c", [(3, 64, 96), (2, 1, 8), (2, 9, 40), (2, 63, 200), (1, 4096, 64)])
+def test_channel_mean_at_edges(ops, n, hw, c, affine, dtype):
+    """Channel counts off the 64-channel block, pixel counts off the four lanes, a 64x64 map; written into a column window."""
+    torch.manual_seed(600 + hw + c)
+    _edge(f"channel_mean {(n, hw, c)} affine {affine} {dtype}", _check_channel_mean(n, hw, c, affine, 24, c + 56, dtype))
+
+
+@pytest.mark.parametrize("dtype", TORSOS)
+@pytest.mark.parametrize("with_add", [False, True])
+@pytest.mark.parametrize("n,hw,c", [(3, 64, 96), (1, 1, 8), (2, 4100, 1024)])
+def test_bcast_add_at_edges(ops, n, hw, c, with_add, dtype):
+    """1 049 600 items enter the grid-stride loop; col > 0; without `add` the result is round_T(v scale), bitwise."""
+    torch.manual_seed(700 + hw + c)
+    _edge(f"bcast_add {(n, hw, c)} add {with_add} {dtype}", _check_bcast_add(n, hw, c, with_add, 16, c + 40, dtype), dtype)
+
+
+@pytest.mark.parametrize("backward", [False, True])
+@pytest.mark.parametrize("mode", [1, 2])
+@pytest.mark.parametrize("items", [1, 255, 5 * 2048, 4096 * 256 + 3])
+def test_vec_act_at_edges(ops, items, mode, backward):
+    """+-0, +-88 and +-104 among the inputs: no NaN, ReLU'(0) = 0; one item, a partial block, past the 4096 x 256 grid."""
+    torch.manual_seed(800 + items % 1000)
+    _edge(f"vec_act items {items} mode {mode} backward {backward}", _check_vec_act(items, mode, backward))
+
+
+VEC_GN_SHAPES = [(5, 2048, 0.3, 1.0), (1, 32, 0.3, 1.0), (3, 96, 0.0, 1.0), (2, 288, 0.0, 2.0), (4, 2048, 100.0, 0.1)]
+
+
+@pytest.mark.parametrize("n,c,offset,std", VEC_GN_SHAPES)
+def test_vec_gn_at_edges(ops, n, c, offset, std):
+    """One value per group (y = beta exactly), a lane's second trip (c = 288), rows of mean 100 and standard deviation 0.1."""
+    torch.manual_seed(900 + c)
+    _edge(f"vec_gn {(n, c)} mean {offset} std {std}", _check_vec_gn(n, c, 1e-5, offset, std))
+
+
+@pytest.mark.parametrize("n,c,offset,std", VEC_GN_SHAPES)
+def test_vec_gn_bwd_at_edges(ops, n, c, offset, std):
+    torch.manual_seed(950 + c)
+    _edge(f"vec_gn_bwd {(n, c)} mean {offset} std {std}", _check_vec_gn_bwd(n, c, offset, std))
+
+
+@pytest.mark.parametrize("scale", [1.0, 2.5, 1024.0])
+@pytest.mark.parametrize("n,k", [(5, 1000), (1, 1), (2, 255), (2, 256), (2, 257), (3, 4097)])
+def test_logsoftmax_grad_at_edges(ops, n, k, scale):
+    """k around the 256 threads of the block, one class, y at 0 and at k - 1, a row of logits spread over +-1e4, the fp16
+    classifier's scale; logp_sel against float64 log_softmax."""
+    torch.manual_seed(1000 + k)
+    _edge(f"logsoftmax_grad {(n, k)} scale {scale:g}", _check_logsoftmax_grad(n, k, scale, spread=True))
+
+
+@pytest.mark.parametrize("dtype", TORSOS)
+@pytest.mark.parametrize("n,h,w,c,b_half", [(2, 8, 8, 64, 0), (2, 8, 8, 64, 1), (1, 2, 2, 8, 1), (1, 6, 10, 72, 1), (3, 128, 128, 256, 0)])
+def test_grad_add_at_edges(ops, n, h, w, c, b_half, dtype):
+    """adm_grad_add has no caller in the package: round_T(a + s b) with one fp32 add, at same and half resolution, a non-square
+    map, and 1 572 864 items: past the 4096 x 256 grid."""
+    torch.manual_seed(1100 + h + c)
+    a = torch.randn(n, h, w, c, device=DEV).to(dtype)
+    b = torch.randn(n, h // 2 if b_half else h, w // 2 if b_half else w, c, device=DEV).to(dtype)
+    buf, out = _owned((n, h, w, c), dtype)
+    _call(lr.KIND_OF_DTYPE[dtype], "adm_grad_add", _p(a), _p(b), _p(buf), n, h, w, c, b_half)
+    _guard_ok(buf, "adm_grad_add")
+    ref, bound = lr.grad_add_restate(a, b, bool(b_half), dtype)
+    wst, e2, r2, rep = lr.worst_ratio(out, ref, bound)
+    _edge(f"grad_add {(n, h, w, c, b_half)} {dtype}", (wst, _fro(e2, r2), rep), dtype)
+    if n == 2:
+        assert torch.equal(ops.grad_add(a, b, bool(b_half)), out)      # the ops wrapper reaches the same kernel
+
+
+@pytest.mark.parametrize("dtype", TORSOS)
+@pytest.mark.parametrize("h,w", [(5, 8), (8, 7)])
+def test_grad_add_refuses_an_odd_size_at_half_resolution(ops, h, w, dtype):
+    """Row h / 2 of an h / 2-row operand lies past its end: refused before the launch."""
+    from autodiffusion_amd._lib import AdmError
+    a = torch.zeros(1, h, w, 8, device=DEV, dtype=dtype)
+    b = torch.zeros(1, (h + 1) // 2, (w + 1) // 2, 8, device=DEV, dtype=dtype)
+    with pytest.raises(AdmError, match="odd size"):
+        ops.grad_add(a, b, b_half=True)
+    assert ops.grad_add(a, a).shape == a.shape

@@ -276,7 +276,8 @@ def test_every_test_named_elsewhere_exists():
 
 
 def _fake_records():
-    """One record per new kind and library, and the VAE's / CLIP's conv and attention families, shaped as the recorder shapes them."""
+    """One record per new kind and library (the classifier heads' from _fake_head_records), and the VAE's / CLIP's conv and attention
+    families, shaped as the recorder shapes them."""
     from autodiffusion_amd._lib import ConvArgs
     recs = {}
     for kind in ("bf16", "f16"):
@@ -295,6 +296,7 @@ def _fake_records():
         recs[("vae_latent_in", kind)] = ("vae_latent_in", kind, 1, 4, 4, 64, 64)
         recs[("conv2d", kind)] = ("conv2d", kind, ("cin", 320), ("cout", 320))
     recs[("vae_image_out", "bf16")] = ("vae_image_out", "bf16", 1, 512, 512, True, True)
+    recs.update(_fake_head_records())
     return recs
 
 
@@ -303,7 +305,8 @@ def test_coverage_guard_fails_when_a_model_or_a_hook_is_removed():
     hook's records, without the VAE's or without the CLIP encoder's, the guard names what is missing."""
     recs = _fake_records()
     here = {s: cov for s, cov in lr.SYMBOL_COVERAGE.items() if cov[0] != "elsewhere" and set(cov) & set(lr.NEW_KINDS)}
-    census = {(s, k) for s in here for k in ("bf16", "f16") if not (s == "adm_vae_image_out" and k == "f16")}
+    one_library = {"adm_" + f for f, k in lr.ONE_LIBRARY_FAMILIES.items() if k == "bf16"}   # fp32 kernels on the bf16 library alone
+    census = {(s, k) for s in here for k in ("bf16", "f16") if not (s in one_library and k == "f16")}
     census |= {("adm_linear_f32", "bf16")}   # held elsewhere: needs no record
     assert lr.coverage_gaps(census, recs.values(), lr.REPLAYED) == []
     new = set(lr.NEW_KINDS) | {"attention d 512", "non-square map"}
@@ -608,3 +611,470 @@ def test_families_of_the_new_records():
     assert lr.families(recs[("vae attention", "f16")]) == {("f16", "attention d 512")}
     for kind in lr.NEW_KINDS:
         assert lr.families(recs[(kind, "bf16")]) == {("bf16", kind)}
+
+
+# ------------------------------------------------------------------ classifier heads and gradient helpers
+def _fake_head_records():
+    """One record per classifier-head kind, shaped as the recorder shapes them: the attention pool and the 16-bit head kernels on
+    both libraries, the fp32 vector kernels and the loss gradient on the bf16 library that ops launches them from."""
+    recs = {}
+    for kind in ("bf16", "f16"):
+        recs[("pool_prep", kind)] = ("pool_prep", kind, 2, 64, 256, 128)
+        recs[("pool_attn_fwd", kind)] = ("pool_attn_fwd", kind, 2, 65, 128, 4, 64)
+        recs[("pool_attn_bwd", kind)] = ("pool_attn_bwd", kind, 2, 65, 128, 4, 64)
+        recs[("pool_prep_bwd", kind)] = ("pool_prep_bwd", kind, 2, 64, 256, 128)
+        recs[("channel_mean", kind)] = ("channel_mean", kind, 2, 64, 256, False, 448, 1024)
+        recs[("bcast_add", kind)] = ("bcast_add", kind, 2, 64, 256, True, 448, 1024)
+    recs[("vec_act", "bf16")] = ("vec_act", "bf16", 4096, 2, True)
+    recs[("vec_gn", "bf16")] = ("vec_gn", "bf16", 2, 2048, 1e-5)
+    recs[("vec_gn_bwd", "bf16")] = ("vec_gn_bwd", "bf16", 2, 2048)
+    recs[("logsoftmax_grad", "bf16")] = ("logsoftmax_grad", "bf16", 2, 1000, 1024.0)
+    return recs
+
+
+SPATIAL_HEAD_KINDS = ("channel_mean", "bcast_add", "vec_act", "vec_gn", "vec_gn_bwd")
+F32_LIBRARY_KINDS = ("vec_act", "vec_gn", "vec_gn_bwd", "logsoftmax_grad")
+
+
+def test_head_kinds_are_listed_required_and_replayed():
+    assert len(lr.HEAD_KINDS) == 10 and set(lr.HEAD_KINDS) <= set(lr.NEW_KINDS) and set(lr.HEAD_KINDS) <= set(lr.REQUIRED_FAMILIES)
+    assert set(lr.HEAD_KINDS) <= lr.REPLAYED
+    for k in lr.HEAD_KINDS:
+        assert lr.SYMBOL_COVERAGE["adm_" + k] == (k,)
+    assert {f for f, lib in lr.ONE_LIBRARY_FAMILIES.items() if lib == "bf16"} == {"vae_image_out"} | set(F32_LIBRARY_KINDS)
+    assert lr.SYMBOL_COVERAGE["adm_grad_add"] == ("elsewhere", "tests/test_hip_launch_replay.py::test_grad_add_at_edges")
+    recs = _fake_head_records()
+    for (k, lib), r in recs.items():
+        assert lr.families(r) == {(lib, k)}
+
+
+def test_coverage_guard_fails_when_a_head_hook_or_the_spatial_head_classifiers_are_removed():
+    recs = {**_fake_records(), **_fake_head_records()}
+    census = {("adm_" + k, lib) for (k, lib) in _fake_head_records()}
+    assert lr.coverage_gaps(census, recs.values(), lr.REPLAYED) == []
+    heads = set(lr.HEAD_KINDS)
+    assert not [m for m in lr.missing_families(recs.values()) if m[1] in heads]
+    for kind in lr.HEAD_KINDS:   # one hook removed from the recorder
+        left = [r for r in recs.values() if r[0] != kind]
+        gaps = lr.coverage_gaps(census, left, lr.REPLAYED)
+        assert gaps and all(kind in g for g in gaps), (kind, gaps)
+        want = {("bf16", kind)} if kind in F32_LIBRARY_KINDS else {("bf16", kind), ("f16", kind)}
+        assert {m for m in lr.missing_families(left) if m[1] in heads} == want
+    # without the adaptive / spatial / spatial_v2 classifiers nothing launches the kernels of csrc/adm_clfhead.hip
+    left = [r for r in recs.values() if r[0] not in SPATIAL_HEAD_KINDS]
+    assert {m[1] for m in lr.missing_families(left) if m[1] in heads} == set(SPATIAL_HEAD_KINDS)
+    # a record of the fp32 kernels taken under the other library's name does not stand in
+    assert lr.coverage_gaps({("adm_vec_gn", "bf16")}, [("vec_gn", "f16", 2, 2048, 1e-5)], lr.REPLAYED)
+
+
+def test_recorder_hooks_every_head_wrapper():
+    """Each of the ten ops wrappers is replaced, and the hook records before it passes the call on (the call itself fails here:
+    host tensors)."""
+    from autodiffusion_amd import ops
+    from autodiffusion_amd._lib import AdmError
+    with pytest.MonkeyPatch.context() as mp:
+        rec = lr.Recorder(mp)
+        h = torch.zeros(2, 8, 8, 64, dtype=torch.float16)
+        v = torch.zeros(2, 96)
+        calls = [lambda: ops.pool_prep(h, (v, v), v, 128), lambda: ops.pool_attn_fwd(torch.zeros(2, 128, 192, dtype=BF), 65, 1),
+                 lambda: ops.pool_attn_bwd(torch.zeros(2, 128, 192, dtype=BF), v, v, 65, 1),
+                 lambda: ops.pool_prep_bwd(torch.zeros(2, 128, 64, dtype=BF), 8, 8), lambda: ops.channel_mean(h, out=v, col=32),
+                 lambda: ops.bcast_add(v, (2, 8, 8, 64), BF, 0.5, col=16), lambda: ops.vec_act(v, "relu", dy=v),
+                 lambda: ops.vec_gn(v, v, v), lambda: ops.vec_gn_bwd(v, v, v, v),
+                 lambda: ops.logsoftmax_grad(v, torch.zeros(2, dtype=torch.int64), 1024.0)]
+        for call in calls:
+            with pytest.raises(AdmError):
+                call()
+        assert rec.records == {("pool_prep", "f16", 2, 64, 64, 128), ("pool_attn_fwd", "bf16", 2, 65, 128, 1, 64),
+                               ("pool_attn_bwd", "bf16", 2, 65, 128, 1, 64), ("pool_prep_bwd", "bf16", 2, 64, 64, 128),
+                               ("channel_mean", "f16", 2, 64, 64, False, 32, 96), ("bcast_add", "bf16", 2, 64, 64, False, 16, 96),
+                               ("vec_act", "bf16", 192, 2, True), ("vec_gn", "bf16", 2, 96, 1e-5), ("vec_gn_bwd", "bf16", 2, 96),
+                               ("logsoftmax_grad", "bf16", 2, 96, 1024.0)}
+
+
+def _silu32(z):
+    return z * (1.0 / (1.0 + torch.exp2(z * torch.tensor(-1.4426950408889634, dtype=F32))))
+
+
+def _seq_sum(v, dim=-1):
+    """fp32 sum along dim in index order, one add at a time."""
+    v = v.movedim(dim, 0)
+    s = torch.zeros_like(v[0])
+    for x in v:
+        s = s + x
+    return s
+
+
+def _lane_sum(v, lanes):
+    """The kernels' strided sums along the last axis: lane l adds elements l, l + lanes, ... in order, then the lanes are halved
+    (lane l takes lane l + half: the butterfly's and the block tree's pairing for lane 0)."""
+    pad = (-v.shape[-1]) % lanes
+    v = F.pad(v, (0, pad)).reshape(*v.shape[:-1], -1, lanes)
+    s = _seq_sum(v, -2)
+    while s.shape[-1] > 1:
+        half = s.shape[-1] // 2
+        s = s[..., :half] + s[..., half:]
+    return s[..., 0]
+
+
+def _ratio(got, ref, bound):
+    return ((got.double() - ref).abs() / bound).max().item()
+
+
+def _pool_case(n, hw, c, dtype, seed):
+    h = lr.round_t(_rnd((n, hw, c), seed), dtype)
+    a, b = 1 + 0.2 * _rnd((n, c), seed + 1), 0.2 * _rnd((n, c), seed + 2)
+    pos = _rnd((c, hw + 1), seed + 3, c ** -0.5) + 0.01 * torch.arange(c * (hw + 1)).reshape(c, hw + 1) / (c * (hw + 1))
+    return h, a, b, pos
+
+
+def _pool_prep_emulated(h, a, b, pos, tpad, dtype, pos_tc=False, div_t=False):
+    n, hw, c = h.shape
+    v = _silu32(a[:, None, :] * h.to(F32) + b[:, None, :])
+    p = pos.reshape(hw + 1, c) if pos_tc else pos.t()
+    tok = torch.zeros(n, tpad, c, dtype=dtype)
+    tok[:, 1:hw + 1] = (v + p[None, 1:]).to(dtype)
+    tok[:, 0] = (_seq_sum(v, 1) / torch.tensor(float(hw + 1 if div_t else hw), dtype=F32) + p[0]).to(dtype)
+    return tok
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+def test_pool_prep_restatement_emulation_and_defects(dtype):
+    n, hw, c, tpad = 2, 64, 96, 128
+    h, a, b, pos = _pool_case(n, hw, c, dtype, 1)
+    ref, bound = lr.pool_prep_restate(h, a, b, pos, tpad, dtype)
+    act = F.silu(a.double()[:, None] * h.double() + b.double()[:, None])
+    plain = torch.cat([act.mean(1, keepdim=True), act], 1) + pos.double().t()[None]
+    torch.testing.assert_close(ref, plain, rtol=1e-12, atol=1e-12)
+    emu = _pool_prep_emulated(h, a, b, pos, tpad, dtype)
+    r = _ratio(emu[:, :hw + 1], ref, bound)
+    print(f"pool_prep {dtype}: emulation worst err/bound {r:.3f}")
+    assert r <= 1.0 and bool((emu[:, hw + 1:] == 0).all())
+    assert (bound / lr.half_ulp(ref, dtype)).median() <= 1.1           # the bound stays close to a bare half ulp
+    for kw in (dict(pos_tc=True), dict(div_t=True)):
+        bad = _pool_prep_emulated(h, a, b, pos, tpad, dtype, **kw)
+        rb = _ratio(bad[:, :hw + 1], ref, bound)
+        print(f"pool_prep {dtype}: defect {kw} {rb:.1f} x the bound")
+        assert rb > 1.0, kw
+
+
+def _pool_qkv(n, t, tpad, heads, d, dtype, seed, qk_scale=1.0):
+    qkv = torch.full((n, tpad, 3 * heads * d), float("nan"))
+    x = _rnd((n, t, 3 * heads * d), seed)
+    x[..., :2 * heads * d] *= qk_scale
+    qkv[:, :t] = x
+    qkv[:, t:] = 0.0       # the pad rows hold the projection's bias in a model; zero keeps the pad-key defect's logits at 0
+    return lr.round_t(qkv, dtype)
+
+
+def _pool_fwd_emulated(qkv, t, heads, inv_d=False, pad_keys=False):
+    n, tpad, c3 = qkv.shape
+    c = c3 // 3
+    d = c // heads
+    x = qkv.to(F32).reshape(n, tpad, 3, heads, d)
+    q0, k, v = x[:, 0, 0], x[:, :, 1].permute(0, 2, 1, 3), x[:, :, 2].permute(0, 2, 1, 3)     # [n, H, d], [n, H, tpad, d]
+    scale = torch.tensor(1.0 / d if inv_d else d ** -0.5, dtype=F32)
+    tk = tpad if pad_keys else t
+    lg = _seq_sum(q0[:, :, None, :] * k[:, :, :tk], -1) * scale
+    e = torch.exp(lg - lg.amax(-1, keepdim=True))
+    w = torch.zeros(n, heads, tpad)
+    w[..., :tk] = e / _lane_sum(e, 64)[..., None]
+    if pad_keys:
+        w[..., t:] = 0.0
+    a0 = _seq_sum(w[..., :t, None] * v[:, :, :t], 2)
+    return w, a0.reshape(n, c)
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+@pytest.mark.parametrize("n,heads,d,t,tpad,qk", [(2, 4, 64, 65, 128, 1.0), (1, 3, 32, 130, 192, 1.0), (2, 1, 8, 17, 24, 1.0),
+                                                 (1, 2, 64, 65, 128, 2.7)])
+def test_pool_attn_fwd_restatement_emulation_and_defects(n, heads, d, t, tpad, qk, dtype):
+    qkv = _pool_qkv(n, t, tpad, heads, d, dtype, 3, qk)
+    (w, a0), (bw, ba) = lr.pool_attn_fwd_restate(qkv, t, heads)
+    q, k, v = lr.pool_split(qkv, t, heads)
+    s = torch.einsum("nhd,nhtd->nht", q, k) / math.sqrt(d)
+    e = torch.exp(s - s.amax(-1, keepdim=True))
+    torch.testing.assert_close(w, e / e.sum(-1, keepdim=True), rtol=1e-12, atol=1e-300)
+    torch.testing.assert_close(a0, torch.einsum("nht,nhtd->nhd", w, v).reshape(n, -1), rtol=1e-12, atol=1e-12)
+    gw, ga = _pool_fwd_emulated(qkv, t, heads)
+    rw, ra = _ratio(gw[..., :t], w, bw), _ratio(ga, a0, ba)
+    print(f"pool_attn_fwd {dtype} d {d} T {t} qk x{qk}: logits span {s.min().item():.1f} .. {s.max().item():.1f}; emulation worst "
+          f"err/bound weights {rw:.3f}, a0 {ra:.3f}")
+    assert rw <= 1.0 and ra <= 1.0 and bool((gw[..., t:] == 0).all())
+    assert ((gw[..., :t].double().sum(-1) - 1).abs() <= bw.sum(-1)).all()
+    for kw in (dict(inv_d=True), dict(pad_keys=True)):
+        bwd, bad = _pool_fwd_emulated(qkv, t, heads, **kw)
+        rb = max(_ratio(bwd[..., :t], w, bw), _ratio(bad, a0, ba))
+        print(f"pool_attn_fwd {dtype}: defect {kw} {rb:.1f} x the bound")
+        assert rb > 1.0 or (kw == dict(pad_keys=True) and t == tpad), kw
+
+
+def _pool_bwd_emulated(qkv, wts, da0, t, heads, dtype, no_delta=False, dq_row1=False, dk_w=False):
+    n, tpad, c3 = qkv.shape
+    c = c3 // 3
+    d = c // heads
+    x = qkv.to(F32).reshape(n, tpad, 3, heads, d)
+    q0, k, v = x[:, 0, 0], x[:, :t, 1].permute(0, 2, 1, 3), x[:, :t, 2].permute(0, 2, 1, 3)
+    w, da = wts[..., :t], da0.reshape(n, heads, d)
+    dw = _seq_sum(da[:, :, None, :] * v, -1)
+    delta = torch.zeros(n, heads, 1) if no_delta else _lane_sum(w * dw, 64)[..., None]
+    dlg = w * (dw - delta) * torch.tensor(d ** -0.5, dtype=F32)
+    out = torch.zeros(n, tpad, 3, heads, d, dtype=dtype)
+    out[:, :t, 1] = ((w if dk_w else dlg)[..., None] * q0[:, :, None, :]).permute(0, 2, 1, 3).to(dtype)
+    out[:, :t, 2] = (w[..., None] * da[:, :, None, :]).permute(0, 2, 1, 3).to(dtype)
+    out[:, 0, 0] = _seq_sum(dlg[..., None] * k, 2).to(dtype)
+    if dq_row1 and t > 1:
+        out[:, 1, 0] = out[:, 0, 0]
+    return out.reshape(n, tpad, c3)
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+@pytest.mark.parametrize("n,heads,d,t,tpad", [(2, 4, 64, 65, 128), (1, 3, 32, 130, 192), (2, 1, 8, 17, 24), (3, 1, 32, 1, 64)])
+@pytest.mark.parametrize("mag", [1e-3, 1.024])
+def test_pool_attn_bwd_restatement_emulation_and_defects(n, heads, d, t, tpad, mag, dtype):
+    qkv = _pool_qkv(n, t, tpad, heads, d, dtype, 5)
+    wts, _ = _pool_fwd_emulated(qkv, t, heads)
+    da0 = _rnd((n, heads * d), 6, mag)
+    ref, bound = lr.pool_attn_bwd_restate(qkv, wts, da0, t, heads, dtype)
+    # autograd of the float64 pool, with the stored weights' softmax replaced by its own (they agree to fp32 accuracy)
+    x = qkv[:, :t].double().clone().requires_grad_()
+    (_, a0), _ = lr.pool_attn_fwd_restate(x, t, heads)
+    (a0 * da0.double()).sum().backward()
+    torch.testing.assert_close(ref, x.grad, rtol=2e-5, atol=2e-6 * mag)
+    got = _pool_bwd_emulated(qkv, wts, da0, t, heads, dtype)
+    r = _ratio(got[:, :t], ref, bound)
+    c = heads * d
+    under = float(((got[:, :t, c:2 * c] == 0) & (ref[:, :, c:2 * c] != 0)).float().mean())
+    print(f"pool_attn_bwd {dtype} d {d} T {t} |da0| {mag:g}: emulation worst err/bound {r:.3f}; dK flushed to zero {under:.1%}")
+    assert r <= 1.0 and lr.pool_zero_rows_ok(got, t)
+    if t == 1:
+        assert bool((got[:, 0, :2 * c] == 0).all())      # a single key: weight 1, dK = 0 and dQ = 0, exactly (of either sign)
+        return
+    for kw in (dict(no_delta=True), dict(dk_w=True)):
+        rb = _ratio(_pool_bwd_emulated(qkv, wts, da0, t, heads, dtype, **kw)[:, :t], ref, bound)
+        print(f"pool_attn_bwd {dtype}: defect {kw} {rb:.1f} x the bound")
+        assert rb > 1.0, kw
+    bad = _pool_bwd_emulated(qkv, wts, da0, t, heads, dtype, dq_row1=True)
+    assert _ratio(bad[:, :t], ref, bound) > 1.0 and not lr.pool_zero_rows_ok(bad, t)
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+def test_pool_prep_bwd_restatement_emulation_and_defects(dtype):
+    n, hw, c, tpad = 2, 64, 40, 128
+    dtok = lr.round_t(_rnd((n, tpad, c), 7), dtype)
+    ref, bound = lr.pool_prep_bwd_restate(dtok, hw, dtype)
+    act = _rnd((n, hw, c), 8).double().requires_grad_()
+    (torch.cat([act.mean(1, keepdim=True), act], 1) * dtok[:, :hw + 1].double()).sum().backward()
+    torch.testing.assert_close(ref, act.grad, rtol=1e-12, atol=1e-12)
+    x = dtok.to(F32)
+    emu = (x[:, 1:hw + 1] + x[:, :1] / torch.tensor(float(hw), dtype=F32)).to(dtype)
+    r = _ratio(emu, ref, bound)
+    bad = (x[:, 1:hw + 1] + x[:, :1] / torch.tensor(float(hw + 1), dtype=F32)).to(dtype)
+    rb = _ratio(bad, ref, bound)
+    print(f"pool_prep_bwd {dtype}: emulation worst err/bound {r:.3f}; token 0 over T {rb:.1f} x the bound")
+    assert r <= 1.0 and rb > 1.0
+
+
+def test_pool_restatements_compose_to_the_oracle_attention_pool():
+    """pool_prep -> a float64 qkv projection -> pool_attn_fwd against oracle.nets.attention_pool with an identity c_proj."""
+    from types import SimpleNamespace
+    from oracle import nets
+    n, hw, c, heads = 2, 64, 64, 2
+    h, a, b, pos = _pool_case(n, hw, c, BF, 11)
+    tok, _ = lr.pool_prep_restate(h, a, b, pos, 128, BF)
+    wq, bq = _rnd((3 * c, c), 12, c ** -0.5).double(), _rnd((3 * c,), 13, 0.1).double()
+    (_, a0), _ = lr.pool_attn_fwd_restate(tok @ wq.t() + bq, hw + 1, heads)
+    P = {"out.2.positional_embedding": pos.double(), "out.2.qkv_proj.weight": wq[:, :, None], "out.2.qkv_proj.bias": bq,
+         "out.2.c_proj.weight": torch.eye(c, dtype=torch.float64)[:, :, None], "out.2.c_proj.bias": torch.zeros(c, dtype=torch.float64)}
+    act = F.silu(a.double()[:, None] * h.double() + b.double()[:, None]).permute(0, 2, 1).reshape(n, c, 8, 8)
+    orc = nets.attention_pool(P, SimpleNamespace(prefix="out", num_heads=heads), act)
+    torch.testing.assert_close(a0, orc.double(), rtol=1e-5, atol=1e-5)   # the oracle's softmax runs in fp32
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+@pytest.mark.parametrize("affine", [False, True])
+@pytest.mark.parametrize("hw", [9, 64, 63])
+def test_channel_mean_restatement_emulation_and_defects(hw, affine, dtype):
+    n, c = 2, 40
+    h, a, b, _ = _pool_case(n, hw, c, dtype, 21)
+    aff = (a, b) if affine else None
+    ref, bound = lr.channel_mean_restate(h, aff)
+    v = F.silu(a.double()[:, None] * h.double() + b.double()[:, None]) if affine else h.double()
+    torch.testing.assert_close(ref, v.mean(1), rtol=1e-12, atol=1e-12)
+    v32 = _silu32(a[:, None] * h.to(F32) + b[:, None]) if affine else h.to(F32)
+    lanes = F.pad(v32, (0, 0, 0, (-hw) % 4)).reshape(n, -1, 4, c)
+    r4 = _seq_sum(lanes, 1)
+    tot = ((r4[:, 0] + r4[:, 1]) + r4[:, 2]) + r4[:, 3]
+    emu = tot / torch.tensor(float(hw), dtype=F32)
+    r = _ratio(emu, ref, bound)
+    bad = tot / torch.tensor(float((hw + 3) // 4), dtype=F32)        # divided by one lane's pixels
+    rb = _ratio(bad, ref, bound)
+    print(f"channel_mean {dtype} hw {hw} affine {affine}: emulation worst err/bound {r:.3f}; one lane's count {rb:.3g} x the bound")
+    assert r <= 1.0 and rb > 1.0
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+def test_bcast_add_restatement_emulation_and_defects(dtype):
+    n, hw, c, col, scale = 3, 16, 24, 8, 1.0 / 64
+    v = _rnd((n, 64), 31)
+    add = lr.round_t(_rnd((n, hw, c), 32), dtype)
+    win = v[:, col:col + c]
+    ref, bound = lr.bcast_add_restate(win, scale, add, hw, dtype)
+    torch.testing.assert_close(ref, add.double() + win.double()[:, None] * scale, rtol=1e-12, atol=1e-12)
+    emu = (win[:, None] * torch.tensor(scale, dtype=F32) + add.to(F32)).to(dtype)
+    r = _ratio(emu, ref, bound)
+    bad = (v[:, None, :c] * torch.tensor(scale, dtype=F32) + add.to(F32)).to(dtype)           # col ignored
+    rb = _ratio(bad, ref, bound)
+    print(f"bcast_add {dtype}: emulation worst err/bound {r:.3f}; col ignored {rb:.1f} x the bound")
+    assert r <= 1.0 and rb > 1.0
+    exact, none = lr.bcast_add_restate(win, 1.0 / 3, None, hw, dtype)
+    assert none is None and exact.dtype == dtype and exact.shape == (n, hw, c)
+    assert torch.equal(exact[:, 5], (win * torch.tensor(1.0 / 3, dtype=F32)).to(dtype))
+    assert not torch.equal(exact[:, 5], (v[:, :c] * torch.tensor(1.0 / 3, dtype=F32)).to(dtype))
+
+
+VEC_SPECIALS = (0.0, -0.0, 88.0, -88.0, 104.0, -104.0, 1e-3, -1.2784645)
+
+
+def _vec_act_emulated(x, mode, dy=None, plain_sigmoid=False, relu_at_zero=False):
+    if mode == 2:
+        if dy is None:
+            return torch.clamp(x, min=0.0)
+        return dy * ((x >= 0) if relu_at_zero else (x > 0)).to(F32)
+    s = 1.0 / (1.0 + torch.exp(-x))
+    if dy is None:
+        return x / (1.0 + torch.exp(-x))
+    return dy * (s if plain_sigmoid else s * (1.0 + x * (1.0 - s)))
+
+
+def test_vec_act_restatement_emulation_and_defects():
+    x = _rnd((5 * 2048,), 41, 3.0)
+    x[:len(VEC_SPECIALS)] = torch.tensor(VEC_SPECIALS)
+    dy = _rnd((5 * 2048,), 42)
+    xd = x.double().requires_grad_()
+    F.silu(xd).backward(dy.double())
+    ref, bound = lr.vec_act_restate(x, 1)
+    torch.testing.assert_close(ref, F.silu(x.double()), rtol=1e-12, atol=1e-300)
+    refb, boundb = lr.vec_act_restate(x, 1, dy)
+    torch.testing.assert_close(refb, xd.grad, rtol=1e-12, atol=1e-15)
+    r, rb = _ratio(_vec_act_emulated(x, 1), ref, bound), _ratio(_vec_act_emulated(x, 1, dy), refb, boundb)
+    bad = _ratio(_vec_act_emulated(x, 1, dy, plain_sigmoid=True), refb, boundb)
+    print(f"vec_act: emulation worst err/bound SiLU {r:.3f}, SiLU' {rb:.3f}; SiLU' without z (1 - s) {bad:.3g} x the bound")
+    assert r <= 1.0 and rb <= 1.0 and bad > 1.0
+    assert torch.isfinite(_vec_act_emulated(x, 1)).all() and torch.isfinite(_vec_act_emulated(x, 1, dy)).all()
+    ref, none = lr.vec_act_restate(x, 2)
+    refb, noneb = lr.vec_act_restate(x, 2, dy)
+    assert none is None and noneb is None
+    assert torch.equal(ref, F.relu(x.double())) and torch.equal(refb, dy.double() * (x > 0))
+    assert torch.equal(_vec_act_emulated(x, 2).double(), ref) and torch.equal(_vec_act_emulated(x, 2, dy).double(), refb)
+    assert refb[0] == 0 and refb[1] == 0                                   # ReLU'(+-0) = 0
+    assert not torch.equal(_vec_act_emulated(x, 2, dy, relu_at_zero=True).double(), refb)
+
+
+def _vec_gn_emulated(x, gamma, beta, eps, unbiased=False):
+    n, c = x.shape
+    cpg = c // 32
+    g = x.reshape(n, 32, cpg)
+    fc = torch.tensor(float(cpg), dtype=F32)
+    mean = (_lane_sum(g, 8) / fc)[..., None]
+    d = g - mean
+    ss = _lane_sum(d * d, 8)
+    rstd = (1.0 / torch.sqrt(ss / (fc - 1 if unbiased else fc) + torch.tensor(eps, dtype=F32)))[..., None]
+    y = gamma.reshape(1, 32, cpg) * d * rstd + beta.reshape(1, 32, cpg)
+    return y.reshape(n, c), torch.cat([mean, rstd], -1)
+
+
+def _vec_gn_bwd_emulated(x, gamma, stats, dz, no_xhat=False):
+    n, c = x.shape
+    cpg = c // 32
+    fc = torch.tensor(float(cpg), dtype=F32)
+    mean, rstd = stats[..., :1], stats[..., 1:]
+    g = (gamma[None] * dz).reshape(n, 32, cpg)
+    xh = (x.reshape(n, 32, cpg) - mean) * rstd
+    s1, s2 = (_lane_sum(g, 8) / fc)[..., None], (_lane_sum(g * xh, 8) / fc)[..., None]
+    return (rstd * (g - s1 - (0 if no_xhat else xh * s2))).reshape(n, c)
+
+
+def _vec_rows(n, c, seed, offset=0.0, std=1.0):
+    return _rnd((n, c), seed, std) + offset, 1 + 0.2 * _rnd((c,), seed + 1), 0.1 * _rnd((c,), seed + 2)
+
+
+@pytest.mark.parametrize("n,c,offset,std", [(5, 2048, 0.3, 1.0), (1, 32, 0.3, 1.0), (3, 96, 0.0, 1.0), (2, 288, 0.0, 2.0), (4, 2048, 100.0, 0.1)])
+def test_vec_gn_restatements_emulation_and_defects(n, c, offset, std):
+    x, gamma, beta = _vec_rows(n, c, 51, offset, std)
+    (y, mean, rstd), (by, bm, br) = lr.vec_gn_restate(x, gamma, beta, 1e-5)
+    plain = (F.group_norm(x.double(), 32, gamma.double(), beta.double(), float(torch.tensor(1e-5, dtype=F32))) if c > 32
+             else beta.double()[None].expand(n, -1))           # one value per group: torch refuses it, the result is beta
+    torch.testing.assert_close(y, plain, rtol=1e-10, atol=1e-10)
+    ye, st = _vec_gn_emulated(x, gamma, beta, 1e-5)
+    r = max(_ratio(ye, y, by), _ratio(st[..., 0], mean, bm), _ratio(st[..., 1], rstd, br))
+    print(f"vec_gn n {n} c {c} mean {offset} std {std}: emulation worst err/bound {r:.3f}")
+    assert r <= 1.0
+    dz = _rnd((n, c), 54)
+    ref, bound = lr.vec_gn_bwd_restate(x, gamma, st, dz)
+    rbw = _ratio(_vec_gn_bwd_emulated(x, gamma, st, dz), ref, bound)
+    print(f"vec_gn_bwd n {n} c {c}: emulation worst err/bound {rbw:.3f}")
+    assert rbw <= 1.0
+    if c == 32:   # one value per group: y = beta and dx = 0, both exactly
+        assert torch.equal(ye, beta[None].expand(n, -1)) and not bool(_vec_gn_bwd_emulated(x, gamma, st, dz).view(torch.int32).any())
+        return
+    # the backward restatement against autograd through the float64 GroupNorm (its own float64 statistics)
+    xd = x.double().requires_grad_()
+    F.group_norm(xd, 32, gamma.double(), beta.double(), float(torch.tensor(1e-5, dtype=F32))).backward(dz.double())
+    st64 = torch.stack([mean, rstd], -1)
+    torch.testing.assert_close(lr.vec_gn_bwd_restate(x, gamma, st64, dz)[0], xd.grad, rtol=1e-8, atol=1e-8)
+    bad_y = _ratio(_vec_gn_emulated(x, gamma, beta, 1e-5, unbiased=True)[0], y, by)
+    bad_dx = _ratio(_vec_gn_bwd_emulated(x, gamma, st, dz, no_xhat=True), ref, bound)
+    print(f"vec_gn: variance over cpg - 1 {bad_y:.3g} x the bound; vec_gn_bwd without the xhat term {bad_dx:.3g} x the bound")
+    assert bad_dx > 1.0 and (bad_y > 1.0 or offset == 100.0)
+
+
+def _logsoftmax_emulated(logits, y, scale, onehot_unscaled=False):
+    n, k = logits.shape
+    mx = logits.amax(-1, keepdim=True)
+    e = torch.exp(logits - mx)
+    total = _lane_sum(e, 256)[..., None]
+    sm = e / total
+    one = torch.zeros(n, k)
+    one[torch.arange(n), y] = 1.0
+    sc = torch.tensor(scale, dtype=F32)
+    dl = (one - sc * sm) if onehot_unscaled else sc * (one - sm)
+    return dl, logits[torch.arange(n), y] - mx[:, 0] - torch.log(total[:, 0])
+
+
+@pytest.mark.parametrize("n,k", [(5, 1000), (1, 1), (2, 255), (2, 257), (3, 4097)])
+@pytest.mark.parametrize("scale", [1.0, 2.5, 1024.0])
+def test_logsoftmax_grad_restatement_emulation_and_defects(n, k, scale):
+    logits = _rnd((n, k), 61, 3.0)
+    logits[-1] = torch.linspace(-1e4, 1e4, k) if k > 1 else logits[-1]
+    y = torch.tensor([0, k - 1, k // 2, 0, k - 1][:n])
+    (dl, lp), (bd, bl) = lr.logsoftmax_grad_restate(logits, y, scale)
+    ld = logits.double().requires_grad_()
+    sel = F.log_softmax(ld, -1)[torch.arange(n), y]
+    (scale * sel.sum()).backward()
+    torch.testing.assert_close(dl, ld.grad, rtol=1e-10, atol=1e-12 * scale)
+    torch.testing.assert_close(lp, sel.detach(), rtol=1e-12, atol=1e-12)
+    ge, gl = _logsoftmax_emulated(logits, y, scale)
+    r, rl = _ratio(ge, dl, bd), _ratio(gl, lp, bl)
+    print(f"logsoftmax_grad n {n} k {k} scale {scale:g}: emulation worst err/bound dl {r:.3f}, logp_sel {rl:.3f}")
+    assert r <= 1.0 and rl <= 1.0 and torch.isfinite(ge).all()
+    if scale != 1.0 and k > 1:
+        rb = _ratio(_logsoftmax_emulated(logits, y, scale, onehot_unscaled=True)[0], dl, bd)
+        print(f"logsoftmax_grad: scale on the softmax only {rb:.3g} x the bound")
+        assert rb > 1.0
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+@pytest.mark.parametrize("b_half", [False, True])
+def test_grad_add_restatement_emulation_and_defects(b_half, dtype):
+    n, h, w, c = 1, 6, 10, 8
+    a = lr.round_t(_rnd((n, h, w, c), 71), dtype)
+    b = lr.round_t(_rnd((n, h // 2, w // 2, c) if b_half else (n, h, w, c), 72), dtype)
+    ref, bound = lr.grad_add_restate(a, b, b_half, dtype)
+    up = F.interpolate(b.permute(0, 3, 1, 2).double(), scale_factor=2, mode="nearest").permute(0, 2, 3, 1) * 0.25 if b_half else b.double()
+    torch.testing.assert_close(ref, a.double() + up, rtol=1e-12, atol=1e-12)
+    emu = (a.to(F32) + up.to(F32)).to(dtype)
+    assert _ratio(emu, ref, bound) <= 1.0
+    if b_half:   # the AvgPool2d backward's 1 / 4 left out
+        assert _ratio((a.to(F32) + 4 * up.to(F32)).to(dtype), ref, bound) > 1.0
+    assert (_truncate(a.to(F32) + up.to(F32), dtype).double() - ref).norm() / ref.norm() > lr.fro_bound(1, lr.U[dtype])
