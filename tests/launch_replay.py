@@ -8,8 +8,10 @@ captured as a copy of its adm_conv_args without the pointers, plus which optiona
 attention, GroupNorm, token (LayerNorm, GEGLU, quick-GELU, embedding), resample, layout, VAE entry / exit and stride-2 conv2d calls
 are captured at the ops level by shape and flags, and so are the classifier heads: the attention pool's four kernels, the
 adaptive / spatial / spatial_v2 heads' channel mean, broadcast add, vector activation and vector GroupNorm, and the loss
-gradient.  The sampler-step kernels (adm_ddim_step, adm_ddpm_step, adm_sd_step,
-adm_dpm_step) are not launched by a model evaluation: they stay with their oracle goldens.
+gradient, and the fp32 embedding path: adm_linear_f32 (time_embed, every emb_layers, the heads' Linear layers) by (n, k, o),
+SiLU, the bias / table flags and the operands' alignment, adm_timestep_embedding by (n, dim, max_period) -- their restatements
+and bounds are tests/f32_kernels.py's.  The sampler-step kernels (adm_ddim_step, adm_ddpm_step, adm_sd_step, adm_dpm_step) are
+not launched by a model evaluation: tests/test_hip_f32_kernels.py holds them.
 
 Restatement: the op in float64 on the operands exactly as the kernel sees them -- 16-bit inputs, weights and residuals; the
 GroupNorm affine (+ SiLU) prologue in fp32, rounded once to the 16-bit type T.
@@ -96,6 +98,7 @@ Per-element bounds, u = 2^-8 (bf16) or 2^-11 (fp16), ulp_T(v) = 2u * 2^floor(log
              dl = scale (onehot - softmax): |scale| (rel softmax + F32_MIN) + 2 e |ref|.  logp_sel = l_y - max - logf(sum):
              e dist_y + SILU_REL (1 + |log sum|) + the sum's relative error + 2 e |ref|.
   grad_add   round_T(a + s b), s = 1 or an exact 1 / 4: ulp_T(|ref|) / 2 + e (|a| + |s b|).
+  linear_f32, timestep_embedding   fp32 throughout: f32_kernels.linear_restate / timestep_restate (derived in that module's docstring).
   Frobenius  ||got - ref|| / ||ref|| <= FRO_U u sqrt(r), FRO_U = 0.6: one rounding to T has an RMS relative error of at most
              u / sqrt(3) ~ 0.58 u; r roundings in sequence (A, then A + residual; dz, then dz SiLU'; P, then the output) add in
              quadrature.
@@ -108,6 +111,8 @@ from __future__ import annotations
 import math
 
 import torch
+
+from f32_kernels import linear_path, linear_restate, timestep_restate   # noqa: F401  (the two fp32 record kinds of the embedding path)
 
 U = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
 KIND_DTYPE = {"bf16": torch.bfloat16, "f16": torch.float16}
@@ -160,9 +165,9 @@ def _e(test: str) -> tuple:
 
 
 # launch symbol -> the record kinds that replay it here, or ("elsewhere", "tests/<file>.py::<test>") for what stays where it is:
-# the fp32 embedding / linear kernels, the weight packers (every conv replay
-# compares against round_t(w), so a mis-packed weight fails there too), the sampler steps, and the evaluation-side kernels of
-# the Inception replay and the FID / precision-recall tests.
+# the weight packers (every conv replay compares against round_t(w), so a mis-packed weight fails there too), the sampler steps
+# and the direct stem (tests/test_hip_f32_kernels.py), and the evaluation-side kernels of the Inception replay and the FID /
+# precision-recall tests.
 SYMBOL_COVERAGE = {
     "adm_conv": ("conv",),
     "adm_attention_lse": ("attention",),
@@ -200,28 +205,28 @@ SYMBOL_COVERAGE = {
     "adm_logsoftmax_grad": ("logsoftmax_grad",),
     # no caller in the package: held by its direct test
     "adm_grad_add": _e("tests/test_hip_launch_replay.py::test_grad_add_at_edges"),
-    # fp32 embedding path and the direct stem
-    "adm_linear_f32": _e("tests/test_hip_kernels.py::test_linear_f32"),
-    "adm_timestep_embedding": _e("tests/test_hip_kernels.py::test_timestep_embedding"),
-    "adm_stem_conv3x3": _e("tests/test_hip_kernels.py::test_stem_conv"),
+    # fp32 embedding path: record kinds; the direct stem has no caller in the shipped models
+    "adm_linear_f32": ("linear_f32",),
+    "adm_timestep_embedding": ("timestep_embedding",),
+    "adm_stem_conv3x3": _e("tests/test_hip_f32_kernels.py::test_stem_conv_at_edges"),
     # weight packers
     "adm_pack_conv_weight": _e("tests/test_hip_kernels.py::test_conv_fused"),
     "adm_pack_conv_weight32": _e("tests/test_hip_kernels.py::test_conv_fused"),
     "adm_pack_conv_weight_bwd": _e("tests/test_hip_classifier.py::test_conv_backward_data_weights"),
     "adm_pack_conv2d_weight": _e("tests/test_hip_inception_replay.py::test_conv_launches_match_float64"),
     # sampler steps: not launched by a model evaluation
-    "adm_ddim_step": _e("tests/test_hip_kernels.py::test_sampler_steps_match_oracle"),
-    "adm_ddpm_step": _e("tests/test_hip_kernels.py::test_sampler_steps_match_oracle"),
-    "adm_pack_u8_nhwc": _e("tests/test_hip_kernels.py::test_pack_u8_bit_exact_and_odd_sizes"),
-    "adm_sd_step": _e("tests/test_hip_sd.py::test_ddim_step_with_noise_matches_the_oracle_formula"),
-    "adm_dpm_step": _e("tests/test_hip_sd.py::test_dpm_solver_sampler_matches_reference_goldens"),
+    "adm_ddim_step": _e("tests/test_hip_f32_kernels.py::test_sampler_step_flag_product"),
+    "adm_ddpm_step": _e("tests/test_hip_f32_kernels.py::test_sampler_step_flag_product"),
+    "adm_pack_u8_nhwc": _e("tests/test_hip_f32_kernels.py::test_pack_u8_bitwise"),
+    "adm_sd_step": _e("tests/test_hip_f32_kernels.py::test_sd_step_every_operand_subset"),
+    "adm_dpm_step": _e("tests/test_hip_f32_kernels.py::test_dpm_step_every_operand_subset"),
     # evaluation side
     "adm_pool2d": _e("tests/test_hip_inception_replay.py::test_pool_launches_match_float64"),
     "adm_global_avgpool_f32": _e("tests/test_hip_inception_replay.py::test_global_avgpool_launches_match_float64"),
     "adm_resize_bilinear": _e("tests/test_hip_inception_replay.py::test_resize_launches_match_float64"),
     "adm_fid_accumulate": _e("tests/test_fid.py::test_gram_kernel_ragged_shapes_and_symmetry"),
-    "adm_knn_smallest": _e("tests/test_hip_evaluator.py::test_radii_match_the_restatement"),
-    "adm_knn_cover": _e("tests/test_hip_evaluator.py::test_precision_recall_exactly_the_restatement"),
+    "adm_knn_smallest": _e("tests/test_hip_f32_kernels.py::test_knn_smallest_at_narrow_widths"),
+    "adm_knn_cover": _e("tests/test_hip_f32_kernels.py::test_knn_cover_at_narrow_widths"),
     # no caller in the package (ops.attention always asks adm_attention_lse): only its export is held
     "adm_attention": _e("tests/test_cabi.py::test_library_loads_and_exports_every_symbol"),
 }
@@ -253,7 +258,8 @@ RESAMPLE_MODES = {"down": 1, "up": 2, "stride2": 3, "zero2": 4}
 
 class Recorder:
     """Patches (through pytest's monkeypatch) every launch symbol on both libraries -- the census, and adm_conv's record -- and
-    the attention / GroupNorm / token / resample / layout / VAE / conv2d / classifier-head wrappers of ops (the other records)."""
+    the attention / GroupNorm / token / resample / layout / VAE / conv2d / classifier-head / embedding wrappers of ops (the other
+    records)."""
 
     def __init__(self, monkeypatch):
         from autodiffusion_amd import _lib, ops
@@ -420,7 +426,19 @@ class Recorder:
             self._add(("logsoftmax_grad", "bf16", logits.shape[0], logits.shape[1], float(scale)))
             return o_lsg(logits, y, scale)
 
-        for name, fn in (("attention", attention), ("attention_cross", attention_cross), ("attention_bwd", attention_bwd),
+        o_lin, o_temb = ops.linear_f32, ops.timestep_embedding
+
+        # fp32 kernels that ops launches from the bf16 library whatever the torso
+        def linear_f32(x, w, b=None, silu_in=False, table=None, idx=None, out=None):
+            aligned = x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0
+            self._add(("linear_f32", "bf16", x.shape[0], x.shape[1], w.shape[0], bool(silu_in), b is not None, table is not None, aligned))
+            return o_lin(x, w, b, silu_in, table, idx, out)
+
+        def timestep_embedding(t, dim, max_period=10000.0):
+            self._add(("timestep_embedding", "bf16", t.shape[0], int(dim), float(max_period)))
+            return o_temb(t, dim, max_period)
+
+        for name, fn in (("linear_f32", linear_f32), ("timestep_embedding", timestep_embedding), ("attention", attention), ("attention_cross", attention_cross), ("attention_bwd", attention_bwd),
                          ("gn_affine", gn_affine), ("gn_bwd", gn_bwd), ("layernorm", layernorm), ("layernorm_f32out", layernorm_f32out),
                          ("geglu", geglu), ("quick_gelu", quick_gelu), ("attention_causal", attention_causal), ("clip_embed", clip_embed),
                          ("resample", resample), ("nchw_to_nhwc_pad", nchw_to_nhwc_pad), ("vae_latent_in", vae_latent_in),
@@ -465,6 +483,11 @@ def families(rec: tuple) -> set:
     elif op == "attention_cross":
         _, _, n, tq, qs, rows, kvs, tk, heads, d, scale = rec
         out.add(f"attention_cross d {d} ({'self' if tk == tq and qs == kvs else 'cross'})")
+    elif op == "linear_f32":
+        _, _, n, k, o, silu_in, has_bias, has_table, aligned = rec
+        out.update({op, f"linear_f32 {linear_path(k, aligned)}"})   # which of the three kernels ran: by k and alignment alone
+        if has_table:
+            out.add("linear_f32 table")
     else:
         out.add(op)
     return {(kind, f) for f in out}
@@ -490,7 +513,14 @@ HEAD_KINDS = ("pool_prep", "pool_attn_fwd", "pool_attn_bwd", "pool_prep_bwd", "c
               "vec_gn_bwd", "logsoftmax_grad")
 NEW_KINDS = TOKEN_KINDS + HEAD_KINDS
 REQUIRED_FAMILIES += list(HEAD_KINDS)
-REPLAYED = {"conv", "attention", "attention_cross", "attention_bwd", "gn_bwd", "gn_affine"} | set(NEW_KINDS)
+# the fp32 embedding path: the two kinds, the linear kernels the models reach -- the matrix pipe (k % 16 == 0: time_embed, every
+# emb_layers) and the GEMV (k % 4 == 0, k % 16 != 0: the attention pool's 1000-wide backward projection); no model reaches the
+# 64x64 tile kernel (k % 4 != 0, or misaligned operands) -- and the label table's gather-add
+EMBED_KINDS = ("linear_f32", "timestep_embedding")
+EMBED_FAMILIES = EMBED_KINDS + ("linear_f32 mfma", "linear_f32 gemv", "linear_f32 table")
+REQUIRED_FAMILIES += list(EMBED_FAMILIES)
+ONE_LIBRARY_FAMILIES.update({f: "bf16" for f in EMBED_FAMILIES})
+REPLAYED = {"conv", "attention", "attention_cross", "attention_bwd", "gn_bwd", "gn_affine"} | set(NEW_KINDS) | set(EMBED_KINDS)
 
 
 def missing_families(records) -> list:

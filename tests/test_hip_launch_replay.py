@@ -4,7 +4,8 @@ The models (built as tests/test_hip_fullsize.py, tests/test_hip_sd_vae.py and te
 values do not matter, only the launch list does) run eagerly at the batches bench.py uses and at batch 1-2, in the bf16 and the
 fp16 torso, under tests/launch_replay.Recorder: ADM-64 / 128 / 256, the classifiers (the shipped attention-pool ones, and the
 adaptive / spatial / spatial_v2 heads at width 64), the SD latent UNet, the KL-f8 VAE decoder
-(with the image exit that follows it) and the CLIP text encoder.  Each distinct record is then launched again through the same
+(with the image exit that follows it) and the CLIP text encoder.  The fp32 embedding path rides along: every adm_linear_f32 and
+adm_timestep_embedding launch of those evaluations is a record too (tests/f32_kernels.py states and bounds them).  Each distinct record is then launched again through the same
 entry point with fresh seeded operands and compared element by element with the float64 restatement of tests/launch_replay.py,
 within the per-element bounds derived there (and tested on the host by tests/test_launch_replay_host.py).  Large conv maps are
 compared at the corners of every 16x16 (8x8) output tile of every image plus seeded random pixels, all channels.  A coverage
@@ -183,7 +184,7 @@ def test_recorded_launches_cover_every_known_family(recorded):
         print(f"{kind}: {len([r for r in recorded.records if r[1] == kind])} distinct launches; families {have}")
         print(f"{kind}: launch symbols called: {sorted(s for s, k in recorded.census if k == kind)}")
         print(f"{kind}: distinct launches per new kind: "
-              f"{ {op: sum(1 for r in recorded.records if r[0] == op and r[1] == kind) for op in lr.NEW_KINDS} }")
+              f"{ {op: sum(1 for r in recorded.records if r[0] == op and r[1] == kind) for op in lr.NEW_KINDS + lr.EMBED_KINDS} }")
     missing = lr.missing_families(recorded.records)
     assert not missing, f"the models no longer reach (or the recorder missed) {missing}"
     # every kind of record is replayed below: a new kind must get a restatement, not be dropped
@@ -518,7 +519,7 @@ def test_groupnorm_affine_launches_match_float64(ops, recorded):
 
 
 # ------------------------------------------------------------------ token, resample, layout, VAE entry / exit, stride-2 conv
-SEEDS = {k: 6000 + 1000 * i for i, k in enumerate(lr.NEW_KINDS)}
+SEEDS = {k: 6000 + 1000 * i for i, k in enumerate(lr.NEW_KINDS + lr.EMBED_KINDS)}
 
 
 def _replay_kind(name, recorded, replay, roundings=1):
@@ -1163,6 +1164,54 @@ def test_vec_gn_bwd_launches_match_float64(ops, recorded):
 
 def test_logsoftmax_grad_launches_match_float64(ops, recorded):
     _replay_head("logsoftmax_grad", recorded, _check_logsoftmax_grad)
+
+
+# ------------------------------------------------------------------ the fp32 embedding path
+LABEL_ROWS = 1000
+
+
+def _check_linear_f32(n, k, o, silu_in, has_bias, has_table, aligned):
+    off = 0 if aligned else 1      # as recorded: operands one float into their buffers take the tile kernel
+    xb, wb = torch.randn(off + n * k, device=DEV), torch.randn(off + o * k, device=DEV) * k ** -0.5
+    x, w = xb[off:].view(n, k), wb[off:].view(o, k)
+    bias = 0.1 * torch.randn(o, device=DEV) if has_bias else None
+    table = idx = None
+    if has_table:
+        table = torch.randn(LABEL_ROWS, o, device=DEV)
+        idx = torch.randint(0, LABEL_ROWS, (n,), device=DEV)
+        idx[0], idx[-1] = 0, LABEL_ROWS - 1
+        if n > 2:
+            idx[1] = idx[2] = 7          # a repeated row
+    buf, out = _owned((n, o), torch.float32)
+    _call("bf16", "adm_linear_f32", _p(x), _p(w), _p(bias), _p(table), _p(idx), _p(buf), n, k, o, int(silu_in))
+    _guard_ok(buf, "adm_linear_f32")
+    ref, bound = lr.linear_restate(x, w, bias, table, idx, silu_in)
+    wr, _, _, rep = lr.worst_ratio(out, ref, bound)
+    return wr, None, rep
+
+
+def _check_timestep_embedding(n, dim, max_period):
+    t = torch.randint(0, 1000, (n,), device=DEV).float()
+    t[0], t[-1] = 0.0, 999.0
+    buf, out = _owned((n, dim), torch.float32)
+    _call("bf16", "adm_timestep_embedding", _p(t), _p(buf), n, dim, max_period)
+    _guard_ok(buf, "adm_timestep_embedding")
+    ref, bound = lr.timestep_restate(t, dim, max_period)
+    inside = 2 * (dim // 2)
+    if bool(out[:, inside:].contiguous().view(torch.int32).any()):
+        return float("inf"), None, "the odd column is not +0"
+    wr, _, _, rep = lr.worst_ratio(out[:, :inside], ref[:, :inside], bound[:, :inside])
+    return wr, None, rep
+
+
+def test_linear_f32_launches_match_float64(ops, recorded):
+    _replay_head("linear_f32", recorded, _check_linear_f32)
+    ks = {r[3] for r in recorded.records if r[0] == "linear_f32"}
+    assert any(k % 16 == 0 for k in ks) and any(k % 4 == 0 and k % 16 for k in ks), sorted(ks)
+
+
+def test_timestep_embedding_launches_match_float64(ops, recorded):
+    _replay_head("timestep_embedding", recorded, _check_timestep_embedding)
 
 
 # ------------------------------------------------------------------ the same kernels at the smallest shapes that can still go wrong

@@ -307,7 +307,7 @@ def test_coverage_guard_fails_when_a_model_or_a_hook_is_removed():
     here = {s: cov for s, cov in lr.SYMBOL_COVERAGE.items() if cov[0] != "elsewhere" and set(cov) & set(lr.NEW_KINDS)}
     one_library = {"adm_" + f for f, k in lr.ONE_LIBRARY_FAMILIES.items() if k == "bf16"}   # fp32 kernels on the bf16 library alone
     census = {(s, k) for s in here for k in ("bf16", "f16") if not (s in one_library and k == "f16")}
-    census |= {("adm_linear_f32", "bf16")}   # held elsewhere: needs no record
+    census |= {("adm_stem_conv3x3", "bf16")}   # held elsewhere: needs no record
     assert lr.coverage_gaps(census, recs.values(), lr.REPLAYED) == []
     new = set(lr.NEW_KINDS) | {"attention d 512", "non-square map"}
     assert not [m for m in lr.missing_families(recs.values()) if m[1] in new]
@@ -641,7 +641,7 @@ def test_head_kinds_are_listed_required_and_replayed():
     assert set(lr.HEAD_KINDS) <= lr.REPLAYED
     for k in lr.HEAD_KINDS:
         assert lr.SYMBOL_COVERAGE["adm_" + k] == (k,)
-    assert {f for f, lib in lr.ONE_LIBRARY_FAMILIES.items() if lib == "bf16"} == {"vae_image_out"} | set(F32_LIBRARY_KINDS)
+    assert {f for f, lib in lr.ONE_LIBRARY_FAMILIES.items() if lib == "bf16"} == {"vae_image_out"} | set(F32_LIBRARY_KINDS) | set(lr.EMBED_FAMILIES)
     assert lr.SYMBOL_COVERAGE["adm_grad_add"] == ("elsewhere", "tests/test_hip_launch_replay.py::test_grad_add_at_edges")
     recs = _fake_head_records()
     for (k, lib), r in recs.items():
@@ -690,6 +690,67 @@ def test_recorder_hooks_every_head_wrapper():
                                ("channel_mean", "f16", 2, 64, 64, False, 32, 96), ("bcast_add", "bf16", 2, 64, 64, False, 16, 96),
                                ("vec_act", "bf16", 192, 2, True), ("vec_gn", "bf16", 2, 96, 1e-5), ("vec_gn_bwd", "bf16", 2, 96),
                                ("logsoftmax_grad", "bf16", 2, 96, 1024.0)}
+
+
+# ------------------------------------------------------------------ the fp32 embedding path as record kinds
+def _fake_embed_records():
+    """The embedding path's records as the recorder shapes them, on the bf16 library that ops launches the fp32 kernels from: every
+    emb_layers at batch 256 (matrix pipe), the attention pool's 1000-wide backward projection (GEMV), time_embed's second Linear
+    with the label table, and the sinusoid."""
+    return {("emb_layers", "bf16"): ("linear_f32", "bf16", 256, 768, 33792, True, True, False, True),
+            ("pool backward", "bf16"): ("linear_f32", "bf16", 2, 1000, 512, False, False, False, True),
+            ("label table", "bf16"): ("linear_f32", "bf16", 2, 768, 768, True, True, True, True),
+            ("timestep_embedding", "bf16"): ("timestep_embedding", "bf16", 2, 192, 10000.0)}
+
+
+def test_embedding_kinds_are_required_replayed_and_guarded():
+    assert lr.SYMBOL_COVERAGE["adm_linear_f32"] == ("linear_f32",) and lr.SYMBOL_COVERAGE["adm_timestep_embedding"] == ("timestep_embedding",)
+    assert set(lr.EMBED_KINDS) <= lr.REPLAYED and set(lr.EMBED_FAMILIES) <= set(lr.REQUIRED_FAMILIES)
+    recs = _fake_embed_records()
+    assert lr.families(recs[("emb_layers", "bf16")]) == {("bf16", "linear_f32"), ("bf16", "linear_f32 mfma")}
+    assert lr.families(recs[("pool backward", "bf16")]) == {("bf16", "linear_f32"), ("bf16", "linear_f32 gemv")}
+    assert lr.families(recs[("label table", "bf16")]) == {("bf16", "linear_f32"), ("bf16", "linear_f32 mfma"), ("bf16", "linear_f32 table")}
+    assert lr.families(("linear_f32", "bf16", 2, 30, 8, False, True, False, True)) == {("bf16", "linear_f32"), ("bf16", "linear_f32 tile")}
+    assert lr.families(("linear_f32", "bf16", 2, 32, 8, False, True, False, False)) == {("bf16", "linear_f32"), ("bf16", "linear_f32 tile")}
+    assert lr.families(recs[("timestep_embedding", "bf16")]) == {("bf16", "timestep_embedding")}
+    # the stubbed census: both symbols called on the bf16 library
+    census = {("adm_linear_f32", "bf16"), ("adm_timestep_embedding", "bf16")}
+    embed = set(lr.EMBED_FAMILIES)
+    assert lr.coverage_gaps(census, recs.values(), lr.REPLAYED) == []
+    assert not [m for m in lr.missing_families(recs.values()) if m[1] in embed]
+    # one hook removed from the recorder: the census still sees the symbol, the guard names the missing record kind
+    left = [r for r in recs.values() if r[0] != "linear_f32"]
+    gaps = lr.coverage_gaps(census, left, lr.REPLAYED)
+    assert len(gaps) == 1 and "adm_linear_f32" in gaps[0] and "no linear_f32 record" in gaps[0]
+    assert {m for m in lr.missing_families(left) if m[1] in embed} == {("bf16", f) for f in embed - {"timestep_embedding"}}
+    left = [r for r in recs.values() if r[0] != "timestep_embedding"]
+    gaps = lr.coverage_gaps(census, left, lr.REPLAYED)
+    assert len(gaps) == 1 and "adm_timestep_embedding" in gaps[0] and "no timestep_embedding record" in gaps[0]
+    assert {m for m in lr.missing_families(left) if m[1] in embed} == {("bf16", "timestep_embedding")}
+    # a model dropped: without the classifier's backward projection the GEMV family is missing, without the class-conditional
+    # UNets the table's
+    for gone, fam in (("pool backward", "linear_f32 gemv"), ("label table", "linear_f32 table")):
+        left = [r for k, r in recs.items() if k[0] != gone]
+        assert {m for m in lr.missing_families(left) if m[1] in embed} == {("bf16", fam)}
+    # a kind the replay does not take
+    assert "not replayed" in lr.coverage_gaps({("adm_linear_f32", "bf16")}, recs.values(), lr.REPLAYED - {"linear_f32"})[0]
+
+
+def test_recorder_hooks_the_embedding_wrappers():
+    """Both ops wrappers are replaced, and the hook records before it passes the call on (the call itself fails here: host tensors)."""
+    from autodiffusion_amd import ops
+    from autodiffusion_amd._lib import AdmError
+    with pytest.MonkeyPatch.context() as mp:
+        rec = lr.Recorder(mp)
+        x, w, b = torch.zeros(2, 20), torch.zeros(8, 20), torch.zeros(8)
+        for call in (lambda: ops.linear_f32(x, w, b, silu_in=True), lambda: ops.linear_f32(x, w, None, table=torch.zeros(3, 8), idx=torch.zeros(2, dtype=torch.int64)),
+                     lambda: ops.timestep_embedding(torch.zeros(3), 33), lambda: ops.timestep_embedding(torch.zeros(3), 32, 100)):
+            with pytest.raises(AdmError):
+                call()
+        al = x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0
+        assert rec.records == {("linear_f32", "bf16", 2, 20, 8, True, True, False, al), ("linear_f32", "bf16", 2, 20, 8, False, False, True, al),
+                               ("timestep_embedding", "bf16", 3, 33, 10000.0), ("timestep_embedding", "bf16", 3, 32, 100.0)}
+    assert ops.linear_f32.__module__ == "autodiffusion_amd.ops"   # the patch is undone
 
 
 def _silu32(z):
