@@ -1,0 +1,316 @@
+#!/usr/bin/env python3
+"""Evolutionary search over Stable-Diffusion sampling schedules on the HIP evaluation path -- the reference's
+"Stable Diffusion"/scripts/search_ea.py as a CLI over ``autodiffusion_amd.sd_search.EvolutionSearcher``.
+
+The reference's flags keep their names and defaults (search_ea.py:636-848): ``--plms --dpm_solver --fixed_code --ddim_eta --H --W
+--C --f --n_samples --scale --config --ckpt --seed --outdir --num_sample --max_epochs --select_num --population_num --m_prob
+--crossover_num --mutation_num --max_fid --thres --ref_mu --ref_sigma --time_step --use_ddim_init_x``.  ``--use_ddim_init_x`` is
+parsed by ``str2bool`` (the reference's ``type=bool`` turns the string ``False`` into True).  ``--precision --laion400m
+--skip_grid --skip_save --n_iter --n_rows --prompt --ddim_steps --cal_fid --data_dir`` are accepted and ignored; one log line
+names those that were given.
+
+Additions.  Prompts: ``--captions FILE`` -- a COCO-style JSON whose ``annotations[i]['caption'].lower()`` are taken in file order,
+or a text file with one caption per line -- batched ``--n_samples`` at a time with the last short batch dropped (what the
+reference's ``CocoDataset`` + ``DataLoader(shuffle=False, drop_last=True)`` feed), tokenised by the ``transformers`` tokenizer in
+the LOCAL directory ``--tokenizer_dir`` (nothing is fetched); or ``--prompt_ids FILE.npy``, an int64 [num, T] array of token ids,
+when no tokenizer is at hand (the empty prompt of classifier-free guidance is then built from the vocabulary's last two ids,
+CLIP's start- and end-of-text).  FID: ``--inception_path`` is the pytorch_fid checkpoint; without it the run needs
+``--allow_random_inception``, and every FID line then carries the "RANDOM Inception weights" note.  ``--ref_mu`` / ``--ref_sigma``
+take the reference's ``.npy`` pair; ``--ref_mu`` alone may name an ``.npz`` holding ``mu`` and ``sigma`` (what
+``scripts/evaluator.py --save_ref_stats`` writes).  ``--torso {bf16,fp16}`` selects the 16-bit torso; ``--population_parallel``
+shards whole candidates over ranks (candidate i on rank i % world, one all_gather of the FIDs per epoch).
+``--evaluate "[t0, t1, ...]"`` scores that one candidate over ``--num_sample`` images, prints the FID and exits (the reference's
+txt2img_fid.py use of a searched schedule).  ``--synthetic {tiny,v1}`` builds the networks with ``randomize_()`` instead of
+reading ``--ckpt``: tests and throughput runs.
+
+Loading: ``--ckpt`` is read with ``torch.load(map_location="cpu")`` and its ``"state_dict"`` (or the dict itself) goes through
+``LatentDiffusion.load_state_dict``.  ``--config``, when given, is read with PyYAML and supplies ``model.params.{timesteps,
+linear_start, linear_end, scale_factor}`` and the ``params`` of ``unet_config``, ``first_stage_config`` and ``cond_stage_config``;
+without it the SD-v1 constants of the package are used.
+
+``OUTDIR/log.txt`` gets the reference's lines: the ``population_num = ...`` header, ``epoch = e``, ``epoch = e : top n result``,
+``No.i cand fid = v`` and ``total searching time = ... hours`` (ranks > 0 write ``log-rankNNN.txt``).
+"""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from autodiffusion_amd import dist_util, logger  # noqa: E402
+from autodiffusion_amd.script_util import str2bool  # noqa: E402
+from autodiffusion_amd.sd_search import EvolutionSearcher, dpm_search_params, parse_sd_candidate  # noqa: E402
+
+IGNORED = ("precision", "laion400m", "skip_grid", "skip_save", "n_iter", "n_rows", "prompt", "ddim_steps", "cal_fid", "data_dir")
+
+# --synthetic tiny: the smallest networks the test suite runs (a 64-wide two-level UNet, a three-level decoder that turns an
+# h x w latent into a 4h x 4w image, a one-layer text transformer of the UNet's context width over 512 token ids)
+TINY_UNET = dict(in_channels=4, out_channels=4, model_channels=64, attention_resolutions=[1, 2], num_res_blocks=1,
+                 channel_mult=[1, 2], num_heads=2, transformer_depth=1, context_dim=128, legacy=False)
+TINY_VAE = dict(ddconfig=dict(ch=32, out_ch=3, ch_mult=(1, 2, 4), num_res_blocks=1, attn_resolutions=[], dropout=0.0, in_channels=3,
+                              resolution=32, z_channels=4), embed_dim=4)
+TINY_CLIP = dict(vocab_size=512, hidden_size=128, intermediate_size=512, num_hidden_layers=1, num_attention_heads=2,
+                 max_position_embeddings=77)
+
+
+def create_argparser():
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    # ---- the reference's flags (search_ea.py:636-848)
+    p.add_argument("--outdir", type=str, nargs="?", help="dir to write results to", default="outputs/txt2img-samples")
+    p.add_argument("--plms", action="store_true", help="use plms sampling")
+    p.add_argument("--dpm_solver", action="store_true", help="use dpm_solver sampling")
+    p.add_argument("--fixed_code", action="store_true", help="if enabled, uses the same starting code across samples")
+    p.add_argument("--ddim_eta", type=float, default=0.0, help="ddim eta (eta=0.0 corresponds to deterministic sampling)")
+    p.add_argument("--H", type=int, default=512, help="image height, in pixel space")
+    p.add_argument("--W", type=int, default=512, help="image width, in pixel space")
+    p.add_argument("--C", type=int, default=4, help="latent channels")
+    p.add_argument("--f", type=int, default=8, help="downsampling factor")
+    p.add_argument("--n_samples", type=int, default=3, help="how many samples to produce for each given prompt. A.k.a. batch size")
+    p.add_argument("--scale", type=float, default=7.5,
+                   help="unconditional guidance scale: eps = eps(x, empty) + scale * (eps(x, cond) - eps(x, empty))")
+    p.add_argument("--config", type=str, default="configs/stable-diffusion/v1-inference.yaml",
+                   help="path to config which constructs model (read when the file exists; else the SD-v1 constants)")
+    p.add_argument("--ckpt", type=str, default="models/ldm/stable-diffusion-v1/model.ckpt", help="path to checkpoint of model")
+    p.add_argument("--seed", type=int, default=42, help="the seed (for reproducible sampling)")
+    p.add_argument("--num_sample", type=int, default=4, help="samples num")
+    p.add_argument("--max_epochs", type=int, default=10)
+    p.add_argument("--select_num", type=int, default=10)
+    p.add_argument("--population_num", type=int, default=50)
+    p.add_argument("--m_prob", type=float, default=0.1)
+    p.add_argument("--crossover_num", type=int, default=25)
+    p.add_argument("--mutation_num", type=int, default=25)
+    p.add_argument("--max_fid", type=float, default=3.)
+    p.add_argument("--thres", type=float, default=0.2)
+    p.add_argument("--ref_mu", type=str, default="", help="reference mean (.npy), or an .npz holding mu and sigma")
+    p.add_argument("--ref_sigma", type=str, default="", help="reference covariance (.npy)")
+    p.add_argument("--time_step", type=int, default=50)
+    p.add_argument("--use_ddim_init_x", type=str2bool, default=False,
+                   help="seed the population with the evenly spaced schedule; parsed as a boolean word (true/false/1/0/...): "
+                        "the reference's type=bool turns the string 'False' into True, this flag does not")
+    # ---- accepted and ignored
+    p.add_argument("--prompt", type=str, nargs="?", default=None, help="ignored (the prompts come from --captions / --prompt_ids)")
+    p.add_argument("--skip_grid", action="store_true", default=None, help="ignored")
+    p.add_argument("--skip_save", action="store_true", default=None, help="ignored")
+    p.add_argument("--ddim_steps", type=int, default=None, help="ignored (--time_step is the number of steps)")
+    p.add_argument("--laion400m", action="store_true", default=None, help="ignored")
+    p.add_argument("--n_iter", type=int, default=None, help="ignored")
+    p.add_argument("--n_rows", type=int, default=None, help="ignored")
+    p.add_argument("--precision", type=str, choices=["full", "autocast"], default=None, help="ignored (see --torso)")
+    p.add_argument("--data_dir", type=str, default=None, help="ignored (see --captions)")
+    p.add_argument("--cal_fid", type=str, default=None, help="ignored")
+    # ---- additions
+    p.add_argument("--captions", type=str, default="", help="COCO-style annotations JSON, or a text file with one caption per line")
+    p.add_argument("--tokenizer_dir", type=str, default="", help="LOCAL directory of the transformers CLIP tokenizer (nothing is fetched)")
+    p.add_argument("--prompt_ids", type=str, default="",
+                   help=".npy int64 [num, T] token ids; replaces --captions and --tokenizer_dir (the empty prompt of classifier-free "
+                        "guidance is then T ids: start-of-text, then end-of-text, the last two ids of the vocabulary)")
+    p.add_argument("--inception_path", type=str, default="", help="the pytorch_fid Inception checkpoint (pt_inception-2015-12-05)")
+    p.add_argument("--allow_random_inception", action="store_true",
+                   help="run without --inception_path: every FID line is then tagged as computed on RANDOM Inception weights")
+    p.add_argument("--torso", choices=["bf16", "fp16"], default="bf16", help="16-bit type of activations and weights between kernels")
+    p.add_argument("--population_parallel", action="store_true", help="evaluate candidate i on rank i %% world, one all_gather per epoch")
+    p.add_argument("--evaluate", type=str, default="", help="'[t0, t1, ...]': score this one candidate, print its FID and exit")
+    p.add_argument("--synthetic", choices=["tiny", "v1"], default="", help="build the networks with randomize_() instead of reading --ckpt")
+    return p
+
+
+# ------------------------------------------------------------------ prompts
+def read_captions(path):
+    """COCO-style JSON -> annotations[i]['caption'].lower() in file order (ldm/data/coco.py:36-46); otherwise one caption per line."""
+    with open(path, "r", encoding="utf-8") as f:
+        text = f.read()
+    if text.lstrip().startswith("{"):
+        return [a["caption"].lower() for a in json.loads(text)["annotations"]]
+    return [line.strip() for line in text.splitlines() if line.strip()]
+
+
+def batch_captions(captions, n_samples):
+    """DataLoader(batch_size=n_samples, shuffle=False, drop_last=True) (build_dataloader.py:66-73): batches of {'text': [...]}."""
+    return [{"text": list(captions[i:i + n_samples])} for i in range(0, len(captions) - n_samples + 1, n_samples)]
+
+
+def build_loader(opt, device):
+    if opt.prompt_ids:
+        ids = np.load(opt.prompt_ids, allow_pickle=False)
+        if ids.ndim != 2 or not np.issubdtype(ids.dtype, np.integer):
+            raise SystemExit(f"sd_search_ea.py: --prompt_ids must hold an integer [num, T] array, got {ids.dtype} {ids.shape}")
+        ids = torch.from_numpy(ids.astype(np.int64)).to(device)
+        loader = [{"text": ids[i:i + opt.n_samples]} for i in range(0, ids.shape[0] - opt.n_samples + 1, opt.n_samples)]
+    elif opt.captions:
+        if not opt.tokenizer_dir:
+            raise SystemExit("sd_search_ea.py: --captions needs --tokenizer_dir (a local CLIP tokenizer directory); "
+                             "or pass token ids with --prompt_ids")
+        loader = batch_captions(read_captions(opt.captions), opt.n_samples)
+    else:
+        raise SystemExit("sd_search_ea.py: give --captions FILE (with --tokenizer_dir DIR) or --prompt_ids FILE.npy")
+    if not loader:
+        raise SystemExit(f"sd_search_ea.py: fewer prompts than one batch of --n_samples {opt.n_samples}")
+    return loader
+
+
+class EmptyPromptTokenizer:
+    """Stands in for the CLIP tokenizer in a --prompt_ids run, which has one string left to tokenise: the empty prompt of
+    classifier-free guidance.  CLIP's tokenizer turns "" into <|startoftext|> followed by <|endoftext|> up to max_length (its pad
+    token is <|endoftext|>), and those two are the last two ids of its vocabulary (49406 and 49407 of 49408)."""
+
+    def __init__(self, vocab_size):
+        self.bos, self.eos = int(vocab_size) - 2, int(vocab_size) - 1
+
+    def __call__(self, text, max_length, **kw):
+        if any(t != "" for t in text):
+            raise SystemExit("sd_search_ea.py: a --prompt_ids run has no tokenizer for strings; give --tokenizer_dir")
+        ids = torch.full((len(text), max_length), self.eos, dtype=torch.int64)
+        ids[:, 0] = self.bos
+        return {"input_ids": ids}
+
+
+# ------------------------------------------------------------------ reference statistics
+def load_ref_stats(opt):
+    if opt.ref_mu.endswith(".npz") and not opt.ref_sigma:
+        z = np.load(opt.ref_mu, allow_pickle=False)
+        return np.asarray(z["mu"], dtype=np.float64), np.asarray(z["sigma"], dtype=np.float64)
+    if not opt.ref_mu or not opt.ref_sigma:
+        raise SystemExit("sd_search_ea.py: give --ref_mu MU.npy --ref_sigma SIGMA.npy, or --ref_mu STATS.npz holding mu and sigma")
+    return (np.asarray(np.load(opt.ref_mu, allow_pickle=False), dtype=np.float64),
+            np.asarray(np.load(opt.ref_sigma, allow_pickle=False), dtype=np.float64))
+
+
+# ------------------------------------------------------------------ networks
+def build_model(opt, device, prompt_len=None):
+    """LatentDiffusion (UNet + first stage + cond stage) on `device`: synthetic weights, or --ckpt under --config / the v1 constants.
+    prompt_len: the T of --prompt_ids; without --tokenizer_dir the empty prompt is then built as T ids by EmptyPromptTokenizer."""
+    from autodiffusion_amd.sd_arch import SD_V1
+    from autodiffusion_amd.sd_clip import CLIP_VIT_L14_TEXT, FrozenCLIPEmbedder
+    from autodiffusion_amd.sd_sampler import LatentDiffusion
+    from autodiffusion_amd.sd_unet import UNetModel
+    from autodiffusion_amd.sd_vae import SD_V1_VAE, AutoencoderKL
+    unet_cfg = dict(image_size=32, use_spatial_transformer=True, **SD_V1)
+    vae_cfg, clip_cfg, ld_cfg = dict(SD_V1_VAE), dict(config=CLIP_VIT_L14_TEXT), {}
+    if opt.synthetic == "tiny":
+        unet_cfg = dict(image_size=32, use_spatial_transformer=True, **TINY_UNET)
+        vae_cfg, clip_cfg = dict(TINY_VAE), dict(config=TINY_CLIP)
+    elif not opt.synthetic and opt.config and os.path.isfile(opt.config):
+        import yaml
+        with open(opt.config, "r", encoding="utf-8") as f:
+            params = yaml.safe_load(f)["model"]["params"]
+        ld_cfg = {k: params[k] for k in ("timesteps", "linear_start", "linear_end", "scale_factor") if k in params}
+        unet_cfg = dict(params["unet_config"].get("params") or {})
+        vae_cfg = dict(params["first_stage_config"].get("params") or {})
+        clip_cfg = dict(params["cond_stage_config"].get("params") or {})
+        clip_cfg.pop("device", None)
+        logger.log(f"model configuration from {opt.config}")
+    elif not opt.synthetic:
+        logger.log(f"--config {opt.config} is not a file: using the SD-v1 constants of the package")
+    if opt.tokenizer_dir:
+        clip_cfg["version"] = opt.tokenizer_dir
+    unet = UNetModel(**unet_cfg).set_torso(opt.torso)
+    vae = AutoencoderKL(**vae_cfg).set_torso(opt.torso)
+    if prompt_len is not None and not opt.tokenizer_dir:
+        clip_cfg["max_length"] = int(prompt_len)
+    clip = FrozenCLIPEmbedder(device="cpu", **clip_cfg).set_torso(opt.torso)
+    if prompt_len is not None and not opt.tokenizer_dir:
+        clip._tokenizer = EmptyPromptTokenizer(clip.transformer.plan.vocab_size)
+    if opt.synthetic:
+        unet.randomize_(1234)
+        vae.randomize_(4321)
+        clip.randomize_(2468)
+        logger.log(f"--synthetic {opt.synthetic}: the networks hold RANDOM weights (randomize_()); --ckpt is not read")
+    unet.to(device)
+    vae.to(device)
+    clip.to(device)
+    model = LatentDiffusion(unet, device=device, first_stage=vae, cond_stage=clip, **ld_cfg)
+    if not opt.synthetic:
+        print(f"Loading model from {opt.ckpt}")
+        pl_sd = torch.load(opt.ckpt, map_location="cpu")
+        if "global_step" in pl_sd:
+            print(f"Global Step: {pl_sd['global_step']}")
+        model.load_state_dict(pl_sd["state_dict"] if "state_dict" in pl_sd else pl_sd, strict=False)
+    return model
+
+
+def build_inception(opt, device):
+    from autodiffusion_amd.inception import InceptionV3
+    if not opt.inception_path and not opt.allow_random_inception:
+        raise SystemExit("sd_search_ea.py: give --inception_path (the pytorch_fid pt_inception-2015-12-05 state_dict); FID on "
+                         "random Inception weights ranks candidates on a meaningless metric (--allow_random_inception opts in "
+                         "for throughput runs and tests)")
+    net = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[2048]]).to(device)
+    if opt.inception_path:
+        net.load_state_dict(dist_util.load_state_dict(opt.inception_path))
+    else:
+        logger.log("WARNING: FID features come from an Inception-v3 with RANDOM weights (--allow_random_inception): "
+                   "every fid value below is NOT a quality metric")
+    return net
+
+
+def build_sampler(opt, model):
+    from autodiffusion_amd.sd_sampler import DDIMSampler, DPMSolverSampler, PLMSSampler
+    if opt.dpm_solver:
+        return DPMSolverSampler(model)
+    if opt.plms:
+        return PLMSSampler(model)
+    return DDIMSampler(model)
+
+
+def main(argv=None, *, evaluator=None):
+    """Returns the searcher after a search, or the FID under --evaluate.  ``evaluator=`` injects a candidate evaluator (an
+    object with ``get_cand_fid(cand, opt)``) in place of the networks: host tests of the command line."""
+    opt = create_argparser().parse_args(argv)
+    ignored = [k for k in IGNORED if getattr(opt, k) is not None]
+    random.seed(opt.seed)      # pytorch_lightning.seed_everything(opt.seed): random, numpy, torch
+    np.random.seed(opt.seed)
+    torch.manual_seed(opt.seed)
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        dist_util.setup_dist()
+    logger.configure(opt.outdir)
+    logger.log(str(opt))
+    if ignored:
+        logger.log("ignored flags (accepted for the reference's command lines, unused on this path): "
+                   + ", ".join("--" + k for k in ignored))
+    ref_mu, ref_sigma = load_ref_stats(opt)
+    model = sampler = inception = None
+    dpm_params = None
+    if evaluator is None:
+        device = dist_util.dev()
+        if device.type != "cuda":
+            raise SystemExit("sd_search_ea.py: no GPU is visible (the HIP path has no CPU fallback)")
+        torch.cuda.set_device(device)
+        loader = build_loader(opt, device)
+        ids = loader[0]["text"]
+        model = build_model(opt, device, prompt_len=ids.shape[1] if torch.is_tensor(ids) else None)
+        sampler = build_sampler(opt, model)
+        inception = build_inception(opt, device)
+        alphas_cumprod = model.alphas_cumprod
+    else:
+        loader = []
+        sampler = type("Sampler", (), {"ddpm_num_timesteps": 1000})()
+        alphas_cumprod = range(1000)
+    if opt.dpm_solver:
+        dpm_params = dpm_search_params(alphas_cumprod, opt.time_step)
+    t = time.time()
+    searcher = EvolutionSearcher(opt=opt, model=model, time_step=opt.time_step, ref_mu=ref_mu, ref_sigma=ref_sigma, sampler=sampler,
+                                 dataloader_info={"validation_loader": loader}, batch_size=opt.n_samples, dpm_params=dpm_params,
+                                 evaluator=evaluator, population_parallel=opt.population_parallel, inception=inception,
+                                 allow_random_inception=opt.allow_random_inception)
+    if opt.evaluate:
+        cand = parse_sd_candidate(opt.evaluate, "--evaluate")
+        want = opt.time_step + (1 if opt.dpm_solver else 0)
+        if len(cand) != want:
+            raise SystemExit(f"sd_search_ea.py: --evaluate holds {len(cand)} entries; --time_step {opt.time_step} "
+                             f"{'with --dpm_solver ' if opt.dpm_solver else ''}needs {want}")
+        fid = searcher.get_cand_fid(cand=cand, opt=opt)
+        logger.log('cand: {}, fid: {}'.format(cand, fid) + searcher.fid_note)
+        return fid
+    searcher.search()
+    logger.log('total searching time = {:.2f} hours'.format((time.time() - t) / 3600))
+    return searcher
+
+
+if __name__ == "__main__":
+    main()
