@@ -22,6 +22,7 @@ import time
 import pytest
 import torch
 
+import guarded as gd
 import launch_replay as lr
 
 pytestmark = pytest.mark.gpu
@@ -201,124 +202,26 @@ REPLAYED = lr.REPLAYED
 
 
 # ------------------------------------------------------------------ conv replay
-def _conv_operands(ops, d, T, seed):
-    torch.manual_seed(seed)
-    n, h, w, c0, c1, cout, taps = d["n"], d["h"], d["w"], d["c0"], d["c1"], d["cout"], d["taps"]
-    up = d["up_phase"]
-    if up not in (0, 5) or d["prologue"] not in (0, 1, 2, 3):
-        raise NotImplementedError(f"the restatement does not express up_phase {up} / prologue {d['prologue']}")
-    hi, wi = (h // 2, w // 2) if d["in_up"] else (h, w)
-    ho, wo = (2 * h, 2 * w) if up else (h, w)
-    cin, k = c0 + c1, (3 if taps == 9 else 1)
-    t = {"x0": torch.randn(n, hi, wi, c0, device=DEV).to(T), "x1": torch.randn(n, hi, wi, c1, device=DEV).to(T) if d["has_in1"] else None}
-    w32 = torch.randn(cout, cin, k, k, device=DEV) * (cin * taps) ** -0.5
-    bias = 0.1 * torch.randn(cout, device=DEV) if d["prologue"] != 3 else torch.zeros(cout, device=DEV)  # backward-data convs: no bias
-    w32p = None
-    if up:
-        packed, t["w"] = ops.pack_conv_weight_up(w32, T), lr.round_t(ops.up_phase_weights(w32), T)
-    elif d["geglu"]:
-        wi_, bias = ops.geglu_interleave(w32[:, :, 0, 0], bias)
-        packed, t["w"] = ops.pack_conv_weight(wi_[:, :, None, None], T), lr.round_t(wi_[:, :, None, None], T)
-    else:
-        packed, t["w"] = ops.pack_conv_weight(w32, T), lr.round_t(w32, T)
-        if d["has_w_packed32"]:
-            w32p = ops.pack_conv_weight32(w32, T)
-    if d["has_fold0"]:
-        fc = d["fc0"] + d["fc1"]
-        w1 = torch.randn(cout, fc, device=DEV) * fc ** -0.5
-        packed = ops.fold_weights(packed, ops.pack_conv_weight(w1, T))
-        t["w1"] = lr.round_t(w1, T)
-        t["f0"] = torch.randn(n, h, w, d["fc0"], device=DEV).to(T)
-        t["f1"] = torch.randn(n, h, w, d["fc1"], device=DEV).to(T) if d["has_fold1"] else None
-    t["bias"] = bias
-    if d["prologue"] in (1, 2):
-        t["a"], t["b"] = 1 + 0.2 * torch.randn(n, cin, device=DEV), 0.2 * torch.randn(n, cin, device=DEV)
-    if d["prologue"] == 3:
-        t["gnb_a"], t["gnb_b"] = 1 + 0.2 * torch.randn(n, cout, device=DEV), 0.2 * torch.randn(n, cout, device=DEV)
-    if d["has_res"]:
-        t["res"] = torch.randn(n, h // 2 if d["res_up"] else ho, w // 2 if d["res_up"] else wo, cout, device=DEV).to(T)
-    if d["out_mode"] == 1:
-        out = torch.empty(n, cout, h, w, device=DEV)
-    else:
-        out = torch.empty(n, ho, wo, cout // 2 if d["geglu"] else cout, device=DEV, dtype=T)
-    return t, packed, w32p, out
+def _conv_operands(ops, d, T, seed, g=None):
+    return gd.conv_operands(ops, d, T, seed, DEV, g)
 
 
-def _launch_conv(lib, orig, d, t, packed, w32p, out):
-    from autodiffusion_amd._lib import ConvArgs, check
-    a = ConvArgs()
-    for name, _ in ConvArgs._fields_:
-        if name in d:
-            setattr(a, name, d[name])
-    keep = [packed, w32p]
-    a.in0, a.in1 = t["x0"].data_ptr(), (t["x1"].data_ptr() if t["x1"] is not None else None)
-    a.w_packed, a.bias, a.out = packed.data_ptr(), t["bias"].data_ptr(), out.data_ptr()
-    a.w_packed32 = w32p.data_ptr() if w32p is not None else None
-    if "a" in t:
-        a.aff_a, a.aff_b = t["a"].data_ptr(), t["b"].data_ptr()
-    if "gnb_a" in t:
-        a.aff_a, a.aff_b = t["gnb_a"].data_ptr(), t["gnb_b"].data_ptr()
-    a.res = t["res"].data_ptr() if "res" in t else None
-    if d["has_fold0"]:
-        a.fold0, a.fold1 = t["f0"].data_ptr(), (t["f1"].data_ptr() if t["f1"] is not None else None)
-    stats = None
-    if d["has_out_stats"]:
-        slabs = lib.adm_conv_stat_slabs(C.byref(a))
-        assert slabs > 0, d
-        stats = torch.empty(d["n"], slabs, d["cout"], 2, device=DEV)
-        a.out_stats = stats.data_ptr()
-    if d["ksplit"] > 1:
-        ws = torch.empty(d["ksplit"], d["n"] * d["h"] * d["w"], d["cout"], device=DEV)
-        keep.append(ws)
-        a.ws = ws.data_ptr()
-    check(orig(C.byref(a), torch.cuda.current_stream().cuda_stream), "adm_conv (replay)")
-    torch.cuda.synchronize()
-    return stats
+def _launch_conv(lib, orig, d, t, packed, w32p, out, g=None):
+    return gd.launch_conv(lib, orig, d, t, packed, w32p, out, g or gd.Guarded(DEV, guard_inputs=False))
 
 
 def _replay_conv(ops, orig, rec, seed):
+    """One recorded launch again: the output, the fused statistics and the split-K workspace are guarded carves (NaN inside,
+    sentinels around); the full-size inputs stay plain tensors."""
     from autodiffusion_amd import _lib
     d = lr.record_dict(rec)
     T = lr.KIND_DTYPE[rec[1]]
     lib = _lib.load(rec[1])
-    t, packed, w32p, out = _conv_operands(ops, d, T, seed)
-    stats = _launch_conv(lib, orig, d, t, packed, w32p, out)
-    n = d["n"]
-    ho, wo = (out.shape[2], out.shape[3]) if d["out_mode"] == 1 else (out.shape[1], out.shape[2])
-    img, oy, ox = lr.sample_pixels(n, ho, wo, seed)
-    cin = d["c0"] + d["c1"]
-    per = max(1, (1 << 25) // max(1, (ho * wo * cin)))   # images per reference chunk
-    worst, num, den = 0.0, 0.0, 0.0
-    outv = out.permute(0, 2, 3, 1) if d["out_mode"] == 1 else out
-    for i0 in range(0, n, per):
-        sel = (img >= i0) & (img < i0 + per)
-        ref, bound = lr.conv_restate(d, T, t, img[sel], oy[sel], ox[sel])
-        got = outv[img[sel].to(DEV), oy[sel].to(DEV), ox[sel].to(DEV)].double()
-        assert torch.isfinite(got).all(), f"non-finite output {rec}"
-        err = (got - ref).abs()
-        r = err / bound
-        if r.max().item() > 1.0:   # the worst element, for the failure report
-            j = int(r.argmax())
-            p, c = j // r.shape[1], j % r.shape[1]
-            print(f"  worst element img {int(img[sel][p])} y {int(oy[sel][p])} x {int(ox[sel][p])} ch {c}: got {got[p, c].item():.8g} "
-                  f"ref {ref[p, c].item():.8g} bound {bound[p, c].item():.4g} ulp_T(ref) {lr.ulp_t(ref[p, c], T).item():.4g}")
-        worst = max(worst, r.max().item())
-        num += (err ** 2).sum().item()
-        den += (ref ** 2).sum().item()
-    fro = (num / max(den, 1e-300)) ** 0.5
-    if stats is not None:   # fused output statistics: per (image, channel) sums over the stored tensor
-        y = outv.double()
-        if d["prologue"] == 3:
-            s1, s2 = y.sum((1, 2)), (y * t["res"].double()).sum((1, 2))
-            a1, a2 = y.abs().sum((1, 2)), (y * t["res"].double()).abs().sum((1, 2))
-        else:
-            s1, s2 = y.sum((1, 2)), (y * y).sum((1, 2))
-            a1, a2 = y.abs().sum((1, 2)), s2
-        tot = stats.double().sum(1)
-        tol = (256 + stats.shape[1] + 8) * 2.0 ** -24
-        se = max(((tot[..., 0] - s1).abs() / (tol * a1 + 1e-30)).max().item(), ((tot[..., 1] - s2).abs() / (tol * a2 + 1e-30)).max().item())
-        worst = max(worst, se)
-    return worst, fro
+    g = gd.Guarded(DEV, guard_inputs=False)
+    t, packed, w32p, out = _conv_operands(ops, d, T, seed, g)
+    stats = _launch_conv(lib, orig, d, t, packed, w32p, out, g)
+    g.check()
+    return gd.compare_conv(d, T, t, out, stats, seed, rec)
 
 
 def _label(rec):
@@ -356,17 +259,23 @@ def test_attention_launches_match_float64(ops, recorded):
     t0 = time.time()
     recs = sorted(r for r in recorded.records if r[0] in ("attention", "attention_cross"))
     assert recs
+    hip = gd.Hip(ops)
     fam_worst, fails = {}, []
     for i, rec in enumerate(recs):
         kind = rec[1]
         T = lr.KIND_DTYPE[kind]
         torch.manual_seed(2000 + i)
+        g = gd.Guarded(DEV, guard_inputs=False)   # out and lse: NaN inside, sentinels around; the full-size inputs stay plain
         if rec[0] == "attention":
             _, _, n, t, c3, heads, new_order, want_lse = rec
             qkv = torch.randn(n, t, c3, device=DEV).to(T)
-            out = ops.attention(qkv, heads, new_order, want_lse)
-            out, lse = out if want_lse else (out, None)
             d, scale = c3 // 3 // heads, (c3 // 3 // heads) ** -0.5
+            out = g.out("out", (n, t, c3 // 3), T, gd.margin_rows(c3 // 3))
+            lse = g.out("lse", (n, heads, t), torch.float32) if want_lse else None
+            if heads == 1 and d == 512:   # ops.attention's rule: the VAE decoder's single 512-wide head
+                hip.attention_1h512(qkv, out)
+            else:
+                hip.attention_lse(qkv, out, lse, heads, d, new_order)
         else:
             _, _, n, tq, qs, rows, kvs, tk, heads, d, scale = rec
             hd = heads * d
@@ -375,8 +284,10 @@ def test_attention_launches_match_float64(ops, recorded):
                 q, kv = buf, buf[:, :, hd:]
             else:
                 q, kv = torch.randn(n, tq, qs, device=DEV).to(T), torch.randn(n, rows, kvs, device=DEV).to(T)
-            out = ops.attention_cross(q, kv, heads, d, tk, scale)
+            out = g.out("out", (n, tq, hd), T, gd.margin_rows(hd))
+            hip.attention_cross(q, q.stride(1), kv, kv.stride(1), kv.shape[1], out, n, tq, tk, heads, d, scale)
         torch.cuda.synchronize()
+        g.check()
         sel = sorted({0, n - 1, int(torch.randint(0, n, (1,)).item())})
         worst, num, den = 0.0, 0.0, 0.0
         for j in sel:
@@ -424,6 +335,7 @@ def _report(name, recs, results, fam_worst=None):
 def test_attention_backward_launches_match_float64(ops, recorded):
     recs = sorted(r for r in recorded.records if r[0] == "attention_bwd")
     assert recs
+    hip = gd.Hip(ops)
     results = []
     for i, rec in enumerate(recs):
         _, kind, n, t, c3, heads, new_order = rec
@@ -432,10 +344,16 @@ def test_attention_backward_launches_match_float64(ops, recorded):
         scale = d ** -0.5
         torch.manual_seed(3000 + i)
         qkv = torch.randn(n, t, c3, device=DEV).to(T)
-        out, lse = ops.attention(qkv, heads, new_order, want_lse=True)
+        g = gd.Guarded(DEV, guard_inputs=False)
+        out = g.out("out", (n, t, c3 // 3), T, gd.margin_rows(c3 // 3))
+        lse = g.out("lse", (n, heads, t), torch.float32)
+        hip.attention_lse(qkv, out, lse, heads, d, new_order)
         dout = torch.randn(n, t, c3 // 3, device=DEV).to(T)
-        dqkv = ops.attention_bwd(qkv, out, dout, lse, heads, new_order)
+        delta = g.out("delta_ws", (n, heads, t), torch.float32)
+        dqkv = g.out("dqkv", (n, t, c3), T, gd.margin_rows(c3))
+        hip.attention_bwd(qkv, out, dout, lse, delta, dqkv, heads, d, new_order)
         torch.cuda.synchronize()
+        g.check()
         worst = 0.0
         for j in sorted({0, n - 1, int(torch.randint(0, n, (1,)).item())}):
             qh, kh, vh = lr.split_qkv(qkv[j:j + 1], heads, new_order)
@@ -453,6 +371,7 @@ def test_attention_backward_launches_match_float64(ops, recorded):
 def test_groupnorm_backward_launches_match_float64(ops, recorded):
     recs = sorted(r for r in recorded.records if r[0] == "gn_bwd")
     assert recs
+    hip = gd.Hip(ops)
     results = []
     for i, rec in enumerate(recs):
         _, kind, n, h, w, c, silu, dy_half, has_add, add_half, has_partial, has_norm_add = rec
@@ -470,17 +389,56 @@ def test_groupnorm_backward_launches_match_float64(ops, recorded):
         if has_partial:   # dy is the producing conv's dz, with its (sum dz, sum dz x) slab sums: one slab, summed in float64
             dzd = dy.double()
             partial = torch.stack([dzd.sum((1, 2)), (dzd * x.double()).sum((1, 2))], -1)[:, None].float().contiguous()
-        got = ops.gn_bwd(x, dy, (a, b), stats, silu, dy_half=dy_half, add=add, add_half=add_half, partial=partial, norm_add=e)
+        g = gd.Guarded(DEV, guard_inputs=False)   # partial, k1 / k0 and dx: NaN inside, sentinels around
+        slabs = 1 if has_partial else max(1, h * w // ops.GN_BWD_SLAB_PIXELS)
+        if not has_partial:
+            partial = g.out("partial", (n, slabs, c, 2), torch.float32)
+        k1, k0 = g.out("k1", (n, c), torch.float32), g.out("k0", (n, c), torch.float32)
+        got = g.out("dx", (n, h, w, c), T, gd.margin_rows(c))
+        # with the producing conv's sums (has_partial) dy is its dz: no partial pass, the SiLU derivative is already inside
+        hip.gn_backward(x, dy, a, b, stats, e, add, partial, k1, k0, got, silu and not has_partial, dy_half, add_half, slabs,
+                        partial_given=has_partial)
         torch.cuda.synchronize()
+        g.check()
         ref, bound = lr.gn_bwd_restate(x, dy, a, b, stats, silu and not has_partial, dy_half, add, add_half, e, T)
         assert torch.isfinite(got).all(), rec
         results.append(((got.double() - ref).abs() / bound).max().item())
     _report("gn_bwd", recs, results)
 
 
+def _gn_affine_guarded(hip, g, ops, x0, gamma, beta, x1, film, film_stride, want_stats, eps, add):
+    """ops.gn_affine's three paths on the library symbols, with every output carved from g -> (a, b[, stats])."""
+    n, h, w, c0 = x0.shape
+    c1 = 0 if x1 is None else x1.shape[3]
+    c, hw, T, f32 = c0 + c1, h * w, x0.dtype, torch.float32
+    a, b = g.out("aff_a", (n, c), f32), g.out("aff_b", (n, c), f32)
+    stats = g.out("stats", (n, 32, 2), f32) if want_stats else None
+    fused0 = getattr(x0, "_adm_stats", None)
+    fused1 = getattr(x1, "_adm_stats", None) if x1 is not None else None
+    p = gd._p
+
+    def partial_of(src1):
+        slabs = ops.gn_slabs(hw)
+        part = g.out("partial", (n, slabs, c, 2), f32)
+        hip.call(T, "adm_gn_partial", p(x0), c0, p(src1), 0 if src1 is None else c1, p(part), n, hw, slabs)
+        return part, slabs
+    if add is not None:
+        part, slabs = fused0 if fused0 is not None else partial_of(None)
+        hip.call(T, "adm_gn_finalize_add", p(part), p(gamma), p(beta), p(add), add.stride(0), p(a), p(b), p(stats), n, c, hw, slabs, eps)
+    elif fused0 is not None and (x1 is None or fused1 is not None):
+        p1, s1 = fused1 if fused1 is not None else (None, 0)
+        hip.call(T, "adm_gn_finalize2", p(fused0[0]), c0, fused0[1], p(p1), c1, s1, p(gamma), p(beta), p(film), film_stride, p(a), p(b),
+                 p(stats), n, hw, eps)
+    else:
+        part, slabs = partial_of(x1)
+        hip.call(T, "adm_gn_finalize", p(part), p(gamma), p(beta), p(film), film_stride, p(a), p(b), p(stats), n, c, hw, slabs, eps)
+    return (a, b, stats) if want_stats else (a, b)
+
+
 def test_groupnorm_affine_launches_match_float64(ops, recorded):
     recs = sorted(r for r in recorded.records if r[0] == "gn_affine")
     assert recs
+    hip = gd.Hip(ops)
     results = []
     for i, rec in enumerate(recs):
         _, kind, n, h, w, c0, c1, has_film, has_add, fused, want_stats, eps = rec
@@ -503,9 +461,10 @@ def test_groupnorm_affine_launches_match_float64(ops, recorded):
         gamma, beta = 1 + 0.2 * torch.randn(c, device=DEV), 0.2 * torch.randn(c, device=DEV)
         film = 0.3 * torch.randn(n, 2 * c, device=DEV) if has_film else None
         add = 0.3 * torch.randn(n, c, device=DEV) if has_add else None
-        res = ops.gn_affine(x0, gamma, beta, x1, film=film, film_stride=2 * c if has_film else 0, want_stats=want_stats, eps=eps,
-                            add=add)
+        g = gd.Guarded(DEV, guard_inputs=False)   # partial, a / b and the kept statistics: NaN inside, sentinels around
+        res = _gn_affine_guarded(hip, g, ops, x0, gamma, beta, x1, film, 2 * c if has_film else 0, want_stats, eps, add)
         torch.cuda.synchronize()
+        g.check()
         x = x0 if x1 is None else torch.cat([x0, x1], 3)
         y, mean, rstd = lr.gn_affine_restate(x, gamma, beta, eps, film=film, add=add)
         got = res[0].double()[:, None, None, :] * x.double() + res[1].double()[:, None, None, :]
@@ -621,7 +580,7 @@ def test_quick_gelu_launches_match_float64(ops, recorded):
     _replay_kind("quick_gelu", recorded, replay)
 
 
-SENTINEL = -7.0
+SENTINEL = gd.SENTINEL
 
 
 def _causal_launch(qkv, heads, t, guard=4096):
@@ -897,21 +856,8 @@ def test_attention_causal_at_tile_edges(ops, t, dtype):
 
 
 # ------------------------------------------------------------------ classifier heads, loss gradient, gradient add
-GUARD = 4096
-
-
-def _owned(shape, dtype, fill=float("nan")):
-    """A test-owned output: `shape` elements of NaN (every one must be written) and GUARD sentinel elements behind them."""
-    numel = 1
-    for s_ in shape:
-        numel *= s_
-    buf = torch.full((numel + GUARD,), fill, dtype=dtype, device=DEV)
-    buf[numel:] = SENTINEL
-    return buf, buf[:numel].view(shape)
-
-
-def _guard_ok(buf, what):
-    assert bool((buf[-GUARD:] == SENTINEL).all()), f"{what}: the guard behind the output was written"
+GUARD = gd.GUARD
+_owned, _guard_ok = gd.owned, gd.guard_ok   # (carve, view): the carve answers data_ptr() with the view's
 
 
 def _call(kind, name, *args):
