@@ -66,10 +66,18 @@ bcast_add_kernel(const float* __restrict__ v, int v_stride, float scale, const u
 }
 
 // mode 1: SiLU, 2: ReLU.  out = act(x)   |   out = dy * act'(z)
+// mode 3: the std of a diagonal Gaussian from its log-variance, out = exp(0.5 clamp(x, -30, 20))   |   out = dy * that (noise x std);
+// mode 4: the clamped log-variance itself, out = clamp(x, -30, 20) (no dy).  A NaN stays a NaN in both.
 __global__ void __launch_bounds__(256)
 vec_act_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ out, long long items, int mode) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (long long)gridDim.x * blockDim.x) {
     const float z = x[i];
+    if (mode >= 3) {
+      const float lv = z < -30.0f ? -30.0f : (z > 20.0f ? 20.0f : z);
+      if (mode == 4) out[i] = lv;
+      else { const float sd = expf(0.5f * lv); out[i] = dy ? dy[i] * sd : sd; }
+      continue;
+    }
     if (dy) out[i] = dy[i] * (mode == 1 ? silu_grad_v(z) : (z > 0.f ? 1.f : 0.f));
     else out[i] = mode == 1 ? z / (1.0f + expf(-z)) : fmaxf(z, 0.f);
   }
@@ -153,7 +161,9 @@ extern "C" int adm_bcast_add(const float* v, int v_stride, float scale, const ad
 
 extern "C" int adm_vec_act(const float* x, const float* dy, float* out, int64_t items, int mode, void* stream) {
   ADM_REQUIRE(x && out, ADM_E_ARG, "adm_vec_act: null pointer");
-  ADM_REQUIRE(items > 0 && (mode == 1 || mode == 2), ADM_E_ARG, "adm_vec_act: items > 0, mode 1 (SiLU) or 2 (ReLU)");
+  ADM_REQUIRE(items > 0 && mode >= 1 && mode <= 4, ADM_E_ARG,
+              "adm_vec_act: items > 0, mode 1 (SiLU), 2 (ReLU), 3 (Gaussian std of a log-variance) or 4 (clamped log-variance)");
+  ADM_REQUIRE(mode != 4 || !dy, ADM_E_ARG, "adm_vec_act: the clamped log-variance takes no dy");
   hipLaunchKernelGGL(vec_act_kernel, dim3(blocks_for(items)), dim3(256), 0, (hipStream_t)stream, x, dy, out, (long long)items, mode);
   return adm_check_launch("adm_vec_act");
 }

@@ -207,7 +207,8 @@ gn_finalize_kernel(const float* __restrict__ part0, int c0, int slabs0, const fl
 
 // ------------------------------------------------------------------------------------ resample
 template <int MODE, bool ACT>  // MODE 1: avgpool2, 2: nearest x2, 3: every second pixel (stride-2 subsample), 4: zero-insert x2 (out[2y][2x] = in[y][x], 0 elsewhere:
-                                // the input of a stride-2 conv's backward-data conv)
+                                // the input of a stride-2 conv's backward-data conv), 5: the odd pixels (out[y][x] = in[2y+1][2x+1]: a pad-(0,1,0,1)
+                                // stride-2 3x3 conv is the pad-1 stride-1 conv sampled there -- the KL-f8 encoder's Downsample)
 __global__ void __launch_bounds__(256)
 resample_kernel(const uint16_t* __restrict__ in, const float* __restrict__ aff_a, const float* __restrict__ aff_b,
                 uint16_t* __restrict__ out, int n, int h, int w, int c) {
@@ -234,8 +235,8 @@ resample_kernel(const uint16_t* __restrict__ in, const float* __restrict__ aff_a
     constexpr int TAPS = MODE == 1 ? 4 : 1;
 #pragma unroll
     for (int tp = 0; tp < TAPS; ++tp) {
-      const int iy = MODE == 1 ? oy * 2 + tp / 2 : ((MODE == 2 || MODE == 4) ? oy / 2 : oy * 2);
-      const int ix = MODE == 1 ? ox * 2 + tp % 2 : ((MODE == 2 || MODE == 4) ? ox / 2 : ox * 2);
+      const int iy = MODE == 1 ? oy * 2 + tp / 2 : ((MODE == 2 || MODE == 4) ? oy / 2 : oy * 2 + (MODE == 5 ? 1 : 0));
+      const int ix = MODE == 1 ? ox * 2 + tp % 2 : ((MODE == 2 || MODE == 4) ? ox / 2 : ox * 2 + (MODE == 5 ? 1 : 0));
       const uint4 v = *reinterpret_cast<const uint4*>(in + (((long long)img * h + iy) * w + ix) * c + g * 8);
       const uint32_t u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -358,7 +359,8 @@ extern "C" int adm_resample(const adm_bf16* in, const float* aff_a, const float*
                             int w, int c, int mode, void* stream) {
   ADM_REQUIRE(in && out, ADM_E_ARG, "adm_resample: null pointer");
   ADM_REQUIRE((aff_a != nullptr) == (aff_b != nullptr), ADM_E_ARG, "adm_resample: aff_a/aff_b go together");
-  ADM_REQUIRE(mode >= 1 && mode <= 4, ADM_E_ARG, "adm_resample: mode must be 1 (avgpool2), 2 (nearest x2), 3 (stride-2 subsample) or 4 (zero-insert x2)");
+  ADM_REQUIRE(mode >= 1 && mode <= 5, ADM_E_ARG,
+              "adm_resample: mode must be 1 (avgpool2), 2 (nearest x2), 3 (stride-2 subsample), 4 (zero-insert x2) or 5 (stride-2 subsample of the odd pixels)");
   ADM_REQUIRE(mode != 4 || !aff_a, ADM_E_ARG, "adm_resample: zero-insert takes no affine");
   ADM_REQUIRE(n > 0 && h > 0 && w > 0 && c % 8 == 0, ADM_E_SHAPE, "adm_resample: bad shape");
   ADM_REQUIRE(mode == 2 || mode == 4 || (h % 2 == 0 && w % 2 == 0), ADM_E_SHAPE, "adm_resample: odd size for a 2x reduction");
@@ -374,6 +376,7 @@ extern "C" int adm_resample(const adm_bf16* in, const float* aff_a, const float*
   if (mode == 1) { if (act) LAUNCH(1, true); else LAUNCH(1, false); }
   else if (mode == 2) { if (act) LAUNCH(2, true); else LAUNCH(2, false); }
   else if (mode == 3) { if (act) LAUNCH(3, true); else LAUNCH(3, false); }
+  else if (mode == 5) { if (act) LAUNCH(5, true); else LAUNCH(5, false); }
   else           LAUNCH(4, false);
 #undef LAUNCH
   return adm_check_launch("adm_resample");

@@ -197,9 +197,10 @@ def gn_affine(x0, gamma, beta, x1=None, film=None, film_stride=0, partial=None, 
 
 def resample(x, mode: str, aff=None):
     """mode 'down' = AvgPool2d(2), 'up' = nearest x2, 'stride2' = every second pixel, 'zero2' = zero-insert x2 (out[2y][2x] = x[y][x]:
-    what a stride-2 conv's backward-data conv reads); aff=(a, b) applies SiLU(a*x+b) first."""
+    what a stride-2 conv's backward-data conv reads), 'stride2_odd' = the odd pixels (out[y][x] = x[2y+1][2x+1]: what the KL-f8
+    encoder's pad-(0,1,0,1) stride-2 conv keeps of the pad-1 stride-1 conv); aff=(a, b) applies SiLU(a*x+b) first."""
     n, h, w, c = x.shape
-    m = {"down": 1, "up": 2, "stride2": 3, "zero2": 4}[mode]
+    m = {"down": 1, "up": 2, "stride2": 3, "zero2": 4, "stride2_odd": 5}[mode]
     oh, ow = (h * 2, w * 2) if m in (2, 4) else (h // 2, w // 2)
     out = torch.empty((n, oh, ow, c), dtype=x.dtype, device=x.device)
     a, b = aff if aff is not None else (None, None)
@@ -745,10 +746,11 @@ def bcast_add(v, shape, dtype, scale: float, add=None, col: int = 0):
 
 
 def vec_act(x, mode: str, dy=None):
-    """fp32 vectors: act(x), or dy * act'(x) with dy; mode 'silu' | 'relu'."""
+    """fp32 vectors: act(x), or dy * act'(x) with dy; mode 'silu' | 'relu'.  mode 'gauss_std': exp(0.5 clamp(x, -30, 20)), the std
+    of a diagonal Gaussian from its log-variance, or dy * std with dy (noise x std); 'gauss_logvar': clamp(x, -30, 20), no dy."""
     out = torch.empty_like(x)
     check(_lib.load().adm_vec_act(_ptr(x, torch.float32, "x"), _ptr(dy, torch.float32, "dy"), _ptr(out), x.numel(),
-                                  {"silu": 1, "relu": 2}[mode], _stream()), "adm_vec_act")
+                                  {"silu": 1, "relu": 2, "gauss_std": 3, "gauss_logvar": 4}[mode], _stream()), "adm_vec_act")
     return out
 
 

@@ -123,6 +123,51 @@ class LatentDiffusion:
             out[i:i + chunk].copy_(x)
         return out
 
+    ENCODE_CHUNK_512 = 8   # images per encoder pass at 512 x 512 (peak: two 512 x 512 x 128 16-bit maps per image, as the decoder's)
+
+    def encode_first_stage(self, x, chunk=None):
+        """ddpm.py:826: first_stage_model.encode(x) -> the posterior (sd_vae.DiagonalGaussianPosterior) of fp32 NCHW device images
+        in [-1, 1].  The batch goes through the encoder ``chunk`` images at a time (default 8 at 512 x 512, scaled by the image's
+        area); every kernel's arithmetic per image is independent of the batch, so the moments are bitwise independent of ``chunk``."""
+        from .sd_vae import DiagonalGaussianPosterior
+        vae = self.first_stage_model
+        if vae is None or getattr(vae, "encoder", None) is None:
+            raise AdmError("LatentDiffusion.encode_first_stage: needs first_stage=sd_vae.AutoencoderKL(..., with_encoder=True)")
+        if not torch.is_tensor(x) or x.dim() != 4:
+            raise AdmError("encode_first_stage: expected [N, C, H, W] images")
+        n, _, h, w = x.shape
+        if chunk is None:
+            chunk = max(1, self.ENCODE_CHUNK_512 * 512 * 512 // max(1, h * w))
+        chunk = max(1, int(chunk))
+        if n <= chunk:
+            return vae.encode(x)
+        x = x.to(torch.float32).contiguous()
+        out = None
+        for i in range(0, n, chunk):
+            m = vae.encode_moments(x[i:i + chunk])
+            if out is None:
+                out = torch.empty((n,) + tuple(m.shape[1:]), dtype=m.dtype, device=m.device)
+            out[i:i + chunk].copy_(m)
+        return DiagonalGaussianPosterior(out)
+
+    def get_first_stage_encoding(self, encoder_posterior, noise=None):
+        """ddpm.py:542-549: scale_factor * z, z the posterior's sample (``noise``: the normal draw to use) or the tensor itself."""
+        if hasattr(encoder_posterior, "sample") and hasattr(encoder_posterior, "mode"):
+            return encoder_posterior.sample(noise=noise, scale=self.scale_factor)
+        if torch.is_tensor(encoder_posterior):
+            z = encoder_posterior.to(torch.float32).contiguous()
+            return axpby_noise(z, self.scale_factor, z, 0.0)
+        raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
+
+    def q_sample(self, x_start, t, noise=None):
+        """ddpm.py:274-277: sqrt(abar_t) x_start + sqrt(1 - abar_t) noise, from the float32 tables; t: one timestep (an int, or a
+        tensor whose entries all agree -- one launch has one pair of coefficients)."""
+        t = _one_index(t, self.num_timesteps, "q_sample")
+        ac = self.alphas_cumprod[t].cpu().numpy().astype(np.float32)
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        return axpby_noise(x_start, np.sqrt(ac), noise, np.sqrt(np.float32(1.0) - ac))
+
     _ROUTES = (("model.diffusion_model.", "model"), ("first_stage_model.", "first_stage_model"))
 
     def load_state_dict(self, sd, strict=True):
@@ -203,6 +248,36 @@ def sd_step(x, eps, batch, cfg_scale, weights, hist, a_t, a_prev, sigma, noise=N
                                   x_prev.data_ptr(), pred.data_ptr(), None if e_out is None else e_out.data_ptr(),
                                   x.numel(), C.byref(co), torch.cuda.current_stream().cuda_stream), "adm_sd_step")
     return x_prev, pred, e_out
+
+
+def axpby_noise(x, a, noise, b):
+    """a * x + b * noise on fp32 device tensors, as one ``adm_sd_step`` launch with its eps terms switched off: sqrt_at = 1,
+    sqrt_one_minus_at = 0 and dir_coef = 0 make pred_x0 = x exactly for a finite eps operand (the noise itself stands in), so the
+    update is sqrt_a_prev * x + sigma * noise with sqrt_a_prev = a, sigma = b.  q_sample, DDIMSampler.stochastic_encode and the
+    posterior's sample (sd_vae.DiagonalGaussianPosterior) are this."""
+    if tuple(x.shape) != tuple(noise.shape):
+        raise AdmError(f"axpby_noise: x {tuple(x.shape)} vs noise {tuple(noise.shape)}")
+    out = torch.empty_like(x)
+    co = SdStepCoefs()
+    co.cfg_scale = 1.0
+    co.w = (C.c_float * 4)(1.0, 0.0, 0.0, 0.0)
+    co.sqrt_one_minus_at, co.sqrt_at, co.dir_coef = 0.0, 1.0, 0.0
+    co.sqrt_a_prev, co.sigma = float(np.float32(a)), float(np.float32(b))
+    npt = _f32ptr(noise, "noise")
+    check(_lib.load().adm_sd_step(_f32ptr(x, "x"), None, npt, None, None, None, npt, out.data_ptr(), None, None, x.numel(),
+                                  C.byref(co), torch.cuda.current_stream().cuda_stream), "adm_sd_step")
+    return out
+
+
+def _one_index(t, size, who):
+    """The single index a batch of equal indices (tensor, sequence or int) stands for; it must lie in [0, size)."""
+    vals = {int(v) for v in torch.as_tensor(t).reshape(-1).tolist()}
+    if len(vals) != 1:
+        raise NotImplementedError(f"{who}: per-sample timesteps {sorted(vals)} (one launch has one pair of coefficients)")
+    i = vals.pop()
+    if not 0 <= i < size:
+        raise IndexError(f"{who}: index {i} outside [0, {size})")
+    return i
 
 
 _SIDE_STREAMS = {}  # device -> second HIP stream for the unconditional half of a guided evaluation
@@ -319,6 +394,40 @@ class DDIMSampler(_LatentSampler):
                 intermediates['x_inter'].append(img)
                 intermediates['pred_x0'].append(pred_x0)
         return img, intermediates
+
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+        """ddim.py:219-233: sqrt(ddim_alphas[t]) x0 + ddim_sqrt_one_minus_alphas[t] noise -- ``t`` INDEXES the table make_schedule
+        built (uniform or ``sampled_timestep``), it is not a timestep."""
+        self._unsupported(use_original_steps=use_original_steps)
+        t = _one_index(t, len(self.ddim_alphas), "DDIMSampler.stochastic_encode")
+        x0 = x0.to(torch.float32).contiguous()
+        if noise is None:
+            noise = torch.randn_like(x0)
+        return axpby_noise(x0, np.sqrt(self.ddim_alphas[t]), noise, self.ddim_sqrt_one_minus_alphas[t])
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
+               use_original_steps=False):
+        """ddim.py:235-254: the DDIM updates of ``ddim_timesteps[:t_start]``, downwards, from x_latent.  With the reference's
+        conventions a latent from ``stochastic_encode(x0, t)`` carries the noise level of table entry t and is decoded with
+        ``t_start = t``, whose first update is entry t - 1's: the off-by-one is the reference's and is kept."""
+        self._unsupported(use_original_steps=use_original_steps)
+        device, img = self._start(tuple(x_latent.shape), x_latent)
+        self._begin(cond, unconditional_conditioning, unconditional_guidance_scale)
+        b = img.shape[0]
+        timesteps = np.asarray(self.ddim_timesteps)[:int(t_start)]
+        total = timesteps.shape[0]
+        for i, step in enumerate(np.flip(timesteps)):
+            index = total - i - 1
+            ts = torch.full((b,), int(step), device=device, dtype=torch.long)
+            eps = self._eps(img, ts)
+            sigma = self.ddim_sigmas[index]
+            noise = torch.randn(img.shape, device=device) if sigma != 0 else None
+            img, _, _ = sd_step(img, eps, b, unconditional_guidance_scale, (1.0,), (), self.ddim_alphas[index],
+                                self.ddim_alphas_prev[index], sigma, noise, want_e=False)
+        return img
 
 
 class PLMSSampler(_LatentSampler):

@@ -150,7 +150,9 @@ int adm_gn_finalize2(const float* partial0, int c0, int slabs0, const float* par
  * (turns a stride-1 3x3 conv into the stride-2 Downsample of the latent UNet), mode 4 = zero-insert x2
  * (out[2y][2x] = in[y][x], 0 elsewhere, no affine: the backward-data conv of a stride-2 3x3 conv -- the classifier's
  * Downsample with classifier_resblock_updown = False, unet.py:115-140 -- is the stride-1 conv with transposed, flipped
- * weights over this tensor).                                                                */
+ * weights over this tensor), mode 5 = the odd pixels (out[y][x] = act(in[2y+1][2x+1]), H and W even, the affine as mode 3:
+ * the KL-f8 encoder's Downsample -- pad (0,1,0,1), then a stride-2 pad-0 3x3 conv, model.py:60-79 -- is the pad-1 stride-1
+ * conv sampled at these pixels).                                                            */
 int adm_resample(const adm_bf16* in, const float* aff_a, const float* aff_b, adm_bf16* out,
                  int n, int h, int w, int c, int mode, void* stream);
 
@@ -390,7 +392,10 @@ int adm_resize_bilinear(const void* in, adm_bf16* out, int n, int h, int w, int 
  *                     identity without (spatial: h.mean(dim=(2, 3)) of every block, written at a column offset of the feature row)
  *   adm_bcast_add     out[n][p][ch] = (add ? add[n][p][ch] : 0) + v[n][ch] * scale: the backward of a pixel mean (scale = 1 / HW)
  *                     accumulated into the gradient that flows through the same tensor
- *   adm_vec_act       mode 1 SiLU, 2 ReLU on fp32 vectors: out = act(x), or with dy: out = dy * act'(x)
+ *   adm_vec_act       mode 1 SiLU, 2 ReLU on fp32 vectors: out = act(x), or with dy: out = dy * act'(x);
+ *                     mode 3 the std of a diagonal Gaussian posterior from its log-variance (distributions.py:28-30):
+ *                     out = expf(0.5f * clamp(x, -30, 20)), or with dy: out = dy * that (noise x std);
+ *                     mode 4 the clamped log-variance itself, out = clamp(x, -30, 20) (dy must be NULL)
  *   adm_vec_gn(_bwd)  GroupNorm32(32, C) of fp32 [N][C] rows (spatial_v2's normalization(2048): no spatial axis), stats fp32
  *                     [N][32][2] = (mean, rstd); backward-data dx from dz = d(loss)/d(y)                                    */
 int adm_channel_mean(const adm_bf16* h, const float* aff_a, const float* aff_b, float* out, int out_stride, int n, int hw, int c,

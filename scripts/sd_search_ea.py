@@ -210,7 +210,7 @@ def build_model(opt, device, prompt_len=None):
     if opt.tokenizer_dir:
         clip_cfg["version"] = opt.tokenizer_dir
     unet = UNetModel(**unet_cfg).set_torso(opt.torso)
-    vae = AutoencoderKL(**vae_cfg).set_torso(opt.torso)
+    vae = AutoencoderKL(**vae_cfg, with_encoder=getattr(opt, "with_encoder", False)).set_torso(opt.torso)   # sd_img2img.py asks for the encoder
     if prompt_len is not None and not opt.tokenizer_dir:
         clip_cfg["max_length"] = int(prompt_len)
     clip = FrozenCLIPEmbedder(device="cpu", **clip_cfg).set_torso(opt.torso)

@@ -9,7 +9,10 @@ latent, model TFLOP/s from the plan's algorithmic FLOPs) and `adm_attention_1h51
 torch-composed 16-bit bmm-softmax-bmm, alternating, median of 5.
 --encode times the cond stage: `FrozenCLIPEmbedder.encode` of 6 and 12 prompts of 77 tokens through the ViT-L/14 text transformer
 per torso (ms per call, launches per call, model TFLOP/s from the plan's algorithmic FLOPs) next to the same transformer composed
-from torch's own 16-bit ops on the same weights, alternating, median of 5 windows of 20 calls."""
+from torch's own 16-bit ops on the same weights, alternating, median of 5 windows of 20 calls.
+--vae-encode times the first stage's other half: `encode_first_stage` of 1 and 8 images of 512 x 512 through the v1 KL-f8 encoder per
+torso (ms per pass and per image, median of 5 passes after 2 warm-ups; TFLOP/s and the fraction of the 2.5 PFLOP/s dense 16-bit MFMA
+peak on the plan's algorithmic FLOPs and on the executed ones, which run the three Downsample convs at stride 1)."""
 import os
 import sys
 import time
@@ -113,6 +116,32 @@ def decode_bench():
         del vae, ld
 
 
+PEAK_16BIT_TFLOPS = 2500.0   # MI355X dense bf16 / fp16 MFMA peak
+
+
+def vae_encode_bench():
+    import statistics
+    from autodiffusion_amd.sd_sampler import LatentDiffusion
+    from autodiffusion_amd.sd_vae import SD_V1_VAE, AutoencoderKL
+    hw = int(os.environ.get("HW", "512"))
+    for torso in ("bf16", "fp16"):
+        vae = AutoencoderKL(**SD_V1_VAE, with_encoder=True).set_torso(torso).to(DEV).randomize_(4321)
+        ld = LatentDiffusion(vae.encoder, device=DEV, first_stage=vae)   # the schedule tables are not used here
+        alg, exe = (vae.encoder.plan.flops(hw, hw, executed=e, embed_dim=vae.embed_dim) / 1e9 for e in (False, True))
+        for n in (1, 8):
+            x = torch.tanh(torch.randn(n, 3, hw, hw, device=DEV, generator=torch.Generator(device=DEV).manual_seed(n)))
+            for _ in range(2):
+                out = ld.encode_first_stage(x).parameters
+            torch.cuda.synchronize()
+            assert out.shape == (n, 2 * vae.embed_dim, hw // 8, hw // 8) and torch.isfinite(out).all()
+            ts = [_timed(lambda: ld.encode_first_stage(x)) for _ in range(5)]
+            ms = statistics.median(ts)
+            print(f"SD v1 VAE encode [{torso}] {n} images of {hw}x{hw}: {ms:.1f} ms / pass ({min(ts):.1f} .. {max(ts):.1f}), {ms / n:.2f} ms / image; "
+                  f"algorithmic {alg:.1f} GFLOP / image: {n * alg / ms:.1f} TFLOP/s = {100 * n * alg / ms / PEAK_16BIT_TFLOPS:.1f} % of peak; "
+                  f"executed {exe:.1f} GFLOP / image: {n * exe / ms:.1f} TFLOP/s = {100 * n * exe / ms / PEAK_16BIT_TFLOPS:.1f} % of peak")
+        del vae, ld
+
+
 def _torch_clip(P, plan, dt):
     """The text transformer composed from torch's 16-bit ops on the same parameters: ids -> fp32 [N, T, C]."""
     import torch.nn.functional as F
@@ -208,6 +237,8 @@ def sampler_bench(m):
 if __name__ == "__main__":
     if "--decode" in sys.argv[1:]:
         decode_bench()
+    elif "--vae-encode" in sys.argv[1:]:
+        vae_encode_bench()
     elif "--encode" in sys.argv[1:]:
         encode_bench()
     else:
