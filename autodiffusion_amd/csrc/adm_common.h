@@ -99,6 +99,19 @@ __device__ __forceinline__ float adm_silu(float v) {
   // IEEE division here would triple the VALU cost of the conv prologue, which shares issue slots with MFMA
   return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f));
 }
+// Beside MFMAs a packed v_pk_*_f32 costs far more than the two single instructions it replaces, and under -O3 hipcc's SLP pass
+// pairs adjacent scalar fp32 operations into one: a value passed through adm_single is opaque to that pass (an empty asm: no
+// instruction, no ordering), so the operation that made it and the one that reads it stay single-issue.
+__device__ __forceinline__ float adm_single(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
+// adm_silu, operation for operation, for the transforms inside MFMA loops: every fp32 instruction single-issue
+__device__ __forceinline__ float adm_silu_single(float v) {
+  const float t = adm_single(v * -1.4426950408889634f);
+  const float d = adm_single(1.0f + __builtin_amdgcn_exp2f(t));
+  return adm_single(v * __builtin_amdgcn_rcpf(d));
+}
 // two at a time: the non-transcendental half of the work as packed fp32 (v_pk_mul_f32 / v_pk_add_f32)
 typedef float adm_f32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ adm_f32x2_t adm_silu2(adm_f32x2_t v) {

@@ -424,11 +424,28 @@ conv_kernel(const ConvK p) {
       const bool valid = pixrel[ps] >= 0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        adm_f32x2_t t = {adm_lo_f32(u[j]), adm_hi_f32(u[j])};
-        t = __builtin_elementwise_fma(adm_f32x2_t{a8[2 * j], a8[2 * j + 1]}, t, adm_f32x2_t{b8[2 * j], b8[2 * j + 1]});
-        if constexpr (PRO == 2) t = adm_silu2(t);
-        const uint32_t pk = adm_pack2(t.x, t.y);
-        u[j] = valid ? pk : 0u;
+        if constexpr (ONEW || COLD) {
+          // packed fp32.  ONEW: first_park only (chunk1 transforms inside its K loop itself), no MFMA beside it.  COLD (split-K,
+          // fp32 NCHW output, the 4-wave head tile): these instantiations already spill, and the single-issue form spills more
+          // (profiles/pk_unpack/README.md)
+          adm_f32x2_t t = {adm_lo_f32(u[j]), adm_hi_f32(u[j])};
+          t = __builtin_elementwise_fma(adm_f32x2_t{a8[2 * j], a8[2 * j + 1]}, t, adm_f32x2_t{b8[2 * j], b8[2 * j + 1]});
+          if constexpr (PRO == 2) t = adm_silu2(t);
+          const uint32_t pk = adm_pack2(t.x, t.y);
+          u[j] = valid ? pk : 0u;
+        } else {
+          // the same operations, element by element, as single-issue fp32 (v_fma_f32, v_mul_f32, v_add_f32): this transform sits
+          // between the MFMAs of the K loop, where a packed v_pk_*_f32 costs far more than its two single instructions
+          // (adm_single keeps hipcc from pairing them again)
+          float lo = adm_single(__builtin_fmaf(a8[2 * j], adm_lo_f32(u[j]), b8[2 * j]));
+          float hi = adm_single(__builtin_fmaf(a8[2 * j + 1], adm_hi_f32(u[j]), b8[2 * j + 1]));
+          if constexpr (PRO == 2) {
+            lo = adm_silu_single(lo);
+            hi = adm_silu_single(hi);
+          }
+          const uint32_t pk = adm_pack2(lo, hi);
+          u[j] = valid ? pk : 0u;
+        }
       }
       v = make_uint4(u[0], u[1], u[2], u[3]);
     }
