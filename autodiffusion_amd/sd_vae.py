@@ -28,7 +28,9 @@ The encoder (``AutoencoderKL(..., with_encoder=True)``) runs the same blocks dow
                                  no 8 -> 8 launch, no extra tensor.  The state dict keeps the two layers apart under their names.
   posterior                      DiagonalGaussian: mean | logvar halves copied apart, std = adm_vec_act mode 3, the sample
                                  mean + std * noise on adm_sd_step (sd_sampler.axpby_noise)
-Non-square maps are not built (the CLIP text encoder is sd_clip.py).
+Non-square maps are not built (the CLIP text encoder is sd_clip.py).  The conv kernels tile maps of 8 x 8 or of a multiple of 16 pixels
+a side, so the encoder takes images whose mid map is one of those (v1: sides of 64, or a multiple of 128) and refuses the rest
+before its first launch (Encoder.check_images).
 """
 from __future__ import annotations
 
@@ -417,6 +419,10 @@ class Encoder(HipModule):
         m = self.side_multiple
         if n < 1 or hh != ww or hh < m or hh % m:
             raise AdmError(f"{who}: images of {hh} x {ww} unsupported (square, sides a multiple of {m} = 8 * 2^(levels - 1))")
+        mid = hh // (m // 8)
+        if mid != 8 and mid % 16:   # adm_conv tiles maps of 8 x 8 or of a multiple of 16 pixels a side: refuse before the first launch
+            raise AdmError(f"{who}: images of {hh} x {ww} unsupported: their {mid} x {mid} mid map does not tile into the conv kernels' "
+                           f"16-pixel-wide patches (sides of {m}, or a multiple of {2 * m})")
         if not x.is_cuda:
             raise AdmError(f"{who}: the images must be a device tensor (the HIP path has no CPU fallback)")
 
@@ -449,7 +455,8 @@ class Encoder(HipModule):
 
     def _head(self, hd, h):
         """norm_out -> SiLU -> conv_out with the fp32 NCHW epilogue.  That epilogue's kernel takes 16 x 16-pixel tiles of one image, and
-        the mid map is any multiple of 8 (8 x 8 for a 64-pixel v1 image): such a map is activated on its own pixels
+        the mid map may be 8 x 8 (a 64-pixel v1 image; the torso's convs take no other map that is no multiple of 16, check_images,
+        though this function takes any multiple of 8): such a map is activated on its own pixels
         (resample(up) then resample(stride2, aff): SiLU(a h + b), rounded once to 16 bits as the conv's prologue rounds it), copied
         into the corner of a zeroed map of the next multiple of 16 -- the zeros to the right and below are the conv's own padding --
         convolved without a prologue, and the corner copied out.  Per image, like every launch: independent of the batch."""

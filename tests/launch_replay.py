@@ -1,4 +1,5 @@
-"""Launch recorder, float64 restatements and per-element error bounds for tests/test_hip_launch_replay.py.
+"""Launch recorder, float64 restatements and per-element error bounds for tests/test_hip_launch_replay.py and, for the KL-f8 VAE
+encoder's launches and head, tests/test_hip_vae_encoder_replay.py.
 
 Recording, at two levels.  Census: every exported symbol of autodiffusion_amd/_lib.SIGNATURES whose last argument is the stream
 pointer is a launch (launch_symbols; the adm_stream_* calls manage streams and launch nothing); each is wrapped on both loaded
@@ -51,7 +52,7 @@ Per-element bounds, u = 2^-8 (bf16) or 2^-11 (fp16), ulp_T(v) = 2u * 2^floor(log
   quick_gelu a sigmoid(1.702 a): ulp_T(|ref|) / 2 + SILU_REL (1 + |1.702 a|) |ref|: the fp32 product in front of exp2 has a
              relative error 2^-24 of an argument that grows with |a|, and d log sigmoid(z) / dz <= 1.
   clip_embed round_T(tok[ids] + pos[:t]) with the add in fp32, pad rows zero: bitwise.
-  resample   'up' / 'stride2' / 'zero2' without the affine are copies and zeros: bitwise.  'down' is the mean of four taps:
+  resample   'up' / 'stride2' / 'stride2_odd' / 'zero2' without the affine are copies and zeros: bitwise.  'down' is the mean of four taps:
              ulp_T(|ref|) / 2 + 4 x 2^-24 mean|x| (three fp32 adds, an exact 1 / 4).  With the affine the taps are
              s = silu(a x + b): the mean (the tap) of SILU_REL |s| + 2^-23 (|a x| + |b|) is added -- approximate exp / rcp, and
              the fp32 multiply-add in front through silu' <= 1.1.
@@ -85,7 +86,8 @@ Per-element bounds, u = 2^-8 (bf16) or 2^-11 (fp16), ulp_T(v) = 2u * 2^floor(log
   bcast_add  without add: round_T of the fp32 product v scale, bitwise.  With add: ulp_T(|ref|) / 2 + e (2 |v scale| + |add|).
   vec_act    SiLU: SILU_REL |ref| + F32_MIN (expf, an add, a division; below z = -88.7 expf overflows and the result is -0).
              SiLU': dy s (1 + z (1 - s)): SILU_REL |dy| s (1 + |z|) + F32_MIN -- 1 - s cancels for large z, absolute e there.
-             ReLU and ReLU': exact, ReLU'(0) = 0.
+             ReLU and ReLU': exact, ReLU'(0) = 0.  gauss_std / gauss_logvar (modes 3 / 4, the KL-f8 posterior's): the restatements
+             and bounds of tests/f32_vae_kernels.py; the clamped log-variance is compared bitwise.
   vec_gn     k = (ceil(cpg / 8) + 3) e, cpg = c / 32: a lane's adds and three butterfly steps.  E_m = k mean|x| + SILU_REL
              |mean|; d = x - mean carries E_m + e |d|, so E_v = 2 mean|d| E_m + E_m^2 + (k + 4 e + SILU_REL) var and rstd is
              relative rel_r = E_v / (2 (var + eps)) + e + 2 SILU_REL (the add of eps, sqrtf, the division).  y: |γ| rstd E_m +
@@ -99,6 +101,24 @@ Per-element bounds, u = 2^-8 (bf16) or 2^-11 (fp16), ulp_T(v) = 2u * 2^floor(log
              e dist_y + SILU_REL (1 + |log sum|) + the sum's relative error + 2 e |ref|.
   grad_add   round_T(a + s b), s = 1 or an exact 1 / 4: ulp_T(|ref|) / 2 + e (|a| + |s b|).
   linear_f32, timestep_embedding   fp32 throughout: f32_kernels.linear_restate / timestep_restate (derived in that module's docstring).
+  stem_conv3x3   adm_stem_conv3x3, the KL-f8 encoder's conv_in from the fp32 NCHW image: f32_kernels.stem_restate (derived there).
+  head       the KL-f8 encoder's head as a composite (Encoder._head, both routes; head_restate): float64 GroupNorm + SiLU of the
+             stored map, s = SiLU(z), z = γ ŷ + β, ŷ = (h - mean) rstd, rounded once to T; then the pad-1 3x3 conv of the unpadded
+             map with round_T weights and an fp32 bias, under the conv bound above for fp32 NCHW output.  The midpoint-straddle
+             term is taken with the window the composite needs (head_window): the kernels form z = a h + b from fp32 statistics,
+             which the GroupNorm replay keeps within 2^-20 (|mean| + 1 / rstd) of the mean and 2^-20 rstd of rstd: through γ rstd
+             and γ ŷ that is 2^-20 |γ| (|mean| rstd + 1 + |ŷ|); the fp32 roundings of a = γ rstd, of mean a, of b and of the
+             multiply-add add 2^-22 |γ| (|mean| rstd + |ŷ|) + 2^-23 (|β| + |z|).  So |z_kernel - z| <= dz = (2^-20 + 2^-22) |γ|
+             (|mean| rstd + 1 + |ŷ|) + 2^-23 (|β| + |z|), and s moves by at most 1.1 dz (SiLU' <= 1.1) + PRO_ULPS 2^-23 |s| (the
+             conv bound's own slack for the approximate exp / rcp).  An s within that window of a rounding midpoint may round the
+             other way: its step to the other T neighbour times |w| enters the bound.
+  folded     Encoder.folded_head: W' = wq Wout per tap and b' = wq b_out + bq in fp32, W' then rounded to T.  The reference is
+  head       quant_conv(conv_out(act)) in float64 from the unfolded fp32 weights, W'_64 = Σ_m wq_m Wout_m.  An fp32 dot product of
+             length m (torch's einsum / matmul, any order, with or without fma) is within (m + 1) 2^-24 Σ_m |wq_m Wout_mk| of W'_64
+             to first order (m products, m - 1 adds, one of each per term: m + 1 covers every order); rounding that to T adds
+             ulp_T(|W'_k|) / 2 (at a binade edge the result is the edge itself, inside the lower binade's half ulp).  So the conv
+             bound widens by Σ_k |act_k| dW_k, dW_k = ulp_T(|W'_k|) / 2 + (m + 1) 2^-24 Σ_m |wq_m Wout_mk|, and its magnitude sums
+             take |W'_k| + dW_k.  The bias is a dot product of length m plus the add of bq: (m + 2) 2^-24 (Σ_m |wq_m b_out_m| + |bq|).
   Frobenius  ||got - ref|| / ||ref|| <= FRO_U u sqrt(r), FRO_U = 0.6: one rounding to T has an RMS relative error of at most
              u / sqrt(3) ~ 0.58 u; r roundings in sequence (A, then A + residual; dz, then dz SiLU'; P, then the output) add in
              quadrature.
@@ -112,7 +132,8 @@ import math
 
 import torch
 
-from f32_kernels import linear_path, linear_restate, timestep_restate   # noqa: F401  (the two fp32 record kinds of the embedding path)
+from f32_kernels import linear_path, linear_restate, stem_restate, timestep_restate   # noqa: F401  (the fp32 record kinds of the embedding path, the direct stem)
+from f32_vae_kernels import GAUSS_SPECIALS, gauss_logvar_restate, gauss_std_restate   # noqa: F401  (adm_vec_act modes 3 / 4)
 
 U = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
 KIND_DTYPE = {"bf16": torch.bfloat16, "f16": torch.float16}
@@ -166,7 +187,7 @@ def _e(test: str) -> tuple:
 
 # launch symbol -> the record kinds that replay it here, or ("elsewhere", "tests/<file>.py::<test>") for what stays where it is:
 # the weight packers (every conv replay compares against round_t(w), so a mis-packed weight fails there too), the sampler steps
-# and the direct stem (tests/test_hip_f32_kernels.py), and the evaluation-side kernels of the Inception replay and the FID /
+# (tests/test_hip_f32_kernels.py), and the evaluation-side kernels of the Inception replay and the FID /
 # precision-recall tests.
 SYMBOL_COVERAGE = {
     "adm_conv": ("conv",),
@@ -205,10 +226,13 @@ SYMBOL_COVERAGE = {
     "adm_logsoftmax_grad": ("logsoftmax_grad",),
     # no caller in the package: held by its direct test
     "adm_grad_add": _e("tests/test_hip_launch_replay.py::test_grad_add_at_edges"),
-    # fp32 embedding path: record kinds; the direct stem has no caller in the shipped models
+    # fp32 embedding path: record kinds
     "adm_linear_f32": ("linear_f32",),
     "adm_timestep_embedding": ("timestep_embedding",),
-    "adm_stem_conv3x3": _e("tests/test_hip_f32_kernels.py::test_stem_conv_at_edges"),
+    # the direct stem is the KL-f8 encoder's conv_in (3 -> 128 on the image): a record kind, replayed by
+    # tests/test_hip_vae_encoder_replay.py at the shapes the model launches; tests/test_hip_f32_kernels.py::test_stem_conv_at_edges
+    # holds its edge shapes
+    "adm_stem_conv3x3": ("stem_conv3x3",),
     # weight packers
     "adm_pack_conv_weight": _e("tests/test_hip_kernels.py::test_conv_fused"),
     "adm_pack_conv_weight32": _e("tests/test_hip_kernels.py::test_conv_fused"),
@@ -253,7 +277,7 @@ def kind_of(t) -> str:
     return "f16" if t.dtype == torch.float16 else "bf16"
 
 
-RESAMPLE_MODES = {"down": 1, "up": 2, "stride2": 3, "zero2": 4}
+RESAMPLE_MODES = {"down": 1, "up": 2, "stride2": 3, "zero2": 4, "stride2_odd": 5}
 
 
 class Recorder:
@@ -320,6 +344,12 @@ class Recorder:
         o_ln, o_lnf, o_gg, o_qg, o_cau, o_emb = (ops.layernorm, ops.layernorm_f32out, ops.geglu, ops.quick_gelu, ops.attention_causal,
                                                  ops.clip_embed)
         o_res, o_pad, o_lat, o_img, o_c2d = ops.resample, ops.nchw_to_nhwc_pad, ops.vae_latent_in, ops.vae_image_out, ops.conv2d
+        o_stem = ops.stem_conv3x3
+
+        def stem_conv3x3(x_nchw, w, b, dtype=torch.bfloat16):
+            n, cin, h, wd = x_nchw.shape
+            self._add(("stem_conv3x3", KIND_OF_DTYPE[dtype], n, cin, h, wd, w.shape[0]))
+            return o_stem(x_nchw, w, b, dtype)
 
         def layernorm(x, gamma, beta, eps=1e-5):
             c = x.shape[-1]
@@ -438,7 +468,7 @@ class Recorder:
             self._add(("timestep_embedding", "bf16", t.shape[0], int(dim), float(max_period)))
             return o_temb(t, dim, max_period)
 
-        for name, fn in (("linear_f32", linear_f32), ("timestep_embedding", timestep_embedding), ("attention", attention), ("attention_cross", attention_cross), ("attention_bwd", attention_bwd),
+        for name, fn in (("stem_conv3x3", stem_conv3x3), ("linear_f32", linear_f32), ("timestep_embedding", timestep_embedding), ("attention", attention), ("attention_cross", attention_cross), ("attention_bwd", attention_bwd),
                          ("gn_affine", gn_affine), ("gn_bwd", gn_bwd), ("layernorm", layernorm), ("layernorm_f32out", layernorm_f32out),
                          ("geglu", geglu), ("quick_gelu", quick_gelu), ("attention_causal", attention_causal), ("clip_embed", clip_embed),
                          ("resample", resample), ("nchw_to_nhwc_pad", nchw_to_nhwc_pad), ("vae_latent_in", vae_latent_in),
@@ -520,7 +550,10 @@ EMBED_KINDS = ("linear_f32", "timestep_embedding")
 EMBED_FAMILIES = EMBED_KINDS + ("linear_f32 mfma", "linear_f32 gemv", "linear_f32 table")
 REQUIRED_FAMILIES += list(EMBED_FAMILIES)
 ONE_LIBRARY_FAMILIES.update({f: "bf16" for f in EMBED_FAMILIES})
-REPLAYED = {"conv", "attention", "attention_cross", "attention_bwd", "gn_bwd", "gn_affine"} | set(NEW_KINDS) | set(EMBED_KINDS)
+# the KL-f8 encoder's own kind: recorded and replayed by tests/test_hip_vae_encoder_replay.py, whose guard asserts its presence --
+# not a required family of the big recording above, which does not run the encoder
+ENCODER_KINDS = ("stem_conv3x3",)
+REPLAYED = {"conv", "attention", "attention_cross", "attention_bwd", "gn_bwd", "gn_affine"} | set(NEW_KINDS) | set(EMBED_KINDS) | set(ENCODER_KINDS)
 
 
 def missing_families(records) -> list:
@@ -841,7 +874,7 @@ def clip_embed_restate(ids, tok, pos, pitch: int, dtype):
 
 
 def resample_restate(x, mode: int, aff, dtype):
-    """x [n, h, w, c] holding T values; mode 1 AvgPool2d(2), 2 nearest x2, 3 every second pixel, 4 zero-insert x2; aff = (a, b)
+    """x [n, h, w, c] holding T values; mode 1 AvgPool2d(2), 2 nearest x2, 3 every second pixel, 4 zero-insert x2, 5 the odd pixels; aff = (a, b)
     fp32 [n, c]: silu(a x + b) first -> (ref, bound); the bound is None where the result is a copy (compared bitwise)."""
     n, h, w, c = x.shape
     s = x.double()
@@ -864,6 +897,9 @@ def resample_restate(x, mode: int, aff, dtype):
     elif mode == 3:
         ref = s[:, ::2, ::2]
         e = None if e is None else e[:, ::2, ::2]
+    elif mode == 5:
+        ref = s[:, 1::2, 1::2]
+        e = None if e is None else e[:, 1::2, 1::2]
     elif mode == 4:
         if aff is not None:
             raise NotImplementedError("zero-insert takes no affine")
@@ -1042,11 +1078,18 @@ def bcast_add_restate(v, scale: float, add, hw: int, dtype):
     return ref, half_ulp(ref, dtype) + E24 * (2 * vs.abs() + add.double().abs())
 
 
-VEC_ACT_MODES = {"silu": 1, "relu": 2}
+VEC_ACT_MODES = {"silu": 1, "relu": 2, "gauss_std": 3, "gauss_logvar": 4}
 
 
 def vec_act_restate(x, mode: int, dy=None):
-    """fp32 x (and dy): act(x) or dy act'(x) -> (ref, bound); ReLU is exact (bound None: equal as values), ReLU'(0) = 0."""
+    """fp32 x (and dy): act(x) or dy act'(x) -> (ref, bound); ReLU is exact (bound None: equal as values), ReLU'(0) = 0.  Modes
+    3 / 4 are f32_vae_kernels': exp(0.5 clamp(x)) (times dy), and the clamped log-variance as an fp32 tensor (bound None: bitwise)."""
+    if mode == 3:
+        return gauss_std_restate(x, dy)
+    if mode == 4:
+        if dy is not None:
+            raise NotImplementedError("gauss_logvar takes no dy")
+        return gauss_logvar_restate(x), None
     z = x.double()
     if mode == 2:
         return (torch.clamp(z, min=0.0) if dy is None else dy.double() * (z > 0).double()), None
@@ -1133,3 +1176,77 @@ def pool_zero_rows_ok(dqkv, t: int) -> bool:
     """adm_pool_attn_bwd's zeros: the rows >= t, and the dQ columns of the rows 1 .. t, hold only zero bit patterns."""
     c = dqkv.shape[2] // 3
     return not bool(dqkv[:, t:].contiguous().view(torch.int16).any()) and not bool(dqkv[:, 1:t, :c].contiguous().view(torch.int16).any())
+
+
+# ------------------------------------------------------------------ the KL-f8 encoder's head as a composite
+def head_window(h, gamma, beta, eps: float):
+    """float64 GroupNorm32 of the stored map h [n, hh, ww, c] -> (z, dz): z = γ ŷ + β in front of the SiLU and the distance dz
+    that a z formed from fp32 statistics may lie from it (module docstring)."""
+    n, hh, ww, c = h.shape
+    z, mean, rstd = gn_affine_restate(h, gamma, beta, eps)
+    cpg = c // 32
+    m = mean.repeat_interleave(cpg, 1)[:, None, None, :]
+    r = rstd.repeat_interleave(cpg, 1)[:, None, None, :]
+    g = gamma.double().abs()
+    yh = ((h.double() - m) * r).abs()
+    dz = (2.0 ** -20 + 2.0 ** -22) * g * (m.abs() * r + 1 + yh) + 2.0 ** -23 * (beta.double().abs() + z.abs())
+    return z, dz
+
+
+def head_activation(h, gamma, beta, eps: float, dtype):
+    """-> (act, risk) [n, hh, ww, c] float64: SiLU(GroupNorm(h)) rounded once to T, and the step to the other T neighbour where s
+    lies within 1.1 dz + PRO_ULPS 2^-23 |s| of a rounding midpoint (else 0)."""
+    z, dz = head_window(h, gamma, beta, eps)
+    s = z * torch.sigmoid(z)
+    ds = 1.1 * dz + PRO_ULPS * 2.0 ** -23 * s.abs()
+    r = round_t(s, dtype)
+    risk = torch.maximum((round_t(s - ds, dtype) - r).abs(), (round_t(s + ds, dtype) - r).abs())
+    return r, risk
+
+
+def head_restate(h, gamma, beta, w, bias, eps: float, dtype, wq=None, bq=None):
+    """Encoder._head on the stored 16-bit map h [n, hh, ww, c] -> (ref, bound) fp32-NCHW-shaped [n, cout, hh, ww] in float64: the
+    pad-1 3x3 conv of head_activation on the unpadded map, w fp32 [cout, c, 3, 3] rounded to T, bias fp32.  With wq [o, cout, 1, 1]
+    and bq [o] (Encoder.folded_head) the reference is wq (conv(act) + bias) + bq in float64 from the unfolded fp32 weights and the
+    bound carries the fold's terms (module docstring)."""
+    import torch.nn.functional as F
+    n, hh, ww, c = h.shape
+    act, risk = head_activation(h, gamma, beta, eps, dtype)
+    cols = F.unfold(act.permute(0, 3, 1, 2), 3, padding=1)              # [n, c * 9, hh * ww], zeros outside the map
+    rcols = F.unfold(risk.permute(0, 3, 1, 2), 3, padding=1)
+    kk = c * 9
+    if wq is None:
+        wm = round_t(w.double(), dtype).reshape(w.shape[0], kk)
+        wmag, bd = wm.abs(), bias.double()
+        extra, bextra = 0.0, 0.0
+    else:
+        q = wq.double().reshape(wq.shape[0], -1)                            # [o, m]
+        m = q.shape[1]
+        w64 = w.double().reshape(w.shape[0], kk)
+        wm = q @ w64
+        dw = half_ulp(wm, dtype) + (m + 1) * E24 * (q.abs() @ w64.abs())
+        wmag = wm.abs() + dw
+        bd = q @ bias.double() + bq.double()
+        extra = dw @ cols.abs()
+        bextra = ((m + 2) * E24 * (q.abs() @ bias.double().abs() + bq.double().abs()))[:, None]
+    ref = wm @ cols + bd[:, None]
+    e = wmag @ rcols + (kk + 1 + 2) * E24 * (wmag @ cols.abs() + bd.abs()[:, None]) + extra + bextra
+    bound = e + E24 * ref.abs()
+    shape = (n, wm.shape[0], hh, ww)
+    return ref.reshape(shape), bound.reshape(shape)
+
+
+HEAD_OFFSET = -4.0   # mean / std of the head tests' maps (head_operands)
+
+
+def head_operands(n: int, side: int, c: int, cout: int, dtype, seed: int) -> dict:
+    """Seeded host operands of one head case: the 16-bit mid map h [n, side, side, c], norm_out's (gamma, beta), conv_out's fp32
+    (w, bias) and a 1x1 (wq [cout, cout, 1, 1], bq) to fold.  The map is N(HEAD_OFFSET, 1): with a mean four standard deviations
+    below zero the GroupNorm shift is b = β - γ mean rstd ~ +4, so a pixel that is zero BEFORE the activation (padding activated
+    too late) becomes SiLU(b) ~ 3.9 where the conv must read 0 -- an error of order Σ |w| 3.9 over a row of taps, thousands of
+    times the bound, on the last row and column only.  At a mean of zero the same defect would hide inside SiLU(β) ~ β / 2."""
+    g = torch.Generator().manual_seed(seed)
+    return {"h": (torch.randn(n, side, side, c, generator=g) + HEAD_OFFSET).to(dtype),
+            "gamma": 1 + 0.2 * torch.randn(c, generator=g), "beta": 0.2 * torch.randn(c, generator=g),
+            "w": torch.randn(cout, c, 3, 3, generator=g) * (9 * c) ** -0.5, "bias": 0.1 * torch.randn(cout, generator=g),
+            "wq": torch.randn(cout, cout, 1, 1, generator=g) * cout ** -0.5, "bq": 0.1 * torch.randn(cout, generator=g)}

@@ -4,7 +4,8 @@ The models (built as tests/test_hip_fullsize.py, tests/test_hip_sd_vae.py and te
 values do not matter, only the launch list does) run eagerly at the batches bench.py uses and at batch 1-2, in the bf16 and the
 fp16 torso, under tests/launch_replay.Recorder: ADM-64 / 128 / 256, the classifiers (the shipped attention-pool ones, and the
 adaptive / spatial / spatial_v2 heads at width 64), the SD latent UNet, the KL-f8 VAE decoder
-(with the image exit that follows it) and the CLIP text encoder.  The fp32 embedding path rides along: every adm_linear_f32 and
+(with the image exit that follows it) and the CLIP text encoder; the KL-f8 VAE encoder is recorded and replayed by
+tests/test_hip_vae_encoder_replay.py, on this file's replay functions.  The fp32 embedding path rides along: every adm_linear_f32 and
 adm_timestep_embedding launch of those evaluations is a record too (tests/f32_kernels.py states and bounds them).  Each distinct record is then launched again through the same
 entry point with fresh seeded operands and compared element by element with the float64 restatement of tests/launch_replay.py,
 within the per-element bounds derived there (and tested on the host by tests/test_launch_replay_host.py).  Large conv maps are
@@ -478,7 +479,7 @@ def test_groupnorm_affine_launches_match_float64(ops, recorded):
 
 
 # ------------------------------------------------------------------ token, resample, layout, VAE entry / exit, stride-2 conv
-SEEDS = {k: 6000 + 1000 * i for i, k in enumerate(lr.NEW_KINDS + lr.EMBED_KINDS)}
+SEEDS = {k: 6000 + 1000 * i for i, k in enumerate(lr.NEW_KINDS + lr.EMBED_KINDS + lr.ENCODER_KINDS)}
 
 
 def _replay_kind(name, recorded, replay, roundings=1):
@@ -991,9 +992,12 @@ VEC_SPECIALS = (0.0, -0.0, 88.0, -88.0, 104.0, -104.0, 1e-3, -1.2784645)
 
 
 def _check_vec_act(items, mode, backward):
-    x = torch.randn(items, device=DEV) * 3
-    k = min(items, len(VEC_SPECIALS))
-    x[:k] = torch.tensor(VEC_SPECIALS[:k], device=DEV)
+    if mode in (3, 4):   # the KL-f8 posterior's log-variance: both clamp edges from both sides, far outside, the zeros
+        x, specials = torch.randn(items, device=DEV) * 12, lr.GAUSS_SPECIALS
+    else:
+        x, specials = torch.randn(items, device=DEV) * 3, VEC_SPECIALS
+    k = min(items, len(specials))
+    x[:k] = torch.tensor(specials[:k], device=DEV)
     dy = torch.randn(items, device=DEV) if backward else None
     buf, out = _owned((items,), torch.float32)
     _call("bf16", "adm_vec_act", _p(x), _p(dy), _p(buf), items, mode)
@@ -1001,6 +1005,9 @@ def _check_vec_act(items, mode, backward):
     if bool(torch.isnan(out).any()):
         return float("inf"), None, "NaN in the output"
     ref, bound = lr.vec_act_restate(x, mode, dy)
+    if mode == 4:       # the clamped log-variance: bitwise, -0 stays -0
+        w, rep = _bitwise(out, ref, "gauss_logvar")
+        return w, None, rep
     if bound is None:   # ReLU: equal as values, ReLU'(0) = 0
         bad = out.double() != ref
         return (float("inf"), None, f"{int(bad.sum())} elements differ") if bool(bad.any()) else (0.0, None, "")

@@ -295,6 +295,7 @@ def _fake_records():
         recs[("nchw_to_nhwc_pad", kind)] = ("nchw_to_nhwc_pad", kind, 2, 3, 64, 64, 32)
         recs[("vae_latent_in", kind)] = ("vae_latent_in", kind, 1, 4, 4, 64, 64)
         recs[("conv2d", kind)] = ("conv2d", kind, ("cin", 320), ("cout", 320))
+        recs[("stem_conv3x3", kind)] = ("stem_conv3x3", kind, 1, 3, 512, 512, 128)
     recs[("vae_image_out", "bf16")] = ("vae_image_out", "bf16", 1, 512, 512, True, True)
     recs.update(_fake_head_records())
     return recs
@@ -307,8 +308,12 @@ def test_coverage_guard_fails_when_a_model_or_a_hook_is_removed():
     here = {s: cov for s, cov in lr.SYMBOL_COVERAGE.items() if cov[0] != "elsewhere" and set(cov) & set(lr.NEW_KINDS)}
     one_library = {"adm_" + f for f, k in lr.ONE_LIBRARY_FAMILIES.items() if k == "bf16"}   # fp32 kernels on the bf16 library alone
     census = {(s, k) for s in here for k in ("bf16", "f16") if not (s in one_library and k == "f16")}
-    census |= {("adm_stem_conv3x3", "bf16")}   # held elsewhere: needs no record
+    census |= {("adm_stem_conv3x3", k) for k in ("bf16", "f16")}   # the KL-f8 encoder's conv_in: a record kind of its own
     assert lr.coverage_gaps(census, recs.values(), lr.REPLAYED) == []
+    left = [r for r in recs.values() if r[0] != "stem_conv3x3"]          # its hook removed from the recorder
+    gaps = lr.coverage_gaps(census, left, lr.REPLAYED)
+    assert len(gaps) == 2 and all("adm_stem_conv3x3" in g and "no stem_conv3x3 record" in g for g in gaps), gaps
+    assert "not replayed" in lr.coverage_gaps({("adm_stem_conv3x3", "bf16")}, recs.values(), lr.REPLAYED - {"stem_conv3x3"})[0]
     new = set(lr.NEW_KINDS) | {"attention d 512", "non-square map"}
     assert not [m for m in lr.missing_families(recs.values()) if m[1] in new]
     for kind in lr.NEW_KINDS:   # one hook removed from the recorder
@@ -609,7 +614,7 @@ def test_families_of_the_new_records():
     recs = _fake_records()
     assert lr.families(recs[("clip conv", "bf16")]) == {("bf16", "variant 10"), ("bf16", "non-square map")}
     assert lr.families(recs[("vae attention", "f16")]) == {("f16", "attention d 512")}
-    for kind in lr.NEW_KINDS:
+    for kind in lr.NEW_KINDS + lr.ENCODER_KINDS:
         assert lr.families(recs[(kind, "bf16")]) == {("bf16", kind)}
 
 
@@ -1139,3 +1144,204 @@ def test_grad_add_restatement_emulation_and_defects(b_half, dtype):
     if b_half:   # the AvgPool2d backward's 1 / 4 left out
         assert _ratio((a.to(F32) + 4 * up.to(F32)).to(dtype), ref, bound) > 1.0
     assert (_truncate(a.to(F32) + up.to(F32), dtype).double() - ref).norm() / ref.norm() > lr.fro_bound(1, lr.U[dtype])
+
+
+# ------------------------------------------------------------------ the KL-f8 encoder's launches
+def test_encoder_kinds_are_covered_and_replayed():
+    assert lr.SYMBOL_COVERAGE["adm_stem_conv3x3"] == ("stem_conv3x3",) and lr.ENCODER_KINDS == ("stem_conv3x3",)
+    assert set(lr.ENCODER_KINDS) <= lr.REPLAYED
+    # the big recording does not run the encoder: its kind is no required family there (the encoder replay's own guard asserts it)
+    assert not set(lr.ENCODER_KINDS) & set(lr.REQUIRED_FAMILIES) and not set(lr.ENCODER_KINDS) & set(lr.NEW_KINDS)
+    assert lr.RESAMPLE_MODES["stride2_odd"] == 5 and lr.VEC_ACT_MODES["gauss_std"] == 3 and lr.VEC_ACT_MODES["gauss_logvar"] == 4
+    from autodiffusion_amd import ops
+    import inspect
+    src = inspect.getsource(ops.resample) + inspect.getsource(ops.vec_act)
+    for name, m in list(lr.RESAMPLE_MODES.items()) + list(lr.VEC_ACT_MODES.items()):   # the recorder's tables are ops' own
+        assert f'"{name}": {m}' in src, (name, m)
+
+
+def test_recorder_hooks_the_encoder_launches():
+    """The stem's wrapper is replaced, and the recorder takes the odd-pixel pick and the Gaussian modes: each hook records before
+    it passes the call on (the call itself fails here: host tensors)."""
+    from autodiffusion_amd import ops
+    from autodiffusion_amd._lib import AdmError
+    with pytest.MonkeyPatch.context() as mp:
+        rec = lr.Recorder(mp)
+        v = torch.zeros(96)
+        calls = [lambda: ops.stem_conv3x3(torch.zeros(2, 3, 64, 64), torch.zeros(128, 3, 3, 3), torch.zeros(128), torch.float16),
+                 lambda: ops.stem_conv3x3(torch.zeros(1, 3, 8, 16), torch.zeros(32, 3, 3, 3), torch.zeros(32)),
+                 lambda: ops.resample(torch.zeros(1, 4, 6, 32, dtype=BF), "stride2_odd"),
+                 lambda: ops.resample(torch.zeros(1, 4, 6, 32, dtype=torch.float16), "stride2_odd", (v, v)),
+                 lambda: ops.vec_act(v, "gauss_std"), lambda: ops.vec_act(v, "gauss_std", dy=v), lambda: ops.vec_act(v, "gauss_logvar")]
+        for call in calls:
+            with pytest.raises(AdmError):
+                call()
+        assert rec.records == {("stem_conv3x3", "f16", 2, 3, 64, 64, 128), ("stem_conv3x3", "bf16", 1, 3, 8, 16, 32),
+                               ("resample", "bf16", 1, 4, 6, 32, 5, False), ("resample", "f16", 1, 4, 6, 32, 5, True),
+                               ("vec_act", "bf16", 96, 3, False), ("vec_act", "bf16", 96, 3, True), ("vec_act", "bf16", 96, 4, False)}
+    assert ops.stem_conv3x3.__module__ == "autodiffusion_amd.ops"   # the patch is undone
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+@pytest.mark.parametrize("with_aff", [False, True])
+def test_resample_odd_pixels_restatement_emulation_and_defects(with_aff, dtype):
+    """Mode 5 is out[y][x] = in[2y + 1][2x + 1]: the restatement against the padded stride-2 pick it stands for, the fp32
+    emulation inside the bound (bitwise without the affine), the even pixels and the (2y + 1, 2x) pick outside."""
+    n, h, w, c = 2, 6, 4, 16
+    x = lr.round_t(_rnd((n, h, w, c), 15), dtype)
+    aff = (1 + 0.2 * _rnd((n, c), 16), 0.2 * _rnd((n, c), 17)) if with_aff else None
+    xc = x.permute(0, 3, 1, 2).double()
+    if with_aff:
+        xc = F.silu(aff[0].double()[:, :, None, None] * xc + aff[1].double()[:, :, None, None])
+    ref, bound = lr.resample_restate(x, 5, aff, dtype)
+    # F.pad(x, (0, 1, 0, 1)) sampled where a pad-0 stride-2 3x3 window has its centre: pixel (2y + 1, 2x + 1)
+    torch.testing.assert_close(ref, F.pad(xc, (0, 1, 0, 1))[:, :, 1::2, 1::2][:, :, :h // 2, :w // 2].permute(0, 2, 3, 1), rtol=1e-12, atol=1e-12)
+    assert ref.shape == (n, h // 2, w // 2, c)
+    x32 = x.to(F32)
+    s32 = F.silu(aff[0][:, None, None, :] * x32 + aff[1][:, None, None, :]) if with_aff else x32
+    good, even, mixed = s32[:, 1::2, 1::2], s32[:, ::2, ::2], s32[:, 1::2, ::2]
+    if not with_aff:
+        assert bound is None and torch.equal(good.to(dtype).double(), ref)
+        assert not torch.equal(even.to(dtype).double(), ref) and not torch.equal(mixed.to(dtype).double(), ref)
+        return
+    err = (good.to(dtype).double() - ref).abs()
+    assert (err <= bound).all(), (err / bound).max()
+    assert (bound <= 1.01 * 0.5 * lr.ulp_t(ref, dtype) + 2.0 ** -19 * (1 + ref.abs())).all()
+    assert err.norm() / ref.norm() <= lr.fro_bound(1, lr.U[dtype])
+    for bad in (even, mixed):
+        assert ((bad.to(dtype).double() - ref).abs() > bound).any()
+    assert (_truncate(good, dtype).double() - ref).norm() / ref.norm() > lr.fro_bound(1, lr.U[dtype])
+
+
+def test_vec_act_gaussian_modes_restatement_emulation_and_defects():
+    """Modes 3 / 4 through vec_act_restate: f32_vae_kernels' restatements; exp(x / 2) without the clamp is outside the bound (at
+    the specials beyond the clamp), the clamped log-variance is bitwise."""
+    import f32_vae_kernels as V
+    x = _rnd((5 * 2048,), 43, 12.0)
+    x[:len(lr.GAUSS_SPECIALS)] = torch.tensor(lr.GAUSS_SPECIALS)
+    assert lr.GAUSS_SPECIALS is V.GAUSS_SPECIALS and bool((x < -30).any()) and bool((x > 20).any())
+    dy = _rnd((5 * 2048,), 44)
+    ref, bound = lr.vec_act_restate(x, 3)
+    torch.testing.assert_close(ref, torch.exp(0.5 * torch.clamp(x.double(), -30.0, 20.0)), rtol=1e-15, atol=0)
+    refb, boundb = lr.vec_act_restate(x, 3, dy)
+    torch.testing.assert_close(refb, dy.double() * ref, rtol=1e-15, atol=0)
+    emu = torch.exp(0.5 * torch.clamp(x, -30.0, 20.0))
+    r, rb = _ratio(emu, ref, bound), _ratio(dy * emu, refb, boundb)
+    unclamped = torch.exp(0.5 * x)
+    bad, badb = _ratio(unclamped, ref, bound), _ratio(dy * unclamped, refb, boundb)
+    print(f"vec_act gauss_std: emulation worst err/bound {r:.3f}, with dy {rb:.3f}; without the clamp {bad:.3g} / {badb:.3g} x the bound")
+    assert r <= 1.0 and rb <= 1.0 and bad > 1.0 and badb > 1.0
+    # only the elements beyond the clamp tell: without them the defect is invisible, so every replayed operand carries the specials
+    inside = (x >= -30.0) & (x <= 20.0)
+    assert _ratio(unclamped[inside], ref[inside], bound[inside]) <= 1.0
+    lv, none = lr.vec_act_restate(x, 4)
+    assert none is None and lv.dtype == torch.float32 and torch.equal(lv, torch.clamp(x, -30.0, 20.0))
+    assert torch.equal(torch.signbit(lv), torch.signbit(torch.clamp(x, -30.0, 20.0))) and float(lv.min()) == -30.0 and float(lv.max()) == 20.0
+    assert not torch.equal(lv, x)
+    with pytest.raises(NotImplementedError):
+        lr.vec_act_restate(x, 4, dy)
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+def test_stem_record_restatement_emulation_and_transposed_taps(dtype):
+    """A stem_conv3x3 record (kind, n, cin, h, w, cout) restated by f32_kernels.stem_restate at the encoder's channel counts: fp32
+    conv2d inside the bound, the same conv with its taps transposed (ky <-> kx) outside."""
+    import f32_kernels as fk
+    assert lr.stem_restate is fk.stem_restate
+    _, _, n, cin, h, w, cout = ("stem_conv3x3", lr.KIND_OF_DTYPE[dtype], 2, 3, 9, 7, 128)
+    x, wt, b = fk.stem_inputs(n, cin, h, w, cout, 35)
+    ref, bound = lr.stem_restate(x, wt, b, dtype)
+    assert ref.shape == (n, h, w, cout)
+    torch.testing.assert_close(ref, F.conv2d(x.double(), wt.double(), b.double(), padding=1).permute(0, 2, 3, 1), rtol=1e-12, atol=1e-12)
+    good = F.conv2d(x, wt, b, padding=1).permute(0, 2, 3, 1).to(dtype)
+    assert _ratio(good, ref, bound) <= 1.0
+    assert (good.double() - ref).norm() / ref.norm() <= lr.fro_bound(1, lr.U[dtype])
+    bad = F.conv2d(x, wt.transpose(2, 3).contiguous(), b, padding=1).permute(0, 2, 3, 1).to(dtype)
+    assert _ratio(bad, ref, bound) > 1.0
+
+
+# ------------------------------------------------------------------ the encoder's head as a composite
+HEAD_EPS = 1e-6
+
+
+def _head_emulated(o, dtype, pad_first=False, fold=None):
+    """Encoder._head in fp32 on the operands of lr.head_operands: the GroupNorm affine from float64 statistics as fp32 (a, b),
+    SiLU(a h + b) rounded once to T, the pad-1 3x3 conv with round_T weights.  pad_first: the defect -- the map is copied into the
+    corner of a zeroed map of the next multiple of 16 BEFORE the activation, so the padding is activated too.  fold: None, or
+    "ok" / "no_bq" / "transposed": the head of folded_head (W' = wq Wout and b' = wq b_out + bq in fp32, W' rounded to T), without
+    the bq term, or with wq transposed."""
+    h, gamma, beta = o["h"], o["gamma"], o["beta"]
+    n, side, _, c = h.shape
+    _, mean, rstd = lr.gn_affine_restate(h, gamma, beta, HEAD_EPS)
+    cpg = c // 32
+    a64 = gamma.double() * rstd.repeat_interleave(cpg, 1)
+    b64 = beta.double() - mean.repeat_interleave(cpg, 1) * a64
+    a, b = a64.to(F32)[:, None, None, :], b64.to(F32)[:, None, None, :]
+    x = h.to(F32)
+    if pad_first:
+        big = -(-side // 16) * 16
+        xp = torch.zeros(n, big, big, c)
+        xp[:, :side, :side] = x
+        x = xp
+    act = lr.round_t(F.silu(torch.addcmul(b, a, x)), dtype)
+    w, bias = o["w"], o["bias"]
+    if fold is not None:
+        q = o["wq"].reshape(o["wq"].shape[0], -1)
+        q = q.t().contiguous() if fold == "transposed" else q
+        w = torch.einsum("om,mcyx->ocyx", q, o["w"])
+        bias = q @ o["bias"] + (0.0 if fold == "no_bq" else o["bq"])
+    out = F.conv2d(act.permute(0, 3, 1, 2), lr.round_t(w, dtype), bias, padding=1)
+    return out[:, :, :side, :side]
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+@pytest.mark.parametrize("side", [8, 24, 16])
+def test_head_restatement_emulation_and_an_activated_padding(side, dtype):
+    o = lr.head_operands(2, side, 64, 8, dtype, 9000 + side)
+    ref, bound = lr.head_restate(o["h"], o["gamma"], o["beta"], o["w"], o["bias"], HEAD_EPS, dtype)
+    assert ref.shape == (2, 8, side, side)
+    # the restatement is the reference's norm_out -> SiLU -> conv_out, but for one rounding of the activation to T
+    hc = o["h"].double().permute(0, 3, 1, 2)
+    plain = F.conv2d(F.silu(F.group_norm(hc, 32, o["gamma"].double(), o["beta"].double(), eps=HEAD_EPS)), lr.round_t(o["w"], dtype).double(),
+                     o["bias"].double(), padding=1)
+    assert (ref - plain).norm() / plain.norm() <= 2 * lr.U[dtype]
+    # the offset does what head_operands says: the GroupNorm shift is about +4, a pixel that is zero before the activation becomes ~ 3.9
+    z0 = lr.head_window(torch.zeros_like(o["h"]), o["gamma"], o["beta"], HEAD_EPS)[0]   # all-zero map: z = beta
+    _, mean, rstd = lr.gn_affine_restate(o["h"], o["gamma"], o["beta"], HEAD_EPS)
+    shift = -(mean * rstd)
+    assert z0.abs().max() <= 1.0 and 3.0 <= shift.min() and shift.max() <= 5.5, (shift.min(), shift.max())
+    good = _head_emulated(o, dtype)
+    r = _ratio(good, ref, bound)
+    fro = ((good.double() - ref).norm() / ref.norm()).item()
+    assert r <= 1.0 and fro <= lr.fro_bound(1, lr.U[dtype]), (r, fro / lr.U[dtype])
+    if side % 16 == 0:
+        return
+    bad = _head_emulated(o, dtype, pad_first=True)
+    ratio = (bad.double() - ref).abs() / bound
+    edge = torch.zeros_like(ref, dtype=torch.bool)
+    edge[:, :, -1, :] = edge[:, :, :, -1] = True
+    print(f"head side {side} {dtype}: emulation worst err/bound {r:.3f}; padding activated: last row / column {ratio[edge].min().item():.3g} .. "
+          f"{ratio[edge].max().item():.3g} x the bound (median {ratio[edge].median().item():.3g}), inside {ratio[~edge].max().item():.3f}")
+    assert ratio[~edge].max() <= 1.0           # wrong along the two edges only ...
+    assert ratio[edge].min() > 1.0 and ratio[edge].median() > 100.0   # ... there on every element, and typically by far more than the bound
+
+
+@pytest.mark.parametrize("dtype", TYPES)
+@pytest.mark.parametrize("side", [8, 16])
+def test_folded_head_restatement_emulation_and_defects(side, dtype):
+    o = lr.head_operands(2, side, 64, 8, dtype, 9000 + side)
+    ref, bound = lr.head_restate(o["h"], o["gamma"], o["beta"], o["w"], o["bias"], HEAD_EPS, dtype, o["wq"], o["bq"])
+    ref0, bound0 = lr.head_restate(o["h"], o["gamma"], o["beta"], o["w"], o["bias"], HEAD_EPS, dtype)
+    # quant_conv(conv_out(act)) from the unfolded weights; the unfolded restatement rounds Wout to T, this one does not
+    act = lr.head_activation(o["h"], o["gamma"], o["beta"], HEAD_EPS, dtype)[0].permute(0, 3, 1, 2)
+    plain = F.conv2d(F.conv2d(act, o["w"].double(), o["bias"].double(), padding=1), o["wq"].double(), o["bq"].double())
+    torch.testing.assert_close(ref, plain, rtol=1e-12, atol=1e-12)
+    assert (bound > 0).all() and bound.mean() > bound0.mean()
+    good = _head_emulated(o, dtype, fold="ok")
+    r = _ratio(good, ref, bound)
+    fro = ((good.double() - ref).norm() / ref.norm()).item()
+    bad_q, bad_t = _ratio(_head_emulated(o, dtype, fold="no_bq"), ref, bound), _ratio(_head_emulated(o, dtype, fold="transposed"), ref, bound)
+    print(f"folded head side {side} {dtype}: emulation worst err/bound {r:.3f}, fro/u {fro / lr.U[dtype]:.3f}; without bq {bad_q:.3g}, "
+          f"wq transposed {bad_t:.3g} x the bound")
+    assert r <= 1.0 and fro <= lr.fro_bound(1, lr.U[dtype])
+    assert bad_q > 1.0 and bad_t > 1.0

@@ -186,6 +186,19 @@ def test_encode_refuses_bad_images_and_cpu_tensors():
             vae.encode(torch.zeros(shape))
     with pytest.raises(AdmError, match="square"):
         vae.encode(torch.zeros(1, 3, 32, 64))
+    # a mid map that the conv kernels cannot tile (12 x 12, 20 x 20: no multiple of 16 and not 8 x 8) is refused by name, before
+    # any launch; 8 x 8 and the multiples of 16 pass the shape check (and stop at the host tensor)
+    for side in (96, 160):
+        with pytest.raises(AdmError, match="mid map does not tile"):
+            vae.encode(torch.zeros(1, 3, side, side))
+    for side in (32, 64, 128, 192):
+        with pytest.raises(AdmError, match="device tensor"):
+            vae.encode(torch.zeros(1, 3, side, side))
+    v1 = AutoencoderKL(**SD_V1_VAE, with_encoder=True).encoder
+    assert v1.side_multiple == 64
+    for side, ok in ((64, True), (128, True), (192, False), (256, True), (320, False), (512, True)):
+        with pytest.raises(AdmError, match="device tensor" if ok else "24 x 24 mid map|40 x 40 mid map"):
+            v1.check_images(torch.zeros(1, 3, side, side))
     with pytest.raises(AdmError, match=r"\[N, 3, H, W\]"):
         vae.encode(torch.zeros(1, 4, 32, 32))
     for fn in (vae.encode, vae.encode_moments, vae.encoder):
