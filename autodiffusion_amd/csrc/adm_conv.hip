@@ -1476,6 +1476,9 @@ bool conv_geometry(ConvK& k, int BM, int taps, int halo_max) {
   k.TH = k.H < BM / k.TW ? k.H : BM / k.TW;
   if (k.TH <= 0 || BM % (k.TH * k.TW) != 0 || k.H % k.TH != 0 || k.W % k.TW != 0) return false;
   k.TI = BM / (k.TH * k.TW);
+  // a tile of TI images holds WHOLE images (tile_origin: y0 = x0 = 0, one tile per TI images): a TH x TW patch smaller than the
+  // map -- 8x32 is TH 8 x TW 16, TI 2 -- would leave the columns >= TW of every image uncomputed
+  if (k.TI > 1 && (k.TH != k.H || k.TW != k.W)) return false;
   const int pad = taps == 9 ? 1 : 0;
   if (k.TI > TI_MAX || k.TI * (k.TH + 2 * pad) * (k.TW + 2 * pad) > halo_max) return false;
   k.tiles_x = k.W / k.TW;
@@ -1512,7 +1515,18 @@ int dispatch_conv(ConvK& k, int taps, int prologue, hipStream_t s) {
       }
     }
   } else {   // 1x1 (COLD: split-K on the 8-wave tiles, fp32 NCHW output on the 16-wide tile)
-    if (conv_geometry(k, BM, 1, BM)) {
+    // A 1x1 conv has no neighbours: a map that does not tile as h x w is tiled as the (h w / 16) x 16 map of the same pixels.  The
+    // pixels of an image are flat in every operand (NHWC rows, the planes of the fp32 NCHW output, the split-K workspace), so the
+    // view changes no address; maps that tile as they are keep their tiles.
+    const int h0 = k.H, w0 = k.W;
+    bool tiled = conv_geometry(k, BM, 1, BM);
+    if (!tiled && (h0 * w0) % 16 == 0) {
+      k.H = h0 * w0 / 16;
+      k.W = 16;
+      tiled = conv_geometry(k, BM, 1, BM);
+    }
+    if (!tiled) { k.H = h0; k.W = w0; }
+    if (tiled) {
       const int m_tiles = k.TI == 1 ? k.N * k.tiles_x * k.tiles_y : (k.N + k.TI - 1) / k.TI;
       return launch_conv<WM, WN, TM, TN, OCC, 1, BM, 1, COLD>(k, prologue, m_tiles, s);
     }
@@ -1552,9 +1566,13 @@ bool small_tiles_16(const adm_conv_args* a) {
 int stat_slabs_for(const adm_conv_args* a, int variant) {
   if (a->out_mode != 0 || variant == 7) return 0;
   const int hw = a->h * a->w;
-  if (a->up_phase) return (a->h >= 16 && a->w >= 16 && hw % 256 == 0) ? hw / 256 * 4 : 0;   // one slab per (source tile, phase)
-  if (hw <= 64) return hw == 64 ? 1 : 0;
-  if (a->h < 16 || a->w < 16 || hw % 256 != 0) return 0;
+  const bool tiles16 = a->h % 16 == 0 && a->w % 16 == 0;   // what conv_geometry cuts into 16 x 16 tiles of one image
+  if (a->up_phase) return tiles16 ? hw / 256 * 4 : 0;   // one slab per (source tile, phase)
+  if (a->prologue == 3 && !tiles16) return 0;           // the GroupNorm-backward epilogue exists on the 256-pixel tiles only
+  // 64-pixel maps: two whole images per 128-pixel tile, one statistics group each.  Of the 3x3 convs only the 8x8 map tiles so (the
+  // halo of any other 64-pixel map exceeds the tile's); the 16-wide tile of variant 3 holds four such images under ONE group
+  if (hw <= 64) return (hw == 64 && variant != 3 && (a->taps == 1 || (a->h == 8 && a->w == 8))) ? 1 : 0;
+  if (!tiles16) return 0;
   if (small_tiles_16(a)) return hw / 64;   // 128-pixel tiles x two 64-pixel groups
   return hw / 256;
 }

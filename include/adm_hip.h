@@ -220,6 +220,19 @@ typedef struct adm_conv_args {
                         The classifier's LAST backward-data conv (the stem's) undoes the static 2^10 scale of an fp16 backward
                         network here -- in fp32, not in its fp16 weights, where 2^-10 pushed a quarter of them into subnormals */
 } adm_conv_args;
+/* Which maps adm_conv takes.  What it accepts it computes on every pixel; anything else is refused with ADM_E_SHAPE / ADM_E_ARG before
+ * the first launch, and nothing is written (tests/test_hip_conv_envelope.py walks 121 maps from 1x1 to 64x64 per family):
+ *   3x3, variants 0 / 5 / 6      h and w multiples of 16 (16 x 16 tiles of one image), or the 8x8 map (two images per tile); so with a
+ *                                residual, out_stats, ksplit and fold0.  prologue 3, in_up / res_up, up_phase, the fp32 NCHW output
+ *                                and variants 3 / 7 / 8: h and w multiples of 16 only
+ *   1x1 on the staged kernel     h * w = 64, 128 or a multiple of 256 -- and 32 on variants 0 / 5 / 6 with cout > 16 -- at any h and w
+ *   (variants 0 / 3 / 5 / 6,     with that product: a 1x1 conv has no neighbours, so a map that does not tile as h x w (8x32, 1x64,
+ *   ksplit, fp32 NCHW output)    24x32) is tiled as the (h w / 16) x 16 map of the same pixels.  4x48, 8x48, 24x24 are refused
+ *   1x1 on the resident kernel   h * w a multiple of 64 (it indexes flat pixels); with variant 0 the other maps go to the staged kernel,
+ *   (variant 10; variant 0 at    with variant 10 or geglu they are refused
+ *   cout >= 256, cin % 64 == 0)
+ *   out_stats                    adm_conv_stat_slabs > 0 exactly where adm_conv takes the request with out_stats: h and w multiples of
+ *                                16; the 64-pixel maps a 1x1 conv takes (3x3: 8x8 only) except on variant 3; the resident kernel's maps */
 int adm_conv(const adm_conv_args* args_host, void* stream);
 /* slabs of out_stats for these arguments (0 = fused statistics not offered for this shape / variant). */
 int adm_conv_stat_slabs(const adm_conv_args* args_host);

@@ -246,21 +246,34 @@ def conv_args(d, t, packed, w32p, out):
     return a
 
 
-def launch_conv(lib, fn, d, t, packed, w32p, out, g):
-    """adm_conv through the library symbol `fn` with out_stats and the split-K workspace carved from g -> stats | None."""
-    from autodiffusion_amd._lib import check
+REFUSALS = (-1, -2, -3)   # ADM_E_ARG, ADM_E_SHAPE, ADM_E_ALIGN (include/adm_hip.h): answered before anything is launched
+
+
+def submit_conv(lib, fn, d, t, packed, w32p, out, g):
+    """adm_conv through the library symbol `fn` with out_stats and the split-K workspace carved from g -> (status, stats | None,
+    adm_conv_stat_slabs' answer | None).  Where that answer is 0 the request still goes out, with one slab carved: whether adm_conv
+    then refuses it is the caller's question."""
     a = conv_args(d, t, packed, w32p, out)
-    stats = None
+    stats = slabs = None
     if d["has_out_stats"]:
         slabs = lib.adm_conv_stat_slabs(C.byref(a))
-        assert slabs > 0, d
-        stats = g.out("out_stats", (d["n"], slabs, d["cout"], 2), F32)
+        stats = g.out("out_stats", (d["n"], max(1, slabs), d["cout"], 2), F32)
         a.out_stats = stats.data_ptr()
     if d["ksplit"] > 1:
         ws = g.out("ws", (d["ksplit"], d["n"] * d["h"] * d["w"], d["cout"]), F32, margin_rows(d["cout"]))
         a.ws = ws.data_ptr()
-    check(fn(C.byref(a), torch.cuda.current_stream().cuda_stream), "adm_conv (replay)")
+    rc = fn(C.byref(a), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
+    return rc, stats, slabs
+
+
+def launch_conv(lib, fn, d, t, packed, w32p, out, g):
+    """submit_conv for a case that must run -> stats | None."""
+    from autodiffusion_amd._lib import check
+    a = conv_args(d, t, packed, w32p, out)
+    assert not d["has_out_stats"] or lib.adm_conv_stat_slabs(C.byref(a)) > 0, d
+    rc, stats, _ = submit_conv(lib, fn, d, t, packed, w32p, out, g)
+    check(rc, "adm_conv (replay)")
     return stats
 
 
@@ -335,6 +348,17 @@ class Hip:
             assert got == d["expect_slabs"], f"{d['label']}: adm_conv_stat_slabs answers {got}, not {d['expect_slabs']}"
         return launch_conv(lib, self.conv_fn or lib.adm_conv, d, t, packed, w32p, out, g)
 
+    def conv_try(self, d, T, t, packed, w32p, out, g):
+        """The same launch where a refusal is an answer -> (accepted, stats | None, adm_conv_stat_slabs' answer | None,
+        adm_conv_pick_variant's answer).  Any status but 0 and the three refusals raises."""
+        from autodiffusion_amd import _lib
+        lib = _lib.load(lr.KIND_OF_DTYPE[T])
+        variant = lib.adm_conv_pick_variant(C.byref(conv_args(d, t, packed, w32p, out)))
+        rc, stats, slabs = submit_conv(lib, self.conv_fn or lib.adm_conv, d, t, packed, w32p, out, g)
+        if rc not in REFUSALS:
+            _lib.check(rc, "adm_conv (envelope)")
+        return rc == 0, stats, slabs, variant
+
     def attention_lse(self, qkv, out, lse, heads, d, new_order):
         n, t, _ = qkv.shape
         self.call(qkv.dtype, "adm_attention_lse", _p(qkv), _p(out), _p(lse), n, t, heads, d, int(new_order))
@@ -380,14 +404,55 @@ class Hip:
 
 
 # ------------------------------------------------------------------ case runners (backend: Hip, or the host emulation)
-def run_conv(be, ops, d, T, device, seed):
-    g = Guarded(device)
-    t, packed, w32p, out = conv_operands(ops, d, T, seed, device, g)
-    stats = be.conv(d, T, t, packed, w32p, out, g)
+def judge_conv(g, d, T, t, out, stats, seed):
+    """What an accepted launch is held to: margins intact and every element of every output finite (Guarded.check), then the
+    restatement's bounds -> (worst err / bound, relative Frobenius error, ok)."""
     g.check()
     worst, fro = compare_conv(d, T, t, out, stats, seed)
     u = lr.U[T]
     return worst, fro, worst <= 1.0 and fro <= lr.fro_bound(lr.conv_roundings(d), u)
+
+
+def run_conv(be, ops, d, T, device, seed):
+    g = Guarded(device)
+    t, packed, w32p, out = conv_operands(ops, d, T, seed, device, g)
+    stats = be.conv(d, T, t, packed, w32p, out, g)
+    return judge_conv(g, d, T, t, out, stats, seed)
+
+
+def untouched(g):
+    """What a refused launch is held to: nothing was launched -- every output carve is NaN in every interior element still, and
+    all margins (the inputs' too) are intact."""
+    for c in g.carves:
+        c.guard_ok()
+        if c.output:
+            written = ~torch.isnan(c.view)
+            if bool(written.any()):
+                idx = tuple(int(i) for i in written.nonzero()[0])
+                raise AssertionError(f"{c.what}: the refused launch wrote {int(written.sum())} of {written.numel()} elements, the first at {idx}")
+
+
+def try_conv(be, ops, d, T, device, seed, must=False):
+    """One adm_conv request whose acceptance is the question.  Exactly two outcomes pass -> ("accepted", worst, fro) with
+    judge_conv's conditions, or ("refused", None, None) with untouched()'s.  Besides: adm_conv_pick_variant answers d["expect"]
+    where the case names one, adm_conv_stat_slabs answers > 0 exactly where the request with out_stats is accepted, and a `must`
+    case is not refused."""
+    g = Guarded(device)
+    t, packed, w32p, out = conv_operands(ops, d, T, seed, device, g)
+    accepted, stats, slabs, variant = be.conv_try(d, T, t, packed, w32p, out, g)
+    where = f"{d['label']} {d['h']}x{d['w']}"
+    if d.get("expect") is not None:
+        assert variant == d["expect"], f"{where}: adm_conv_pick_variant answers {variant}, the case is meant for variant {d['expect']}"
+    if d["has_out_stats"]:
+        assert (slabs > 0) == accepted, (f"{where}: adm_conv_stat_slabs answers {slabs} and adm_conv "
+                                         f"{'accepts' if accepted else 'refuses'} the request with out_stats")
+    if not accepted:
+        assert not must, f"{where}: a must-accept case was refused"
+        untouched(g)
+        return "refused", None, None
+    worst, fro, ok = judge_conv(g, d, T, t, out, stats, seed)
+    assert ok, f"{where}: worst err/bound {worst:.3f}, fro/u {fro / lr.U[T]:.3f} (bound {lr.fro_bound(lr.conv_roundings(d), 1.0):.3f})"
+    return "accepted", worst, fro
 
 
 def _heads_of(x, heads, d):

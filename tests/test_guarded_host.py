@@ -71,6 +71,22 @@ class Emulated:
         self._spoil(g, out, t["x0"])
         return stats
 
+    def conv_try(self, d, T, t, packed, w32p, out, g):
+        """guarded.Hip.conv_try's answers from the emulation, which accepts everything; the envelope's defects refuse, or leave
+        the columns behind the 16-pixel tile row unwritten."""
+        slabs = (d["expect_slabs"] or 1) if d["has_out_stats"] else None
+        if self.defect == "refused":
+            return False, None, 0 if slabs else None, d["expect"]
+        if self.defect == "slabs offered, then refused":
+            return False, None, slabs, d["expect"]
+        if self.defect == "refused after a partial write":
+            out.view(-1)[:8] = 0.0
+            return False, None, 0 if slabs else None, d["expect"]
+        stats = self.conv(d, T, t, packed, w32p, out, g)
+        if self.defect == "columns >= 16 unwritten":
+            (out[..., 16:] if d["out_mode"] == 1 else out[:, :, 16:]).fill_(float("nan"))
+        return True, stats, slabs, d["expect"]
+
     def attention_lse(self, qkv, out, lse, heads, d, new_order):
         n = qkv.shape[0]
         q, k, v = lr.split_qkv(qkv, heads, new_order)
