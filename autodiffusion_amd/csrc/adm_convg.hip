@@ -421,6 +421,67 @@ resize_bilinear_kernel(const void* __restrict__ in, uint16_t* __restrict__ out, 
   }
 }
 
+// cubic convolution coefficients (Keys, A = -0.75) of the taps floor(s) - 1 .. floor(s) + 2 at the fraction t = s - floor(s)
+__device__ __forceinline__ void cubic_coeffs(float t, float c[4]) {
+  const float A = -0.75f;
+  const float u = 1.0f - t, p = t + 1.0f, q = 2.0f - t;
+  c[0] = ((A * p - 5.0f * A) * p + 8.0f * A) * p - 4.0f * A;
+  c[1] = ((A + 2.0f) * t - (A + 3.0f)) * t * t + 1.0f;
+  c[2] = ((A + 2.0f) * u - (A + 3.0f)) * u * u + 1.0f;
+  c[3] = ((A * q - 5.0f * A) * q + 8.0f * A) * q - 4.0f * A;
+}
+
+// bicubic resize (adm_resize_bilinear with half_pixel == 2): torch F.interpolate(mode="bicubic", align_corners=True).
+// src = dst * (in - 1) / (out - 1), 0 where out == 1; the four taps per axis are clamped to the border; fp32 throughout,
+// value * scale + shift on the interpolated value, one rounding.  Inputs, output layout and the thread-per-segment mapping are
+// those of resize_bilinear_kernel (a gather of 16 taps per channel straight from global memory: the sources are a few MB).
+__global__ void __launch_bounds__(256)
+resize_bicubic_kernel(const void* __restrict__ in, uint16_t* __restrict__ out, int n, int h, int w, int oh, int ow,
+                      int cpad, int kind, float scale, float shift) {
+  const int segs = cpad / 8;
+  const long long items = (long long)n * oh * ow * segs;
+  const float ry = oh > 1 ? (float)(h - 1) / (float)(oh - 1) : 0.0f, rx = ow > 1 ? (float)(w - 1) / (float)(ow - 1) : 0.0f;
+  for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (long long)gridDim.x * blockDim.x) {
+    const int sg = (int)(it % segs);
+    const long long pix = it / segs;
+    uint4 val = make_uint4(0, 0, 0, 0);
+    if (sg == 0) {
+      const int ox = (int)(pix % ow), oy = (int)((pix / ow) % oh), img = (int)(pix / ((long long)ow * oh));
+      const float sy = (float)oy * ry, sx = (float)ox * rx;
+      const int iy = min((int)sy, h - 1), ix = min((int)sx, w - 1);   // sy, sx >= 0: truncation is floor
+      float cy[4], cx[4];
+      cubic_coeffs(sy - (float)iy, cy);
+      cubic_coeffs(sx - (float)ix, cx);
+      int ys[4], xs[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        ys[j] = min(max(iy - 1 + j, 0), h - 1);
+        xs[j] = min(max(ix - 1 + j, 0), w - 1);
+      }
+      float v[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        auto at = [&](int y, int x) -> float {
+          if (kind == 0) return (float)reinterpret_cast<const uint8_t*>(in)[(((long long)img * h + y) * w + x) * 3 + ch];
+          if (kind == 1) return reinterpret_cast<const float*>(in)[(((long long)img * 3 + ch) * h + y) * w + x];
+          return reinterpret_cast<const float*>(in)[(((long long)img * h + y) * w + x) * 3 + ch];
+        };
+        // torch's order: the four taps of a row along x, then the four rows along y
+        float acc = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float row = at(ys[i], xs[0]) * cx[0] + at(ys[i], xs[1]) * cx[1] + at(ys[i], xs[2]) * cx[2] + at(ys[i], xs[3]) * cx[3];
+          acc += row * cy[i];
+        }
+        v[ch] = acc * scale + shift;
+      }
+      val.x = adm_pack2(v[0], v[1]);
+      val.y = adm_pack2(v[2], 0.0f);
+    }
+    *reinterpret_cast<uint4*>(out + it * 8) = val;
+  }
+}
+
 int grid_for_items(long long items) {
   long long b = (items + 255) / 256;
   if (b > 8192) b = 8192;
@@ -512,7 +573,14 @@ extern "C" int adm_resize_bilinear(const void* in, adm_bf16* out, int n, int h, 
   ADM_REQUIRE(in && out, ADM_E_ARG, "adm_resize_bilinear: null pointer");
   ADM_REQUIRE(n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0 && cpad >= 8 && cpad % 8 == 0 && kind >= 0 && kind <= 2, ADM_E_ARG,
               "adm_resize_bilinear: bad arguments");
+  ADM_REQUIRE(half_pixel >= 0 && half_pixel <= 2, ADM_E_ARG,
+              "adm_resize_bilinear: half_pixel %d (0: TensorFlow-1 bilinear, 1: half-pixel bilinear, 2: bicubic align_corners)", half_pixel);
   ADM_REQUIRE(adm_aligned16(out), ADM_E_ALIGN, "adm_resize_bilinear: unaligned output");
+  if (half_pixel == 2) {
+    hipLaunchKernelGGL(resize_bicubic_kernel, dim3(grid_for_items((long long)n * oh * ow * (cpad / 8))), dim3(256), 0, (hipStream_t)stream,
+                       in, reinterpret_cast<uint16_t*>(out), n, h, w, oh, ow, cpad, kind, scale, shift);
+    return adm_check_launch("adm_resize_bilinear");
+  }
   hipLaunchKernelGGL(resize_bilinear_kernel, dim3(grid_for_items((long long)n * oh * ow * (cpad / 8))), dim3(256), 0, (hipStream_t)stream,
                      in, reinterpret_cast<uint16_t*>(out), n, h, w, oh, ow, cpad, kind, half_pixel, scale, shift);
   return adm_check_launch("adm_resize_bilinear");

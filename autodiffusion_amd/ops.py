@@ -873,8 +873,9 @@ def global_avgpool_f32(x):
 
 def resize_bilinear(images, oh: int, ow: int, cpad: int, layout: str, half_pixel: bool, scale: float, shift: float, dtype=F16):
     """3-channel images -> [N, oh, ow, cpad] 16-bit NHWC (channels 3.. zero), value * scale + shift.
-    layout "u8_nhwc" | "f32_nchw" | "f32_nhwc"."""
-    kind = {"u8_nhwc": 0, "f32_nchw": 1, "f32_nhwc": 2}[layout]
+    layout "u8_nhwc" | "f32_nchw" | "f32_nhwc".  half_pixel False / 0: TensorFlow-1 ResizeBilinear; True / 1: torch bilinear,
+    align_corners=False; 2: torch bicubic, align_corners=True (A = -0.75, border-clamped taps)."""
+    kind ={"u8_nhwc": 0, "f32_nchw": 1, "f32_nhwc": 2}[layout]
     want = torch.uint8 if kind == 0 else torch.float32
     if images.dim() != 4 or images.shape[1 if kind == 1 else 3] != 3:
         raise AdmError(f"resize_bilinear: expected 3-channel {layout} images, got {tuple(images.shape)}")

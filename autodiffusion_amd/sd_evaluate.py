@@ -63,16 +63,23 @@ def inception_features(net, dims: int = 2048, allow_random: bool = False):
 class SDCandidateEvaluator:
     def __init__(self, model, sampler, conditioning=None, ref_mu=None, ref_sigma=None, num_samples: int = None, *, prompts=None,
                  features=None, inception=None, dims: int = 2048, allow_random_inception: bool = False, seed: int = 0,
-                 device=None, image_out=None, accumulator=None):
+                 device=None, image_out=None, accumulator=None, clip_scorer=None):
         """model: ``sd_sampler.LatentDiffusion`` with a first stage (``decode_first_stage``); sampler: one of the
         ``sd_sampler`` samplers around it; conditioning: iterable of per-batch ``(c, uc)`` device tensors (``uc`` may be None
         when ``opt.scale == 1``), re-iterated by every call; prompts (instead of conditioning; the model then needs a cond
         stage): iterable of per-batch prompts -- a list or tuple of strings, or an integer tensor [n_samples, T] of token ids --
         encoded by ``model.get_learned_conditioning``; features: callable float [N, 3, H, W] in [0, 1] -> [N, dims]
         (default: ``inception`` -- an ``InceptionV3`` -- through ``inception_features``).
-        image_out / accumulator: the clamp launch and the statistics sink, replaceable for host-only tests of the batch plan."""
+        image_out / accumulator: the clamp launch and the statistics sink, replaceable for host-only tests of the batch plan.
+        clip_scorer (with prompts= only): an ``sd_clip.CLIPScorer`` -- anything with ``cosine(images, prompts) -> [N]`` and
+        ``score_of(cosines)``; every batch's clamped [0, 1] images, the ones the extractor sees, are also scored against that batch's
+        prompts: ``last_clip`` = {"score", "cosines", "clip_time"} (clip_time: wall time inside the scorer's calls, which are part of
+        sample_time and begin by waiting for the batch's images).  The FID does not change by a bit."""
         if (conditioning is None) == (prompts is None):
             raise ValueError("SDCandidateEvaluator: pass exactly one of conditioning= (precomputed (c, uc) batches) and prompts=")
+        if clip_scorer is not None and prompts is None:
+            raise ValueError("SDCandidateEvaluator: clip_scorer= scores images against their prompts: pass prompts=, not conditioning=")
+        self.clip_scorer, self.last_clip = clip_scorer, None
         if ref_mu is None or ref_sigma is None or num_samples is None:
             raise ValueError("SDCandidateEvaluator: ref_mu, ref_sigma and num_samples are required")
         self.model, self.sampler, self.conditioning, self.prompts = model, sampler, conditioning, prompts
@@ -101,9 +108,10 @@ class SDCandidateEvaluator:
 
     # ------------------------------------------------------------------ search_ea.py:520-526
     def _batches(self, opt):
-        """Per-batch (c, uc): the conditioning iterable as it is, or the prompts through the model's cond stage."""
+        """Per-batch (c, uc, prompts | None): the conditioning iterable as it is, or the prompts through the model's cond stage."""
         if self.prompts is None:
-            yield from self.conditioning
+            for c, uc in self.conditioning:
+                yield c, uc, None
             return
         for prompts in self.prompts:
             uc = None
@@ -113,7 +121,7 @@ class SDCandidateEvaluator:
                     uc = self._uc[opt.n_samples] = self.model.get_learned_conditioning(opt.n_samples * [""])
             if isinstance(prompts, tuple):
                 prompts = list(prompts)
-            yield self.model.get_learned_conditioning(prompts), uc
+            yield self.model.get_learned_conditioning(prompts), uc, prompts
 
     # ------------------------------------------------------------------ search_ea.py:504-566
     def get_cand_fid(self, cand=None, opt=None, device=None):
@@ -124,8 +132,9 @@ class SDCandidateEvaluator:
         sampled_timestep = np.array(cand)
         acc = self._accumulator()
         stage, fill, count, plan = None, 0, 0, []
+        cosines, clip_time = [], 0.0
         with torch.no_grad():
-            for itr, (c, uc) in enumerate(self._batches(opt)):
+            for itr, (c, uc, prompts) in enumerate(self._batches(opt)):
                 if opt.scale == 1.0:
                     uc = None
                 seed = batch_seed(seed0, 0 if opt.fixed_code else itr)
@@ -143,6 +152,10 @@ class SDCandidateEvaluator:
                 while done < x.shape[0]:
                     take = min(x.shape[0] - done, FID_BATCH - fill)
                     self._image_out(x[done:done + take], stage[fill:fill + take])
+                    if self.clip_scorer is not None:
+                        t0 = time.time()
+                        cosines.append(torch.as_tensor(self.clip_scorer.cosine(stage[fill:fill + take], prompts[done:done + take])).cpu())
+                        clip_time += time.time() - t0
                     fill, done = fill + take, done + take
                     if fill == FID_BATCH:
                         acc.add(self.features(stage))
@@ -166,4 +179,8 @@ class SDCandidateEvaluator:
         logger.log('sample_time: ' + str(sample_time) + ', fid_time: ' + str(fid_time))
         self.last_times = {"sample_time": sample_time, "fid_time": fid_time, "images": count, "batches": len(plan)}
         self.last_plan = plan
+        if self.clip_scorer is not None:
+            cos = torch.cat(cosines)
+            self.last_clip = {"score": float(self.clip_scorer.score_of(cos)), "cosines": cos, "clip_time": clip_time}
+            logger.log('CLIP score: ' + str(self.last_clip["score"]) + ', clip_time: ' + str(clip_time))
         return fid

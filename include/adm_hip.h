@@ -394,7 +394,10 @@ int adm_pool2d(const adm_bf16* in, adm_bf16* out, int n, int h, int w, int c, in
 /* mean over the hw pixels: [n][hw][c] -> fp32 [n][c] (the pool3 features)                                                 */
 int adm_global_avgpool_f32(const adm_bf16* in, float* out, int n, int hw, int c, void* stream);
 /* 3-channel images -> [n][oh][ow][cpad] (channels 3.. zero), value * scale + shift.  kind 0: uint8 NHWC, 1: fp32 NCHW,
- * 2: fp32 NHWC.  half_pixel 1: torch bilinear, align_corners=False (pytorch_fid); 0: TensorFlow-1 ResizeBilinear.          */
+ * 2: fp32 NHWC.  half_pixel 1: torch bilinear, align_corners=False (pytorch_fid); 0: TensorFlow-1 ResizeBilinear;
+ * 2: torch BICUBIC, align_corners=True (the CLIP image entry): src = dst (in - 1) / (out - 1), 0 where out == 1, cubic
+ * convolution with A = -0.75 over four border-clamped taps per axis, fp32, scale and shift on the interpolated value, one
+ * rounding.  Any other half_pixel: ADM_E_ARG.                                                                             */
 int adm_resize_bilinear(const void* in, adm_bf16* out, int n, int h, int w, int oh, int ow, int cpad, int kind, int half_pixel,
                         float scale, float shift, void* stream);
 

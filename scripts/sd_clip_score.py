@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""CLIP score of a sample file against its prompts, on the HIP path.
+
+    sd_clip_score.py SAMPLES.npz --clip_ckpt CLIP.pt (--prompt_ids IDS.npy | --captions FILE --tokenizer_dir DIR)
+
+``SAMPLES.npz`` holds uint8 images ``arr_0`` [N, H, W, 3] (what the sampling scripts write as ``samples_*.npz``); image i is scored
+against prompt i: row i of the int64 [num >= N, T] array ``--prompt_ids``, or caption i of ``--captions`` (a COCO-style JSON or one
+caption per line) tokenised by the ``transformers`` tokenizer in the LOCAL directory ``--tokenizer_dir``.  ``--clip_ckpt`` is ONE
+plain state dict holding both CLIP ViT-L/14 towers, in transformers' ``CLIPModel`` layout or the OpenAI ``clip`` package's, read
+with ``dist_util.load_state_dict``; nothing is fetched.
+
+The score is this project's (``sd_clip.CLIPScorer``; the reference has no CLIP-score script): 100 * mean(max(cos_i, 0)) with
+cos_i the cosine of ``encode_image`` of image i -- behind the reference embedder's bicubic resize to 224 -- and ``encode_text`` of
+prompt i.  ``--synthetic tiny`` builds the tiny towers with random weights instead of reading ``--clip_ckpt``: tests.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from autodiffusion_amd import dist_util, sd_clip  # noqa: E402
+from autodiffusion_amd.evaluator import iter_npz_batches  # noqa: E402
+
+
+def create_argparser():
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p.add_argument("samples", help="npz with uint8 images arr_0 [N, H, W, 3]")
+    p.add_argument("--clip_ckpt", type=str, default="", help="a CLIP state dict holding both towers (CLIPModel or OpenAI layout)")
+    p.add_argument("--prompt_ids", type=str, default="", help=".npy with an int64 [num, T] array of token ids")
+    p.add_argument("--captions", type=str, default="", help="COCO-style annotations JSON, or a text file with one caption per line")
+    p.add_argument("--tokenizer_dir", type=str, default="", help="LOCAL directory of the transformers CLIP tokenizer")
+    p.add_argument("--batch_size", type=int, default=64)
+    p.add_argument("--torso", choices=["bf16", "fp16"], default="bf16")
+    p.add_argument("--synthetic", choices=["tiny"], default="", help="random tiny towers instead of --clip_ckpt")
+    return p
+
+
+def read_captions(path):
+    with open(path, "r", encoding="utf-8") as f:
+        text = f.read()
+    if text.lstrip().startswith("{"):
+        return [a["caption"].lower() for a in json.loads(text)["annotations"]]
+    return [line.strip() for line in text.splitlines() if line.strip()]
+
+
+def main(argv=None):
+    opt = create_argparser().parse_args(argv)
+    if bool(opt.prompt_ids) == bool(opt.captions):
+        raise SystemExit("sd_clip_score.py: give exactly one of --prompt_ids IDS.npy and --captions FILE")
+    if opt.captions and not opt.tokenizer_dir:
+        raise SystemExit("sd_clip_score.py: --captions needs --tokenizer_dir (a local CLIP tokenizer directory)")
+    if not opt.synthetic and not opt.clip_ckpt:
+        raise SystemExit("sd_clip_score.py: give --clip_ckpt (or --synthetic tiny)")
+    device = dist_util.dev()
+    if device.type != "cuda":
+        raise SystemExit("sd_clip_score.py: no GPU is visible (the HIP path has no CPU fallback)")
+    torch.cuda.set_device(device)
+    if opt.prompt_ids:
+        prompts = np.load(opt.prompt_ids, allow_pickle=False)
+        if prompts.ndim != 2 or not np.issubdtype(prompts.dtype, np.integer):
+            raise SystemExit(f"sd_clip_score.py: --prompt_ids must hold an integer [num, T] array, got {prompts.dtype} {prompts.shape}")
+        prompts = torch.from_numpy(prompts.astype(np.int64))
+        max_length = int(prompts.shape[1])
+    else:
+        prompts, max_length = read_captions(opt.captions), 77
+    tiny = opt.synthetic == "tiny"
+    scorer = sd_clip.build_clip_scorer(None if tiny else dist_util.load_state_dict(opt.clip_ckpt),
+                                       sd_clip.CLIP_TINY_VISION if tiny else None, sd_clip.CLIP_TINY_TEXT_PROJ if tiny else None,
+                                       device=device, torso=opt.torso, tokenizer_dir=opt.tokenizer_dir or None, max_length=max_length)
+    if tiny:
+        print("--synthetic tiny: the towers hold RANDOM weights; the score below is not a quality metric")
+    t0, done, cosines = time.time(), 0, []
+    for batch in iter_npz_batches(opt.samples, "arr_0", opt.batch_size):
+        if batch.ndim != 4 or batch.shape[3] != 3 or batch.dtype != np.uint8:
+            raise SystemExit(f"sd_clip_score.py: arr_0 must hold uint8 [N, H, W, 3] images, got {batch.dtype} {batch.shape}")
+        n = batch.shape[0]
+        if done + n > len(prompts):
+            raise SystemExit(f"sd_clip_score.py: {len(prompts)} prompts for more than {done + n - 1} images")
+        cosines.append(scorer.cosine(torch.from_numpy(np.ascontiguousarray(batch)).to(device), prompts[done:done + n]))
+        done += n
+    if not done:
+        raise SystemExit("sd_clip_score.py: the sample file holds no image")
+    cos = torch.cat(cosines)
+    score = scorer.score_of(cos)
+    print(f"images: {done}, mean cosine: {float(cos.double().mean()):.6f}, time: {time.time() - t0:.2f} s")
+    print(f"CLIP score: {score}")
+    return score
+
+
+if __name__ == "__main__":
+    main()

@@ -19,6 +19,9 @@ CLIP's start- and end-of-text).  FID: ``--inception_path`` is the pytorch_fid ch
 take the reference's ``.npy`` pair; ``--ref_mu`` alone may name an ``.npz`` holding ``mu`` and ``sigma`` (what
 ``scripts/evaluator.py --save_ref_stats`` writes).  ``--torso {bf16,fp16}`` selects the 16-bit torso; ``--population_parallel``
 shards whole candidates over ranks (candidate i on rank i % world, one all_gather of the FIDs per epoch).
+``--clip_ckpt PATH`` also scores every candidate's images against their prompts (``sd_clip.CLIPScorer``, a ``CLIP score:`` log line
+per candidate; the fitness stays the FID): PATH is ONE plain state dict holding both CLIP towers, in transformers' ``CLIPModel``
+layout or the OpenAI layout, read with ``dist_util.load_state_dict`` (ViT-L/14; under ``--synthetic tiny`` the tiny towers).
 ``--evaluate "[t0, t1, ...]"`` scores that one candidate over ``--num_sample`` images, prints the FID and exits (the reference's
 txt2img_fid.py use of a searched schedule).  ``--synthetic {tiny,v1}`` builds the networks with ``randomize_()`` instead of
 reading ``--ckpt``: tests and throughput runs.
@@ -115,6 +118,8 @@ def create_argparser():
                    help="run without --inception_path: every FID line is then tagged as computed on RANDOM Inception weights")
     p.add_argument("--torso", choices=["bf16", "fp16"], default="bf16", help="16-bit type of activations and weights between kernels")
     p.add_argument("--population_parallel", action="store_true", help="evaluate candidate i on rank i %% world, one all_gather per epoch")
+    p.add_argument("--clip_ckpt", type=str, default="",
+                   help="a CLIP state dict (both towers, CLIPModel or OpenAI layout): also log every candidate's CLIP score")
     p.add_argument("--evaluate", type=str, default="", help="'[t0, t1, ...]': score this one candidate, print its FID and exit")
     p.add_argument("--synthetic", choices=["tiny", "v1"], default="", help="build the networks with randomize_() instead of reading --ckpt")
     return p
@@ -249,6 +254,16 @@ def build_inception(opt, device):
     return net
 
 
+def build_clip_scorer(opt, device, prompt_len=None):
+    """--clip_ckpt: the CLIPScorer of both towers from one file (the tiny towers under --synthetic tiny)."""
+    from autodiffusion_amd import sd_clip
+    tiny = opt.synthetic == "tiny"
+    return sd_clip.build_clip_scorer(dist_util.load_state_dict(opt.clip_ckpt),
+                                     sd_clip.CLIP_TINY_VISION if tiny else None, sd_clip.CLIP_TINY_TEXT_PROJ if tiny else None,
+                                     device=device, torso=opt.torso, tokenizer_dir=opt.tokenizer_dir or None,
+                                     max_length=77 if prompt_len is None or opt.tokenizer_dir else int(prompt_len))
+
+
 def build_sampler(opt, model):
     from autodiffusion_amd.sd_sampler import DDIMSampler, DPMSolverSampler, PLMSSampler
     if opt.dpm_solver:
@@ -274,7 +289,7 @@ def main(argv=None, *, evaluator=None):
         logger.log("ignored flags (accepted for the reference's command lines, unused on this path): "
                    + ", ".join("--" + k for k in ignored))
     ref_mu, ref_sigma = load_ref_stats(opt)
-    model = sampler = inception = None
+    model = sampler = inception = clip_scorer = None
     dpm_params = None
     if evaluator is None:
         device = dist_util.dev()
@@ -286,6 +301,8 @@ def main(argv=None, *, evaluator=None):
         model = build_model(opt, device, prompt_len=ids.shape[1] if torch.is_tensor(ids) else None)
         sampler = build_sampler(opt, model)
         inception = build_inception(opt, device)
+        if opt.clip_ckpt:
+            clip_scorer = build_clip_scorer(opt, device, prompt_len=ids.shape[1] if torch.is_tensor(ids) else None)
         alphas_cumprod = model.alphas_cumprod
     else:
         loader = []
@@ -297,7 +314,7 @@ def main(argv=None, *, evaluator=None):
     searcher = EvolutionSearcher(opt=opt, model=model, time_step=opt.time_step, ref_mu=ref_mu, ref_sigma=ref_sigma, sampler=sampler,
                                  dataloader_info={"validation_loader": loader}, batch_size=opt.n_samples, dpm_params=dpm_params,
                                  evaluator=evaluator, population_parallel=opt.population_parallel, inception=inception,
-                                 allow_random_inception=opt.allow_random_inception)
+                                 allow_random_inception=opt.allow_random_inception, clip_scorer=clip_scorer)
     if opt.evaluate:
         cand = parse_sd_candidate(opt.evaluate, "--evaluate")
         want = opt.time_step + (1 if opt.dpm_solver else 0)

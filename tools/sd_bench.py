@@ -12,7 +12,10 @@ per torso (ms per call, launches per call, model TFLOP/s from the plan's algorit
 from torch's own 16-bit ops on the same weights, alternating, median of 5 windows of 20 calls.
 --vae-encode times the first stage's other half: `encode_first_stage` of 1 and 8 images of 512 x 512 through the v1 KL-f8 encoder per
 torso (ms per pass and per image, median of 5 passes after 2 warm-ups; TFLOP/s and the fraction of the 2.5 PFLOP/s dense 16-bit MFMA
-peak on the plan's algorithmic FLOPs and on the executed ones, which run the three Downsample convs at stride 1)."""
+peak on the plan's algorithmic FLOPs and on the executed ones, which run the three Downsample convs at stride 1).
+--clip-image times the CLIP ViT-L/14 image tower (`FrozenClipImageEmbedder`, random weights) on 6 and 320 images of 512 x 512 in
+[-1, 1] per torso: ms per call, images/s and model TFLOP/s from the plan's algorithmic FLOPs, median of 5 windows; and the bicubic
+resize entry alone."""
 import os
 import sys
 import time
@@ -204,6 +207,27 @@ def encode_bench():
         del emb, composed
 
 
+def clip_image_bench():
+    import statistics
+    from autodiffusion_amd.sd_clip import FrozenClipImageEmbedder
+    for torso in ("bf16", "fp16"):
+        emb = FrozenClipImageEmbedder("ViT-L/14", device="cpu").set_torso(torso).randomize_(1357).to(DEV)
+        plan = emb.model.plan
+        for n, reps in ((6, 10), (320, 2)):
+            x = torch.rand(n, 3, 512, 512, device=DEV, generator=torch.Generator(device=DEV).manual_seed(n)) * 2 - 1
+            for _ in range(2):
+                out = emb(x)
+            torch.cuda.synchronize()
+            assert out.shape == (n, plan.projection_dim) and torch.isfinite(out).all()
+            ta = [_timed(lambda: emb(x), reps) for _ in range(5)]
+            tr = [_timed(lambda: emb.preprocess(x), reps) for _ in range(5)]
+            ma, fl = statistics.median(ta), n * plan.flops()
+            print(f"CLIP ViT-L/14 image tower [{torso}] {n} images 512x512: {ma:.2f} ms / call, {n / ma * 1e3:.1f} images/s, "
+                  f"{fl / ma / 1e9:.1f} model TFLOP/s (windows {min(ta):.2f} .. {max(ta):.2f}); bicubic entry alone "
+                  f"{statistics.median(tr):.3f} ms; {plan.tokens} tokens in {plan.pitch} rows ({1 - plan.tokens / plan.pitch:.1%} dead)")
+        del emb
+
+
 def sampler_bench(m):
     from autodiffusion_amd.sd_sampler import DDIMSampler, DPMSolverSampler, LatentDiffusion, PLMSSampler
     kind = os.environ["SAMPLER"]
@@ -241,5 +265,7 @@ if __name__ == "__main__":
         vae_encode_bench()
     elif "--encode" in sys.argv[1:]:
         encode_bench()
+    elif "--clip-image" in sys.argv[1:]:
+        clip_image_bench()
     else:
         main()
