@@ -20,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import AdmError, SdStepCoefs, check
 
 
@@ -269,6 +269,15 @@ def axpby_noise(x, a, noise, b):
     return out
 
 
+def masked_blend(img, orig, keep, drop):
+    """ddim.py:160 / plms.py:162 ``img_orig * mask + (1. - mask) * img`` for a 0/1 mask, from launches the library has: ``keep`` is
+    the mask expanded to the latent's shape, ``drop`` = 1 - keep.  ``vec_act(m, "relu", dy=t)`` is t * [m > 0] (t itself, or a zero)
+    and ``axpby_noise(a, 1, b, 1)`` adds the two disjoint halves, so every element is ``orig`` or ``img`` to the bit: a select
+    in three launches (four per step with ``q_sample``'s).  Adding the other half's zero turns a selected -0.0 into +0.0, as the
+    reference's expression does; every other value, denormals included, keeps its bits."""
+    return axpby_noise(ops.vec_act(keep, "relu", dy=orig), 1.0, ops.vec_act(drop, "relu", dy=img), 1.0)
+
+
 def _one_index(t, size, who):
     """The single index a batch of equal indices (tensor, sequence or int) stands for; it must lie in [0, size)."""
     vals = {int(v) for v in torch.as_tensor(t).reshape(-1).tolist()}
@@ -322,7 +331,15 @@ class _LatentSampler:
         self._c_in = torch.cat([uc, c]) if (self._guided and not self._split) else c
         self._key = ("sample", next(_CALL_IDS)) if getattr(self.model, "accepts_context_key", False) else None
 
-    def _eps(self, x, t):
+    def _eps(self, x, t, uncond_only=False):
+        if uncond_only:
+            # plms.py:164-171: one evaluation of N on the unconditional conditioning, on the CURRENT stream.  sd_unet.py keeps one
+            # set of conditioning projections and one graph per shape PER LAUNCHING STREAM, so this call never touches what the
+            # side stream holds under the same key (split guidance); it replaces the current stream's projections (the guided
+            # step that follows recomputes them) and replays the current stream's own graph, in stream order.
+            if self._key is not None:
+                return self.model.apply_model(x, t, self._uc, context_key=(self._key, "u"))
+            return self.model.apply_model(x, t, self._uc)
         if self._guided and self._split:
             cur = torch.cuda.current_stream(x.device)
             side = _SIDE_STREAMS.get(x.device)
@@ -352,18 +369,67 @@ class _LatentSampler:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, sampled_timestep=None, **kwargs):
-        self._unsupported(quantize_x0=quantize_x0, mask=mask is not None, noise_dropout=noise_dropout > 0.,
-                          score_corrector=score_corrector is not None)
+               unconditional_conditioning=None, sampled_timestep=None, prompt_mask=None, **kwargs):
+        self._unsupported(quantize_x0=quantize_x0, noise_dropout=noise_dropout > 0., score_corrector=score_corrector is not None)
         if conditioning is not None and not isinstance(conditioning, dict) and conditioning.shape[0] != batch_size:
             print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+        C_, H, W = shape
+        self._check_mask(mask, x0, (batch_size, C_, H, W))
         sampled_timestep = self._order(sampled_timestep)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose, sampled_timestep=sampled_timestep)
-        C_, H, W = shape
-        return self._loop(conditioning, (batch_size, C_, H, W), x_T=x_T, callback=callback, img_callback=img_callback,
-                          log_every_t=log_every_t, temperature=temperature,
-                          unconditional_guidance_scale=unconditional_guidance_scale,
-                          unconditional_conditioning=unconditional_conditioning)
+        self._prompt_mask = self._check_prompt_mask(prompt_mask, len(self.ddim_timesteps), unconditional_conditioning)
+        self._mask = self._begin_mask(mask, x0, (batch_size, C_, H, W))
+        try:
+            return self._loop(conditioning, (batch_size, C_, H, W), x_T=x_T, callback=callback, img_callback=img_callback,
+                              log_every_t=log_every_t, temperature=temperature,
+                              unconditional_guidance_scale=unconditional_guidance_scale,
+                              unconditional_conditioning=unconditional_conditioning)
+        finally:
+            self._mask = self._prompt_mask = None
+
+    # ---- masked sampling (ddim.py:157-160, plms.py:159-162): mask 1 keeps x0, 0 is generated
+    _mask = None          # (keep, drop, x0) during a masked sample() call
+    _prompt_mask = None   # PLMS only: per loop position, 0 = that step runs unguided on the unconditional conditioning
+
+    def _check_mask(self, mask, x0, shape):
+        """The host-side checks, before any launch: the layout first, then x0 (the reference asserts it, ddim.py:158)."""
+        if mask is None:
+            return
+        n, c, h, w = shape
+        if not (torch.is_tensor(mask) and mask.dim() == 4 and mask.shape[0] in (1, n) and mask.shape[1] in (1, c)
+                and tuple(mask.shape[2:]) == (h, w)):
+            got = tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__
+            raise NotImplementedError(f"{type(self).__name__}: mask {got} is not built on the HIP path; accepted layouts are "
+                                      f"[N or 1, C or 1, H, W] for latents {shape}")
+        if not torch.is_tensor(x0) or tuple(x0.shape) != tuple(shape):
+            got = None if x0 is None else (tuple(x0.shape) if torch.is_tensor(x0) else type(x0).__name__)
+            raise AdmError(f"{type(self).__name__}: mask= needs x0= of the latents' shape {shape}, got {got}")
+
+    def _check_prompt_mask(self, prompt_mask, steps, uc):
+        return None   # PLMS only (plms.py:85); the reference's other samplers swallow the keyword unread, and so do these
+
+    def _begin_mask(self, mask, x0, shape):
+        """Per call: the values are checked on the device (one sync), the mask is expanded to contiguous fp32 ``keep`` and
+        ``drop`` = 1 - keep is formed by one launch."""
+        if mask is None:
+            return None
+        device = self.model.betas.device
+        if device.type != "cuda":
+            raise AdmError("latent samplers: the model's tables are on the CPU (the HIP path has no CPU fallback)")
+        m = mask.to(device=device, dtype=torch.float32)
+        if not bool(((m == 0) | (m == 1)).all()):
+            raise NotImplementedError(f"{type(self).__name__}: soft masks are not built on the HIP path (no fp32 launch multiplies two "
+                                      "tensors; the blend is a select): every mask value must be exactly 0 or 1")
+        keep = m.expand(shape).contiguous()
+        drop = axpby_noise(keep, -1.0, torch.ones_like(keep), 1.0)
+        return keep, drop, x0.to(device=device, dtype=torch.float32).contiguous()
+
+    def _blend(self, img, ts):
+        """Before the step's model call(s), exactly where the reference blends: the kept region becomes a freshly noised x0."""
+        if self._mask is None:
+            return img
+        keep, drop, x0 = self._mask
+        return masked_blend(img, self.model.q_sample(x0, ts), keep, drop)
 
 
 class DDIMSampler(_LatentSampler):
@@ -381,6 +447,9 @@ class DDIMSampler(_LatentSampler):
         for i, step in enumerate(np.flip(timesteps)):
             index = total - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
+            # ddim.py:157-160.  The reference does not blend again after the last update: the kept region of the RESULT is the
+            # model's last update of it, not x0; and x_inter below stays the post-step latent.
+            img = self._blend(img, ts)
             eps = self._eps(img, ts)
             sigma = self.ddim_sigmas[index]
             noise = torch.randn(shape, device=device) * temperature if sigma != 0 else None  # ddim.py:198 noise_like
@@ -439,6 +508,17 @@ class PLMSSampler(_LatentSampler):
     def _order(self, sampled_timestep):
         return sampled_timestep  # plms.py takes the list as given; search_ea.py sorts its candidates (:480)
 
+    def _check_prompt_mask(self, prompt_mask, steps, uc):
+        """plms.py:85,131,164: one entry per loop position i (entry 0 is the first, noisiest step)."""
+        if prompt_mask is None:
+            return None
+        pm = [int(v) for v in prompt_mask]
+        if len(pm) != steps:
+            raise AdmError(f"PLMSSampler: prompt_mask holds {len(pm)} entries for {steps} steps")
+        if uc is None and 0 in pm:
+            raise AdmError("PLMSSampler: a prompt_mask entry of 0 needs unconditional_conditioning")
+        return pm
+
     def _loop(self, cond, shape, x_T, callback, img_callback, log_every_t, temperature, unconditional_guidance_scale,
               unconditional_conditioning):
         device, img = self._start(shape, x_T)
@@ -455,10 +535,17 @@ class PLMSSampler(_LatentSampler):
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             ts_next = torch.full((b,), int(time_range[min(i + 1, len(time_range) - 1)]), device=device, dtype=torch.long)
             a_t, a_prev, sigma = self.ddim_alphas[index], self.ddim_alphas_prev[index], self.ddim_sigmas[index]
-            eps = self._eps(img, ts)
+            # plms.py:159-162: one blend per loop iteration, before BOTH model calls of the first step (the second one sees the
+            # predicted point, unblended).  Not repeated after the last update; x_inter below stays the post-step latent.
+            img = self._blend(img, ts)
+            # plms.py:164-171: on a prompt_mask entry of 0 every model call of the step is one unguided evaluation on the
+            # unconditional conditioning (scale 1), and that eps is what the multistep history keeps
+            un = self._prompt_mask is not None and self._prompt_mask[i] == 0
+            scale = 1.0 if un else unconditional_guidance_scale
+            eps = self._eps(img, ts, un)
             if len(old_eps) == 0:    # pseudo improved Euler (2nd order): a second model call at the predicted point
                 x_mid, _, e_t = sd_step(img, eps, b, scale, (1.0,), (), a_t, a_prev, sigma)
-                eps2 = self._eps(x_mid, ts_next)
+                eps2 = self._eps(x_mid, ts_next, un)
                 img, pred_x0, _ = sd_step(img, eps2, b, scale, (0.5, 0.5), (e_t,), a_t, a_prev, sigma, want_e=False)
             else:                    # Adams-Bashforth of order 2 / 3 / 4 over the kept eps history (newest first)
                 w = {1: (3 / 2, -1 / 2), 2: (23 / 12, -16 / 12, 5 / 12), 3: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}[len(old_eps)]

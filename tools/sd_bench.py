@@ -15,7 +15,10 @@ torso (ms per pass and per image, median of 5 passes after 2 warm-ups; TFLOP/s a
 peak on the plan's algorithmic FLOPs and on the executed ones, which run the three Downsample convs at stride 1).
 --clip-image times the CLIP ViT-L/14 image tower (`FrozenClipImageEmbedder`, random weights) on 6 and 320 images of 512 x 512 in
 [-1, 1] per torso: ms per call, images/s and model TFLOP/s from the plan's algorithmic FLOPs, median of 5 windows; and the bicubic
-resize entry alone."""
+resize entry alone.
+--prompt-mask "[1,1,1,0,0,0]" times the K-step PLMS loop at the search's 6-latent call with that `prompt_mask` against all ones, and
+--masked the K-step DDIM loop with `mask=, x0=` against the unmasked one and the per-step blend alone: both on a captured hipGraph
+(GRAPH=0: eager), alternating windows of REPS (default 3) batches in one process, median of 5."""
 import os
 import sys
 import time
@@ -258,8 +261,101 @@ def sampler_bench(m):
           f"{2 * n * evals / dt * GFLOP_PER_LATENT / 1e3:.1f} model TFLOP/s ({evals} guided UNet evaluations)")
 
 
+def _alternate(title, variants, n, windows=5):
+    """Times ``variants`` (name -> fn(seed), each one finished batch of n latents) in alternating windows of ``reps`` batches (host
+    clock around a device synchronise), after two warm-up batches each; prints the median window per variant and its ratio to the first."""
+    import statistics
+    reps = int(os.environ.get("REPS", "3"))
+    for fn in variants.values():
+        for w in range(2):
+            out = fn(-1 - w)
+        torch.cuda.synchronize()
+        assert torch.isfinite(out).all()
+    ms = {k: [] for k in variants}
+    for w in range(windows):
+        for k, fn in variants.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for r in range(reps):
+                fn(w * reps + r)
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) / reps * 1e3)
+    base = None
+    for k, v in ms.items():
+        med = statistics.median(v)
+        base = med if base is None else base
+        print(f"{title} {k}: {med:.1f} ms / batch ({min(v):.1f} .. {max(v):.1f} over {windows} windows of {reps}), "
+              f"{n / med * 1e3:.2f} finished latents/s, {med / base:.4f} x the first")
+    return ms
+
+
+def _sd_v1_sampling():
+    from autodiffusion_amd.sd_sampler import LatentDiffusion
+    m = UNetModel(image_size=32, use_spatial_transformer=True, **SD_V1).to(DEV)
+    m.randomize_(1234)
+    if os.environ.get("GRAPH", "1") == "1":
+        m.enable_graph()
+    k, n = int(os.environ.get("K", "6")), int(os.environ.get("N_SAMPLES", "6"))
+    cand = sorted([94, 834, 217, 944, 574, 354, 153, 690, 424, 926][:k])
+    c, uc = torch.randn(n, 77, 768, device=DEV), torch.randn(n, 77, 768, device=DEV)
+
+    def x_T(seed):
+        return torch.randn(n, 4, 64, 64, device=DEV, generator=torch.Generator(device=DEV).manual_seed(seed))
+    return LatentDiffusion(m, device=DEV), k, n, cand, c, uc, x_T
+
+
+def prompt_mask_bench(prompt_mask):
+    """--prompt-mask "[1,1,1,0,0,0]": the PLMS loop at the search's call (K steps, 6 latents, cfg 7.5, hipGraph replay unless GRAPH=0)
+    with the mask against all ones, alternating in one process."""
+    from autodiffusion_amd.sd_sampler import PLMSSampler
+    ld, k, n, cand, c, uc, x_T = _sd_v1_sampling()
+    if len(prompt_mask) != k:
+        raise SystemExit(f"sd_bench.py: --prompt-mask holds {len(prompt_mask)} entries; K is {k}")
+    sampler = PLMSSampler(ld)
+
+    def run(pm):
+        return lambda seed: sampler.sample(S=k, batch_size=n, shape=[4, 64, 64], conditioning=c, verbose=False, eta=0.0, x_T=x_T(seed),
+                                           unconditional_guidance_scale=7.5, unconditional_conditioning=uc, sampled_timestep=cand,
+                                           prompt_mask=pm)[0]
+    points = [prompt_mask[0]] + list(prompt_mask)     # the first step evaluates twice
+    print(f"prompt_mask {prompt_mask}: {sum(2 if p else 1 for p in points)} UNet evaluations of {n} latents against {2 * len(points)}")
+    _alternate(f"SD v1 plms K={k} cfg 7.5, {n} latents/batch, prompt_mask", {"all ones": run([1] * k), str(prompt_mask): run(list(prompt_mask))}, n)
+
+
+def masked_bench():
+    """--masked: K-step DDIM at the search's call, unmasked against masked (half-plane mask; four more launches per step: q_sample,
+    two selects, their sum), alternating in one process; then the four launches alone."""
+    import statistics
+    from autodiffusion_amd.sd_sampler import DDIMSampler, axpby_noise, masked_blend
+    ld, k, n, cand, c, uc, x_T = _sd_v1_sampling()
+    sampler = DDIMSampler(ld)
+    x0 = torch.randn(n, 4, 64, 64, device=DEV) * 0.8
+    mask = torch.zeros(1, 1, 64, 64, device=DEV)
+    mask[..., :32] = 1.0
+
+    def run(masked):
+        kw = dict(mask=mask, x0=x0) if masked else {}
+        return lambda seed: sampler.sample(S=k, batch_size=n, shape=[4, 64, 64], conditioning=c, verbose=False, eta=0.0, x_T=x_T(seed),
+                                           unconditional_guidance_scale=7.5, unconditional_conditioning=uc, sampled_timestep=cand, **kw)[0]
+    _alternate(f"SD v1 ddim K={k} cfg 7.5, {n} latents/batch,", {"unmasked": run(False), "masked": run(True)}, n)
+    keep = mask.expand(n, 4, 64, 64).contiguous()
+    drop = axpby_noise(keep, -1.0, torch.ones_like(keep), 1.0)
+    img = x_T(0)
+    one = lambda: masked_blend(img, ld.q_sample(x0, 500), keep, drop)   # noqa: E731
+    for _ in range(3):
+        one()
+    us = statistics.median(_timed(one, 200) for _ in range(5)) * 1e3
+    print(f"the blend alone ({n} latents of 64x64: q_sample + 2 x adm_vec_act + adm_sd_step, with torch.randn_like): {us:.1f} us per step, "
+          f"{us / 4:.1f} us per launch")
+
+
 if __name__ == "__main__":
-    if "--decode" in sys.argv[1:]:
+    if "--prompt-mask" in sys.argv[1:]:
+        import ast
+        prompt_mask_bench([int(v) for v in ast.literal_eval(sys.argv[sys.argv.index("--prompt-mask") + 1])])
+    elif "--masked" in sys.argv[1:]:
+        masked_bench()
+    elif "--decode" in sys.argv[1:]:
         decode_bench()
     elif "--vae-encode" in sys.argv[1:]:
         vae_encode_bench()
