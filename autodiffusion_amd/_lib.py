@@ -126,6 +126,9 @@ SIGNATURES = {
     "adm_attention_causal": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "adm_quick_gelu": (_I, [_P, _P, C.c_int64, _I, _P]),
     "adm_layernorm_f32out": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    # the stream is second to last here (the integer mode is last): include/adm_hip.h says why
+    "adm_poly3_work_elems": (C.c_int64, [C.c_int64, C.c_int64, _I]),
+    "adm_poly3_sums": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _P, C.c_int64, _P, _P, _I]),
 }
 
 _libs = {}

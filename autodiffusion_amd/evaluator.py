@@ -10,6 +10,8 @@ reference batch -- what the reference's ``evaluations/evaluator.py`` (``main()``
   ``adm_knn_cover``): one fp16 GEMM per call with the k-smallest selection / radius comparison in its epilogue, no N x N
   distance matrix in memory.  The distances are fp32 sums of fp16 products of the fp16-rounded features (the reference
   rounds each distance to fp16 as well: DESIGN.md section 10).
+* KID (``Evaluator.compute_kid``; project-defined, the reference reports none): ``kid.kid_subsets`` on the cubic-kernel sums of
+  csrc/adm_kid.hip.
 """
 from __future__ import annotations
 
@@ -293,6 +295,13 @@ class Evaluator:
         radii_2 = me.manifold_radii(activations_sample)
         pr = me.evaluate_pr(activations_ref, radii_1, activations_sample, radii_2)
         return float(pr[0][0]), float(pr[1][0])
+
+    def compute_kid(self, activations_ref, activations_sample, subsets: int = 100, subset_size: int = 1000,
+                    seed: int = 0) -> Tuple[float, float]:
+        """(mean, std) of the unbiased cubic-kernel MMD^2 over `subsets` draws of `subset_size` rows from each set (kid.py;
+        project-defined: the reference's evaluator has no KID).  A set smaller than `subset_size` raises ValueError."""
+        from .kid import kid_subsets
+        return kid_subsets(_rows(activations_sample).contiguous(), _rows(activations_ref).contiguous(), subsets, subset_size, seed)
 
 
 def random_inception(device, dtype: torch.dtype = torch.float16, classes: int = 1008, seed: int = 0):

@@ -886,3 +886,26 @@ def resize_bilinear(images, oh: int, ow: int, cpad: int, layout: str, half_pixel
     check(lib.adm_resize_bilinear(_ptr(images, want, "images"), _ptr(out), n, h, w, oh, ow, cpad, kind, int(half_pixel),
                                   float(scale), float(shift), _stream()), "adm_resize_bilinear")
     return out
+
+
+# ------------------------------------------------------------------ Kernel Inception Distance
+def poly3_sums(x, y=None, out=None):
+    """float64 device tensor [1]: sum_i sum_j (x_i . y_j / d + 1)^3 over fp32 rows x [n, d], y [m, d]; with y None the sum over the
+    pairs i != j of x alone (adm_poly3_sums: an f64 matrix-core Gram with the cube and the reduction in its epilogue).  The
+    workspace is sized by the library and allocated here; no host synchronisation."""
+    self_pairs = y is None
+    if x.dim() != 2 or (not self_pairs and (y.dim() != 2 or y.shape[1] != x.shape[1])):
+        raise AdmError(f"poly3_sums: expected rows [n, d] and [m, d], got {tuple(x.shape)}" + ("" if self_pairs else f" and {tuple(y.shape)}"))
+    px, py = _ptr(x, torch.float32, "x"), _ptr(y, torch.float32, "y")
+    n, d = x.shape
+    m = n if self_pairs else y.shape[0]
+    lib = _lib.load()
+    elems = lib.adm_poly3_work_elems(n, m, int(self_pairs))
+    if elems < 0:
+        check(-2, "adm_poly3_work_elems")
+    work = torch.empty(elems, dtype=torch.float64, device=x.device)
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=x.device)
+    check(lib.adm_poly3_sums(px, n, py, m, d, _ptr(work), elems, _ptr(out, torch.float64, "out"), _stream(), int(self_pairs)),
+          "adm_poly3_sums")
+    return out

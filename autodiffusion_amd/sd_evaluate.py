@@ -63,7 +63,7 @@ def inception_features(net, dims: int = 2048, allow_random: bool = False):
 class SDCandidateEvaluator:
     def __init__(self, model, sampler, conditioning=None, ref_mu=None, ref_sigma=None, num_samples: int = None, *, prompts=None,
                  features=None, inception=None, dims: int = 2048, allow_random_inception: bool = False, seed: int = 0,
-                 device=None, image_out=None, accumulator=None, clip_scorer=None):
+                 device=None, image_out=None, accumulator=None, clip_scorer=None, fitness: str = "fid", ref_feats=None):
         """model: ``sd_sampler.LatentDiffusion`` with a first stage (``decode_first_stage``); sampler: one of the
         ``sd_sampler`` samplers around it; conditioning: iterable of per-batch ``(c, uc)`` device tensors (``uc`` may be None
         when ``opt.scale == 1``), re-iterated by every call; prompts (instead of conditioning; the model then needs a cond
@@ -74,17 +74,31 @@ class SDCandidateEvaluator:
         clip_scorer (with prompts= only): an ``sd_clip.CLIPScorer`` -- anything with ``cosine(images, prompts) -> [N]`` and
         ``score_of(cosines)``; every batch's clamped [0, 1] images, the ones the extractor sees, are also scored against that batch's
         prompts: ``last_clip`` = {"score", "cosines", "clip_time"} (clip_time: wall time inside the scorer's calls, which are part of
-        sample_time and begin by waiting for the batch's images).  The FID does not change by a bit."""
+        sample_time and begin by waiting for the batch's images).  The FID does not change by a bit.
+        fitness="kid" with ref_feats= (fp32 rows [m, dims], an array or the .npz of scripts/evaluator.py --save_ref_feats): the value
+        returned is ``kid.KIDReference.fitness`` of the candidate's activation rows -- 1000 x the unbiased cubic-kernel MMD^2 -- and the
+        log line says so; ref_mu / ref_sigma are then not needed."""
         if (conditioning is None) == (prompts is None):
             raise ValueError("SDCandidateEvaluator: pass exactly one of conditioning= (precomputed (c, uc) batches) and prompts=")
         if clip_scorer is not None and prompts is None:
             raise ValueError("SDCandidateEvaluator: clip_scorer= scores images against their prompts: pass prompts=, not conditioning=")
         self.clip_scorer, self.last_clip = clip_scorer, None
-        if ref_mu is None or ref_sigma is None or num_samples is None:
+        if fitness not in ("fid", "kid"):
+            raise ValueError(f"SDCandidateEvaluator: fitness {fitness!r}: expected 'fid' or 'kid'")
+        self.fitness, self.kid_ref, self.last_rows = fitness, None, None
+        if fitness == "kid":
+            if ref_feats is None or (isinstance(ref_feats, str) and not ref_feats) or num_samples is None:
+                raise ValueError("SDCandidateEvaluator: fitness='kid' needs ref_feats= (rows or an .npz with `feats`) and num_samples")
+            if isinstance(ref_feats, str):
+                from .kid import load_ref_feats
+                ref_feats = load_ref_feats(ref_feats)
+            self._ref_feats = ref_feats
+        elif ref_mu is None or ref_sigma is None or num_samples is None:
             raise ValueError("SDCandidateEvaluator: ref_mu, ref_sigma and num_samples are required")
         self.model, self.sampler, self.conditioning, self.prompts = model, sampler, conditioning, prompts
         self._uc = {}            # n_samples -> the encoded empty prompt
-        self.ref_stats = FIDStatistics(np.asarray(ref_mu, dtype=np.float64), np.asarray(ref_sigma, dtype=np.float64))
+        self.ref_stats = (FIDStatistics(np.asarray(ref_mu, dtype=np.float64), np.asarray(ref_sigma, dtype=np.float64))
+                          if ref_mu is not None and ref_sigma is not None else None)
         self.num_samples, self.seed, self.dims = int(num_samples), int(seed), int(dims)
         self.device = torch.device(device) if device is not None else getattr(model, "device", torch.device("cpu"))
         if features is None:
@@ -95,7 +109,11 @@ class SDCandidateEvaluator:
         self.fid_note = (" [FID on RANDOM Inception weights: not a quality metric]"
                          if getattr(features, "random_weights", False) else "")
         self._image_out = image_out or (lambda x, out: ops.vae_image_out(x, unit_out=out)[0])
-        self._accumulator = accumulator or (lambda: ActivationAccumulator(self.dims, self.device))
+        if fitness == "kid":
+            self.fid_note += " [fitness: KID x 1e3]"
+        # KID works from the rows themselves: keep every one (the last batch may carry the count past num_samples)
+        keep = (1 << 30) if fitness == "kid" else 0
+        self._accumulator = accumulator or (lambda: ActivationAccumulator(self.dims, self.device, keep_rows=keep))
         self.last_times = None
         self.last_plan = None    # [(batch index, noise seed)] of the last call
 
@@ -173,7 +191,15 @@ class SDCandidateEvaluator:
             torch.cuda.synchronize(self.device)
         sample_time = time.time() - t1
         t1 = time.time()
-        fid = float(acc.statistics(None, local=True).frechet_distance(self.ref_stats))
+        if self.fitness == "kid":
+            from .kid import KIDReference
+            if self.kid_ref is None:
+                self.kid_ref = KIDReference(self._ref_feats, device=self.device)   # uploads the rows and computes S_yy once
+            acc.join()
+            self.last_rows = torch.cat(acc.rows, 0)
+            fid = float(self.kid_ref.fitness(self.last_rows))                      # fid_time: the two kernel sums
+        else:
+            fid = float(acc.statistics(None, local=True).frechet_distance(self.ref_stats))
         logger.log('FID: ' + str(fid) + self.fid_note)
         fid_time = time.time() - t1
         logger.log('sample_time: ' + str(sample_time) + ', fid_time: ' + str(fid_time))

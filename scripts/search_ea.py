@@ -12,7 +12,10 @@ not in this image).  With neither ``--features`` nor ``--inception_path`` the CL
 random-weight features is meaningless; ``--inception_random True`` opts in for throughput runs and tests, and every FID line
 of log.txt is then tagged "FID on RANDOM Inception weights".  ``--features pkg.module:factory``
 swaps in any callable ``factory(device) -> (features, dim)`` with ``features(uint8 NHWC device batch) -> fp32 [B, dim]``.
-``--ref_path`` is an .npz with ``mu``, ``sigma`` (written from the reference's pickled FIDStatistics).  ``--merge_batches`` (default 0 = auto: evaluate.merge_policy, 256 images per pass at 64x64, 128 at 128x128, 64 at 256x256) evaluates that many reference batches per pass over the networks -- bitwise the
+``--ref_path`` is an .npz with ``mu``, ``sigma`` (written from the reference's pickled FIDStatistics).  ``--fitness kid --ref_feats FILE.npz``
+ranks candidates by 1000 x the unbiased cubic-kernel MMD^2 (KID, autodiffusion_amd/kid.py) of their activation rows against the rows ``feats`` of
+FILE.npz (``scripts/evaluator.py --save_ref_feats``) instead of the Frechet distance; every fitness line of log.txt then carries
+"[fitness: KID x 1e3]".  ``--merge_batches`` (default 0 = auto: evaluate.merge_policy, 256 images per pass at 64x64, 128 at 128x128, 64 at 256x256) evaluates that many reference batches per pass over the networks -- bitwise the
 same images (every sub-batch draws from its own generator, and an image's result does not depend on the batch it rides in), with the chip
 filled like the headline batch.  ``--use_graph`` (default ``auto`` = on when the merged pass is at most 256 64x64-equivalents, e.g. the reference's batch 100 x 2) replays each UNet evaluation /
 guidance gradient as a captured hipGraph: bit-identical, and at such batches the eager path is bound by the host's launch rate
@@ -57,6 +60,9 @@ def create_argparser():
     defaults.update(classifier_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
+    parser.add_argument("--fitness", default="fid", choices=["fid", "kid"],
+                        help="what ranks a candidate: the Frechet distance, or 1000 x the unbiased cubic-kernel MMD^2 (autodiffusion_amd/kid.py)")
+    parser.add_argument("--ref_feats", default="", help="--fitness kid: .npz with `feats` fp32 [m, 2048] (scripts/evaluator.py --save_ref_feats)")
     return parser
 
 
@@ -75,6 +81,11 @@ def build_search_space(args, diffusion):
 
 def main(argv=None):
     args = create_argparser().parse_args(argv)
+    if args.fitness == "fid" and not args.ref_feats:
+        # the defaults leave no trace: log.txt's argument line (str(args) below) stays what it was before the two flags existed
+        del args.fitness, args.ref_feats
+    elif args.fitness == "kid" and not args.ref_feats:
+        raise SystemExit("search_ea.py: --fitness kid needs --ref_feats FILE.npz (scripts/evaluator.py --save_ref_feats writes it)")
     # `auto` is decided on the MERGED batch -- the pass that is launched is what a graph captures (the plan of ONE rank taking
     # every batch: this runs before the process group exists)
     per_pass = len(batch_plan(args.num_samples, args.batch_size, 1, 0, args.image_size, args.merge_batches)[0]) * args.batch_size
