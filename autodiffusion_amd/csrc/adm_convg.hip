@@ -499,8 +499,12 @@ extern "C" int adm_conv2d(const adm_conv2d_args* a, void* stream) {
               a->cin_pad, a->in_stride);
   ADM_REQUIRE(a->cout > 0 && a->cout % 4 == 0 && a->out_stride >= a->cout && a->out_stride % 4 == 0, ADM_E_SHAPE,
               "adm_conv2d: cout %d must be a multiple of 4 within the output's channel stride %d", a->cout, a->out_stride);
+  // the window must fit the padded image: tested on the numerator, since C division truncates toward zero and would turn
+  // -stride < h + 2 pad - k < 0 into an output size of 1 where the floor formula of every caller says 0
+  ADM_REQUIRE(a->h + 2 * a->pad_h >= a->kh && a->w_in + 2 * a->pad_w >= a->kw, ADM_E_SHAPE,
+              "adm_conv2d: empty output (the %dx%d window does not fit the padded %dx%d image)", a->kh, a->kw, a->h + 2 * a->pad_h,
+              a->w_in + 2 * a->pad_w);
   const int oh = (a->h + 2 * a->pad_h - a->kh) / a->stride + 1, ow = (a->w_in + 2 * a->pad_w - a->kw) / a->stride + 1;
-  ADM_REQUIRE(oh > 0 && ow > 0, ADM_E_SHAPE, "adm_conv2d: empty output");
   ADM_REQUIRE(adm_aligned16(a->in) && adm_aligned16(a->w) && (((uintptr_t)a->out) & 7u) == 0 && adm_aligned16(a->bias), ADM_E_ALIGN,
               "adm_conv2d: unaligned pointer");
   const long long in_bytes = (long long)a->n * a->h * a->w_in * a->in_stride * 2;
@@ -550,8 +554,10 @@ extern "C" int adm_pool2d(const adm_bf16* in, adm_bf16* out, int n, int h, int w
   ADM_REQUIRE(c > 0 && c % 8 == 0 && in_stride >= c && out_stride >= c && in_stride % 8 == 0 && out_stride % 8 == 0, ADM_E_SHAPE,
               "adm_pool2d: channels %d (strides %d, %d) must be multiples of 8", c, in_stride, out_stride);
   ADM_REQUIRE(adm_aligned16(in) && adm_aligned16(out), ADM_E_ALIGN, "adm_pool2d: unaligned pointer");
+  // as in adm_conv2d: the numerator is tested before the truncating division
+  ADM_REQUIRE(h + 2 * pad >= k && w + 2 * pad >= k, ADM_E_SHAPE,
+              "adm_pool2d: empty output (the %dx%d window does not fit the padded %dx%d image)", k, k, h + 2 * pad, w + 2 * pad);
   const int oh = (h + 2 * pad - k) / stride + 1, ow = (w + 2 * pad - k) / stride + 1;
-  ADM_REQUIRE(oh > 0 && ow > 0, ADM_E_SHAPE, "adm_pool2d: empty output");
   hipLaunchKernelGGL(pool2d_kernel, dim3(grid_for_items((long long)n * oh * ow * (c / 8))), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const uint16_t*>(in), reinterpret_cast<uint16_t*>(out), n, h, w, c, in_stride, out_stride,
                      oh, ow, k, stride, pad, mode);

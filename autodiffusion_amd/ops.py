@@ -835,6 +835,8 @@ def conv2d(x, w_packed, bias, kh: int, kw: int, stride: int = 1, pad=(0, 0), rel
         raise AdmError(f"conv2d: packed weight has {taps} taps, kernel is {kh}x{kw}")
     if x.shape[3] < cin_pad:
         raise AdmError(f"conv2d: the input holds {x.shape[3]} channels, the packed weight reads {cin_pad} (pad the tensor with zeros)")
+    if h + 2 * pad[0] < kh or w + 2 * pad[1] < kw:   # adm_conv2d's own refusal, before a zero-row tensor is built
+        raise AdmError(f"conv2d: empty output (the {kh}x{kw} window does not fit the padded {h + 2 * pad[0]}x{w + 2 * pad[1]} image)")
     oh, ow = (h + 2 * pad[0] - kh) // stride + 1, (w + 2 * pad[1] - kw) // stride + 1
     if out is None:
         out = torch.empty((n, oh, ow, cout), dtype=x.dtype, device=x.device)
@@ -853,6 +855,8 @@ def conv2d(x, w_packed, bias, kh: int, kw: int, stride: int = 1, pad=(0, 0), rel
 def pool2d(x, k: int, stride: int, pad: int, mode: str, out=None):
     """mode "max" (F.max_pool2d) or "avg" (F.avg_pool2d(count_include_pad=False)) over NHWC; out may be a channel slice."""
     n, h, w, c = x.shape
+    if h + 2 * pad < k or w + 2 * pad < k:   # adm_pool2d's own refusal, before a zero-row tensor is built
+        raise AdmError(f"pool2d: empty output (the {k}x{k} window does not fit the padded {h + 2 * pad}x{w + 2 * pad} image)")
     oh, ow = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
     if out is None:
         out = torch.empty((n, oh, ow, c), dtype=x.dtype, device=x.device)

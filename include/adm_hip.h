@@ -378,7 +378,26 @@ int adm_fid_accumulate(const float* acts, double* s1, double* s2, int n, int d, 
  * adm_conv2d: general 2-D convolution, NHWC.  `in` = [n][h][w_in][in_stride] elements of which channels [0, cin_pad) are
  * read (cin_pad % 32 == 0; channels beyond the layer's real cin must hold zeros or meet zero weights); `w` from
  * adm_pack_conv2d_weight = [cout][kh*kw][cin_pad]; `out` = [n][oh][ow][out_stride] of which channels [0, cout) are written
- * -- point it at a channel slice of a concatenated tensor (cout % 4 == 0, 8-byte aligned).  oh = (h + 2 pad_h - kh)/stride + 1. */
+ * -- point it at a channel slice of a concatenated tensor (cout % 4 == 0, 8-byte aligned).
+ *
+ * What adm_conv2d and adm_pool2d take.  What they accept they compute on every output element; anything else is refused with
+ * ADM_E_ARG / ADM_E_SHAPE / ADM_E_ALIGN before any launch, and nothing is written (tests/test_hip_conv2d_envelope.py walks the
+ * tables of tests/conv2d_envelope.py: every kernel pick at 1 .. 196 K-steps, M = n oh ow around the 64 / 128 / 256-pixel tiles,
+ * partial channel tiles, odd geometry and every layout below, and one request per refusal):
+ *   output size     the window must fit the padded image, h + 2 pad_h >= kh and w + 2 pad_w >= kw (pool: pad and k on both axes);
+ *                   then oh = floor((h + 2 pad_h - kh) / stride) + 1 >= 1, likewise ow.  A window that does not fit is
+ *                   ADM_E_SHAPE at every stride: no division is taken of a negative numerator
+ *   adm_conv2d      accepted: n, h, w_in, kh, kw, stride >= 1 and pad_h, pad_w >= 0, in any combination -- windows larger than the
+ *                   image, pads beyond the window, strides that do not divide the map; cin_pad a multiple of 32 with
+ *                   in_stride >= cin_pad a multiple of 8 (channels cin_pad .. in_stride are never read, `in` may be a channel
+ *                   slice at a multiple of 8 channels); cout a multiple of 4 with out_stride >= cout a multiple of 4; bias or
+ *                   none; operands below 2 GiB.  Refused: anything else (ADM_E_ARG: null in / w / out, a size or stride < 1, a
+ *                   negative pad; ADM_E_SHAPE: the channel rules, the output size, the 2 GiB limit; ADM_E_ALIGN: in, w or bias
+ *                   off 16 bytes, out off 8)
+ *   adm_pool2d      accepted: n, h, w, k, stride >= 1, 0 <= pad < k (so every window holds a tap inside the image, also at pads
+ *                   torch refuses), mode 0 / 1, c a multiple of 8 within in_stride and out_stride, multiples of 8.  Refused:
+ *                   anything else (ADM_E_ARG: null pointers, sizes, pad >= k, another mode; ADM_E_SHAPE: the channel rules, the
+ *                   output size; ADM_E_ALIGN: in or out off 16 bytes)                                                            */
 typedef struct adm_conv2d_args {
   const adm_bf16* in; const adm_bf16* w; const float* bias; adm_bf16* out;
   int32_t n, h, w_in, cin_pad, in_stride, cout, out_stride, kh, kw, stride, pad_h, pad_w;

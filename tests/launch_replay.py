@@ -244,7 +244,9 @@ SYMBOL_COVERAGE = {
     "adm_pack_u8_nhwc": _e("tests/test_hip_f32_kernels.py::test_pack_u8_bitwise"),
     "adm_sd_step": _e("tests/test_hip_f32_kernels.py::test_sd_step_every_operand_subset"),
     "adm_dpm_step": _e("tests/test_hip_f32_kernels.py::test_dpm_step_every_operand_subset"),
-    # evaluation side
+    # evaluation side (the shapes the extractor launches are held by the tests named here; adm_conv2d, adm_pool2d,
+    # adm_global_avgpool_f32 and adm_resize_bilinear at the shapes no model launches, and their refusals, besides by
+    # tests/test_hip_conv2d_envelope.py::test_conv2d_envelope)
     "adm_pool2d": _e("tests/test_hip_inception_replay.py::test_pool_launches_match_float64"),
     "adm_global_avgpool_f32": _e("tests/test_hip_inception_replay.py::test_global_avgpool_launches_match_float64"),
     "adm_resize_bilinear": _e("tests/test_hip_inception_replay.py::test_resize_launches_match_float64"),
