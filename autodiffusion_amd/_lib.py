@@ -59,6 +59,14 @@ class SdStepCoefs(C.Structure):
                 ("sqrt_a_prev", C.c_float), ("dir_coef", C.c_float), ("sigma", C.c_float)]
 
 
+class PixDpmArgs(C.Structure):
+    """struct adm_pix_dpm_args (include/adm_hip.h)."""
+    _fields_ = ([(k, C.c_void_p) for k in ("x_eval", "model_out", "grad", "x_base", "h1", "h2", "m_out", "x_next", "u8_nhwc", "s_out",
+                                           "work")] + [("work_bytes", C.c_int64)]
+                + [(k, C.c_int32) for k in ("n", "c", "h", "w", "model_channels", "start_x", "predict_x0", "thresholding")]
+                + [(k, C.c_float) for k in ("alpha_s", "sigma_s", "a", "b0", "b1", "b2", "q", "max_val")])
+
+
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 
 # name -> (restype, argtypes); every symbol declared in include/adm_hip.h
@@ -129,6 +137,10 @@ SIGNATURES = {
     # the stream is second to last here (the integer mode is last): include/adm_hip.h says why
     "adm_poly3_work_elems": (C.c_int64, [C.c_int64, C.c_int64, _I]),
     "adm_poly3_sums": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _P, C.c_int64, _P, _P, _I]),
+    # likewise: stream second to last, `flags` last
+    "adm_abs_quantile_work_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "adm_abs_quantile": (_I, [_P, C.c_int64, C.c_int64, _F, _P, C.c_int64, _P, _P, _I]),
+    "adm_pix_dpm_step": (_I, [C.POINTER(PixDpmArgs), _P, _I]),
 }
 
 _libs = {}

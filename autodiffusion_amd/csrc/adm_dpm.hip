@@ -1,0 +1,325 @@
+// K17: DPM-Solver / DPM-Solver++ on the pixel (ADM) path: the fused multistep update with classifier guidance and Imagen's
+// dynamic thresholding (reference ldm/models/diffusion/dpm_solver/dpm_solver.py: model_wrapper :289-335, data_prediction_fn
+// :386-399, the multistep updates :504-549, :755-857).
+//
+// Two kernels.
+//   * dpm_step_kernel: one thread owns VEC consecutive pixels of one image and walks the C channels, as step_kernel does
+//     (adm_sampler.hip).  eps (the first C of C or 2C model channels, or derived from a START_X output), the guidance term,
+//     the model value m (eps, or x0 = (x - sigma eps) / alpha, thresholded), x_next = a x_base + b0 m + b1 h1 + b2 h2 with
+//     host-computed coefficients, and the uint8 NHWC pack of the final image.  Every multistep update of orders 1-3 of
+//     either prediction type is such a linear combination (autodiffusion_amd/dpm_solver.py expands D1 / D2 in float64).
+//   * select_kernel: the exact per-image q-quantile of |v| -- torch.quantile(v.abs().reshape(n, -1), q, dim=1), 'linear'.
+//     One workgroup of 1024 threads per image, radix selection over the uint32 bit patterns of |v| (monotone for the
+//     non-negative floats; the sign bit is cleared, so -0 is 0): three passes over 11 + 10 + 10 key bits, each a histogram
+//     in LDS built with integer atomics (counts do not depend on arrival order) followed by a prefix walk that keeps the
+//     bin holding the wanted rank.  Both order statistics the interpolation needs (floor and ceil of the rank) are carried
+//     through the same three passes, each with its own histogram once their prefixes part.  The keys are produced once, in
+//     pass 0 -- from v, or in the fused form from (x, model_out, grad) with dpm_model_value(), the very function the step
+//     kernel calls, so both launches see the same bits -- and stashed where the later passes re-read them: in LDS for an
+//     image of up to QCAP = 12288 elements (3 x 64 x 64), else in the caller's work buffer.  A thread re-reads only what it
+//     stashed itself: no fence is needed.  No float atomics, no host synchronisation, no device-to-host copy: both launches
+//     can be captured in a hipGraph.
+//     Why one workgroup per image and not several: parts of an image in different workgroups must meet between passes,
+//     which is either a launch per pass with global histograms (9 small launches per thresholded step at three passes) or
+//     a grid-wide wait inside one launch, which hangs when the grid is not co-resident.  One workgroup needs neither, is
+//     independent of the batch around it (an image's s is bitwise the same alone and inside a merged batch), and its cost
+//     is small beside the networks of the step it belongs to (tools/dpm_bench.py prints the share).
+// NaN: |NaN| has a key above +inf's, so NaNs take the top ranks; a quantile that lands on one is NaN.  Where both order
+// statistics are the same element value the result is that value (torch's lerp answers NaN for inf - inf there).
+#include "adm_common.h"
+
+namespace {
+
+constexpr int QT = 1024;       // threads of a selection workgroup
+constexpr int QCAP = 12288;    // largest image whose keys stay in LDS (48 KiB)
+constexpr int QBINS = 2048;    // 11-bit digits in pass 0, 10-bit in passes 1 and 2
+
+struct DpmK {
+  float alpha, sigma, a, b0, b1, b2, max_val;
+  int start_x, predict_x0, thresholding, mo_c;
+};
+
+// the model value of one element, in the reference's order of operations
+__device__ __forceinline__ float dpm_model_value(float xv, float ov, float gv, bool has_grad, const DpmK& k) {
+#pragma clang fp contract(off)
+  float eps = ov;
+  if (k.start_x) eps = (xv - k.alpha * ov) / k.sigma;   // model_wrapper :302
+  if (has_grad) eps = eps - k.sigma * gv;               // :333-335 (grad already carries the classifier scale)
+  if (!k.predict_x0) return eps;
+  return (xv - k.sigma * eps) / k.alpha;                // data_prediction_fn :393
+}
+
+template <int VEC>
+__global__ void __launch_bounds__(256)
+dpm_step_kernel(const float* __restrict__ x, const float* __restrict__ mo, const float* __restrict__ grad,
+                const float* __restrict__ xb, const float* __restrict__ h1, const float* __restrict__ h2,
+                const float* __restrict__ s_in, float* __restrict__ m_out, float* __restrict__ x_next,
+                uint8_t* __restrict__ u8, int n, int c, int hw, DpmK k) {
+#pragma clang fp contract(off)
+  const long long groups = (long long)n * (hw / VEC);
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups;
+       g += (long long)gridDim.x * blockDim.x) {
+    const int img = (int)(g / (hw / VEC));
+    const int p = (int)(g % (hw / VEC)) * VEC;
+    const float s = k.thresholding ? s_in[img] : 1.0f;
+    for (int ch = 0; ch < c; ++ch) {
+      const long long xi = ((long long)img * c + ch) * hw + p;
+      const long long mi = ((long long)img * k.mo_c + ch) * hw + p;
+      float xv[VEC], ov[VEC], gv[VEC], bv[VEC], h1v[VEC], h2v[VEC], mv[VEC], outv[VEC];
+      if constexpr (VEC == 4) {
+        *reinterpret_cast<float4*>(xv) = *reinterpret_cast<const float4*>(x + xi);
+        *reinterpret_cast<float4*>(ov) = *reinterpret_cast<const float4*>(mo + mi);
+        if (grad) *reinterpret_cast<float4*>(gv) = *reinterpret_cast<const float4*>(grad + xi);
+        if (x_next) {
+          *reinterpret_cast<float4*>(bv) = *reinterpret_cast<const float4*>(xb + xi);
+          if (h1) *reinterpret_cast<float4*>(h1v) = *reinterpret_cast<const float4*>(h1 + xi);
+          if (h2) *reinterpret_cast<float4*>(h2v) = *reinterpret_cast<const float4*>(h2 + xi);
+        }
+      } else {
+        xv[0] = x[xi];
+        ov[0] = mo[mi];
+        if (grad) gv[0] = grad[xi];
+        if (x_next) {
+          bv[0] = xb[xi];
+          if (h1) h1v[0] = h1[xi];
+          if (h2) h2v[0] = h2[xi];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        float m = dpm_model_value(xv[j], ov[j], grad ? gv[j] : 0.0f, grad != nullptr, k);
+        if (k.thresholding) m = fminf(fmaxf(m, -s), s) / s;   // :398
+        mv[j] = m;
+        float o = m;
+        if (x_next) {
+          o = k.a * bv[j] + k.b0 * m;
+          if (h1) o = o + k.b1 * h1v[j];
+          if (h2) o = o + k.b2 * h2v[j];
+        }
+        outv[j] = o;
+      }
+      if constexpr (VEC == 4) {
+        *reinterpret_cast<float4*>(m_out + xi) = *reinterpret_cast<float4*>(mv);
+        if (x_next) *reinterpret_cast<float4*>(x_next + xi) = *reinterpret_cast<float4*>(outv);
+      } else {
+        m_out[xi] = mv[0];
+        if (x_next) x_next[xi] = outv[0];
+      }
+      if (u8) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          float q = (outv[j] + 1.0f) * 127.5f;
+          q = fminf(fmaxf(q, 0.0f), 255.0f);
+          u8[((long long)img * hw + p + j) * c + ch] = (uint8_t)q;  // truncation, as .to(uint8)
+        }
+      }
+    }
+  }
+}
+
+// the bin of `hist` that holds rank r (0-based, r < the histogram's total), by one wave: lane l sums bins 32 l .. 32 l + 31,
+// an inclusive scan over the lanes finds the lane, which walks its own bins.  -> sel[0] = bin, sel[1] = r - (count below the bin)
+__device__ __forceinline__ void find_bin(const uint32_t* hist, uint32_t r, int lane, uint32_t* sel) {
+  constexpr int PER_LANE = QBINS / 64;
+  uint32_t mine = 0;
+  for (int i = 0; i < PER_LANE; ++i) mine += hist[lane * PER_LANE + i];
+  uint32_t inc = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t up = __shfl_up(inc, off);
+    if (lane >= off) inc += up;
+  }
+  const uint32_t below = inc - mine;
+  if (r >= below && r < inc) {   // exactly one lane
+    uint32_t acc = below;
+    for (int i = 0; i < PER_LANE; ++i) {
+      const uint32_t h = hist[lane * PER_LANE + i];
+      if (r < acc + h) {
+        sel[0] = (uint32_t)(lane * PER_LANE + i);
+        sel[1] = r - acc;
+        break;
+      }
+      acc += h;
+    }
+  }
+}
+
+// FUSED: keys are |x0| of (x, mo, grad); else |v|.  One block per image.
+template <bool FUSED>
+__global__ void __launch_bounds__(QT)
+select_kernel(const float* __restrict__ v, const float* __restrict__ x, const float* __restrict__ mo,
+              const float* __restrict__ grad, uint32_t* __restrict__ stash, int per, int mo_per, uint32_t k_lo,
+              uint32_t k_hi, float w, DpmK k, float* __restrict__ out0, float* __restrict__ out1) {
+#pragma clang fp contract(off)
+  __shared__ uint32_t keys[QCAP];
+  __shared__ uint32_t hist[2][QBINS];
+  __shared__ uint32_t sel[2][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long img = blockIdx.x;
+  const bool in_lds = per <= QCAP;
+  uint32_t* gstash = in_lds ? nullptr : stash + img * (long long)per;
+  uint32_t prefix[2] = {0u, 0u};      // the key bits decided so far, right-aligned
+  uint32_t rank[2] = {k_lo, k_hi};    // rank among the keys that share the prefix
+  for (int pass = 0; pass < 3; ++pass) {
+    for (int i = tid; i < 2 * QBINS; i += QT) (&hist[0][0])[i] = 0u;
+    __syncthreads();
+    const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0);
+    const uint32_t mask = pass == 0 ? 0x7ffu : 0x3ffu;
+    const bool same = prefix[0] == prefix[1];
+    for (int e = tid; e < per; e += QT) {
+      uint32_t key;
+      if (pass == 0) {
+        float val;
+        if constexpr (FUSED) {
+          const long long xi = img * per + e, mi = img * (long long)mo_per + e;
+          val = dpm_model_value(x[xi], mo[mi], grad ? grad[xi] : 0.0f, grad != nullptr, k);
+        } else {
+          val = v[img * per + e];
+        }
+        key = __float_as_uint(val) & 0x7fffffffu;
+        if (in_lds) keys[e] = key;
+        else gstash[e] = key;
+      } else {
+        key = in_lds ? keys[e] : gstash[e];
+      }
+      const uint32_t hi = pass == 0 ? 0u : key >> (shift + 10);
+      const uint32_t digit = (key >> shift) & mask;
+      if (hi == prefix[0]) atomicAdd(&hist[0][digit], 1u);
+      if (!same && hi == prefix[1]) atomicAdd(&hist[1][digit], 1u);
+    }
+    __syncthreads();
+    if (wave < 2) find_bin(hist[same ? 0 : wave], rank[wave], lane, sel[wave]);
+    __syncthreads();
+    const int bits = pass == 0 ? 11 : 10;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      prefix[r] = (prefix[r] << bits) | sel[r][0];
+      rank[r] = sel[r][1];
+    }
+    __syncthreads();   // sel and hist are rewritten by the next pass
+  }
+  if (tid == 0) {
+    const float lo = __uint_as_float(prefix[0]), hi = __uint_as_float(prefix[1]);
+    float res = lo;
+    if (prefix[0] != prefix[1]) {   // torch's lerp (aten/src/ATen/native/Lerp.h)
+      const float diff = hi - lo;
+      res = w < 0.5f ? lo + w * diff : hi - diff * (1.0f - w);
+    }
+    if constexpr (FUSED) res = fmaxf(res, k.max_val);   // :397
+    out0[img] = res;
+    if (out1) out1[img] = res;
+  }
+}
+
+// sizes: per = c h w as int, every tensor's element count inside int64
+bool dpm_sizes(long long n, long long per, long long* total) {
+  if (n < 1 || per < 1 || n > 0x7fffffffLL || per > 0x7fffffffLL) return false;
+  long long t;
+  if (__builtin_mul_overflow(n, per, &t) || t > (1LL << 60)) return false;
+  *total = t;
+  return true;
+}
+
+long long work_bytes(long long n, long long per) {
+  long long total;
+  if (!dpm_sizes(n, per, &total)) return -1;
+  const long long s_bytes = (n * 4 + 15) / 16 * 16;   // the per-image s of the thresholded step
+  return s_bytes + (per > QCAP ? total * 4 : 0);
+}
+
+void rank_of(float q, long long per, uint32_t* k_lo, uint32_t* k_hi, float* w) {
+  // torch.quantile on a float32 input: q as float32 times (per - 1), in float32 (aten/src/ATen/native/Sorting.cpp)
+  const float pos = q * (float)(per - 1);
+  const float fl = floorf(pos), ce = ceilf(pos);
+  *k_lo = (uint32_t)fl;
+  *k_hi = (uint32_t)ce;
+  *w = pos - fl;
+}
+
+}  // namespace
+
+extern "C" int64_t adm_abs_quantile_work_bytes(int64_t n, int64_t per) {
+  const long long b = work_bytes(n, per);
+  if (b < 0) adm_set_error("adm_abs_quantile_work_bytes: unsupported shape n=%lld per=%lld", (long long)n, (long long)per);
+  return b;
+}
+
+extern "C" int adm_abs_quantile(const float* v, int64_t n, int64_t per, float q, void* work, int64_t work_bytes_given,
+                                float* out, void* stream, int flags) {
+  ADM_REQUIRE(flags == 0, ADM_E_ARG, "adm_abs_quantile: flags=%d (must be 0)", flags);
+  ADM_REQUIRE(v && work && out, ADM_E_ARG, "adm_abs_quantile: null pointer");
+  ADM_REQUIRE(q > 0.0f && q < 1.0f, ADM_E_ARG, "adm_abs_quantile: q=%g is outside (0, 1)", (double)q);
+  const long long need = work_bytes(n, per);
+  ADM_REQUIRE(need >= 0, ADM_E_ARG, "adm_abs_quantile: sizes n=%lld per=%lld are not supported (overflow)", (long long)n, (long long)per);
+  ADM_REQUIRE(work_bytes_given >= need, ADM_E_ARG, "adm_abs_quantile: work holds %lld bytes, adm_abs_quantile_work_bytes says %lld",
+              (long long)work_bytes_given, need);
+  ADM_REQUIRE(adm_aligned16(work), ADM_E_ALIGN, "adm_abs_quantile: work must be 16-byte aligned");
+  uint32_t k_lo, k_hi;
+  float w;
+  rank_of(q, per, &k_lo, &k_hi, &w);
+  uint32_t* stash = reinterpret_cast<uint32_t*>(static_cast<char*>(work) + (n * 4 + 15) / 16 * 16);
+  hipLaunchKernelGGL((select_kernel<false>), dim3((unsigned)n), dim3(QT), 0, (hipStream_t)stream, v, (const float*)nullptr,
+                     (const float*)nullptr, (const float*)nullptr, stash, (int)per, 0, k_lo, k_hi, w, DpmK{}, out, (float*)nullptr);
+  return adm_check_launch("adm_abs_quantile");
+}
+
+extern "C" int adm_pix_dpm_step(const adm_pix_dpm_args* a, void* stream, int flags) {
+  ADM_REQUIRE(flags == 0, ADM_E_ARG, "adm_pix_dpm_step: flags=%d (must be 0)", flags);
+  ADM_REQUIRE(a, ADM_E_ARG, "adm_pix_dpm_step: null argument block");
+  ADM_REQUIRE(a->x_eval && a->model_out && a->m_out, ADM_E_ARG, "adm_pix_dpm_step: null x_eval / model_out / m_out");
+  ADM_REQUIRE(!a->x_next || a->x_base, ADM_E_ARG, "adm_pix_dpm_step: x_next without x_base");
+  ADM_REQUIRE(a->n > 0 && a->c > 0 && a->h > 0 && a->w > 0, ADM_E_ARG, "adm_pix_dpm_step: bad shape %d %d %d %d", a->n, a->c, a->h, a->w);
+  ADM_REQUIRE(a->model_channels == a->c || a->model_channels == 2LL * a->c, ADM_E_ARG,
+              "adm_pix_dpm_step: model_out has %d channels, neither C = %d nor 2C", a->model_channels, a->c);
+  ADM_REQUIRE(!a->thresholding || a->predict_x0, ADM_E_ARG, "adm_pix_dpm_step: thresholding needs predict_x0");
+  long long hw, per, mo_per, total;
+  ADM_REQUIRE(!__builtin_mul_overflow((long long)a->h, (long long)a->w, &hw) && hw <= 0x7fffffffLL &&
+                  !__builtin_mul_overflow(hw, (long long)a->model_channels, &mo_per) && mo_per <= 0x7fffffffLL &&
+                  dpm_sizes(a->n, mo_per, &total),
+              ADM_E_ARG, "adm_pix_dpm_step: the sizes %d x %d x %d x %d overflow", a->n, a->model_channels, a->h, a->w);
+  per = hw * a->c;
+  float* s_work = nullptr;
+  uint32_t k_lo = 0, k_hi = 0;
+  float wq = 0.0f;
+  if (a->thresholding) {
+    ADM_REQUIRE(a->q > 0.0f && a->q < 1.0f, ADM_E_ARG, "adm_pix_dpm_step: q=%g is outside (0, 1)", (double)a->q);
+    ADM_REQUIRE(a->max_val > 0.0f, ADM_E_ARG, "adm_pix_dpm_step: max_val=%g must be positive", (double)a->max_val);
+    const long long need = work_bytes(a->n, per);
+    ADM_REQUIRE(a->work, ADM_E_ARG, "adm_pix_dpm_step: thresholding needs a work buffer");
+    ADM_REQUIRE(a->work_bytes >= need, ADM_E_ARG, "adm_pix_dpm_step: work holds %lld bytes, adm_abs_quantile_work_bytes says %lld",
+                (long long)a->work_bytes, need);
+    ADM_REQUIRE(adm_aligned16(a->work), ADM_E_ALIGN, "adm_pix_dpm_step: work must be 16-byte aligned");
+    s_work = static_cast<float*>(a->work);
+    rank_of(a->q, per, &k_lo, &k_hi, &wq);
+  }
+  DpmK k{};
+  k.alpha = a->alpha_s;
+  k.sigma = a->sigma_s;
+  k.a = a->a;
+  k.b0 = a->b0;
+  k.b1 = a->b1;
+  k.b2 = a->b2;
+  k.max_val = a->max_val;
+  k.start_x = a->start_x != 0;
+  k.predict_x0 = a->predict_x0 != 0;
+  k.thresholding = a->thresholding != 0;
+  k.mo_c = a->model_channels;
+  hipStream_t s = (hipStream_t)stream;
+  if (a->thresholding) {
+    uint32_t* stash = reinterpret_cast<uint32_t*>(static_cast<char*>(a->work) + ((long long)a->n * 4 + 15) / 16 * 16);
+    hipLaunchKernelGGL((select_kernel<true>), dim3((unsigned)a->n), dim3(QT), 0, s, (const float*)nullptr, a->x_eval, a->model_out,
+                       a->grad, stash, (int)per, (int)mo_per, k_lo, k_hi, wq, k, s_work, a->s_out);
+  }
+  const bool vec4 = (hw % 4 == 0) && adm_aligned16(a->x_eval) && adm_aligned16(a->model_out) && adm_aligned16(a->m_out) &&
+                    (!a->grad || adm_aligned16(a->grad)) &&
+                    (!a->x_next || (adm_aligned16(a->x_next) && adm_aligned16(a->x_base) && (!a->h1 || adm_aligned16(a->h1)) &&
+                                    (!a->h2 || adm_aligned16(a->h2))));
+  const long long groups = (long long)a->n * (vec4 ? hw / 4 : hw);
+  int blocks = (int)((groups + 255) / 256 > 4096 ? 4096 : (groups + 255) / 256);
+#define LAUNCH(V)                                                                                                            \
+  hipLaunchKernelGGL((dpm_step_kernel<V>), dim3(blocks), dim3(256), 0, s, a->x_eval, a->model_out, a->grad, a->x_base, a->h1, \
+                     a->h2, (const float*)s_work, a->m_out, a->x_next, a->u8_nhwc, a->n, a->c, (int)hw, k)
+  if (vec4) LAUNCH(4); else LAUNCH(1);
+#undef LAUNCH
+  return adm_check_launch("adm_pix_dpm_step");
+}

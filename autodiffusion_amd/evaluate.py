@@ -124,7 +124,13 @@ def parse_index_step(value, flag: str = "--index_step"):
 class CandidateEvaluator:
     def __init__(self, model, base_diffusion, classifier=None, *, image_size: int, use_ddim: bool = True,
                  clip_denoised: bool = True, class_cond: bool = True, classifier_scale: float = 1.0,
-                 device=None, use_graph: bool = False):
+                 device=None, use_graph: bool = False, sampler: Optional[str] = None, dpm_order: int = 2,
+                 dpm_predict_x0: bool = True, dpm_thresholding: bool = False):
+        if sampler not in (None, "dpm_solver"):
+            raise ValueError(f"sampler={sampler!r}: None (use_ddim decides between DDIM and ancestral sampling) or 'dpm_solver'")
+        # sampler="dpm_solver": the candidate's K timesteps are K evaluations of multistep DPM-Solver (dpm_solver.py), not of DDIM
+        self.sampler, self.dpm_order = sampler, int(dpm_order)
+        self.dpm_predict_x0, self.dpm_thresholding = bool(dpm_predict_x0), bool(dpm_thresholding)
         self.model = model
         self.classifier = classifier
         self.base_diffusion = base_diffusion
@@ -186,10 +192,20 @@ class CandidateEvaluator:
         kwargs = {"y": classes}
         if self.skip_layers is not None:
             kwargs["skip_layers"] = self.skip_layers
+        cond_fn = self._cond_fn if self.classifier is not None else None
+        if getattr(self, "sampler", None) == "dpm_solver":
+            # the networks see the candidate's own integer timesteps, so _model_fn's skip-list lookup works as under DDIM; the
+            # solver draws no per-step noise
+            from .dpm_solver import DPMSolver
+            solver = DPMSolver(self.base_diffusion, predict_x0=self.dpm_predict_x0, thresholding=self.dpm_thresholding)
+            sample = solver.sample_candidate(self._model_fn, tuple(x_T.shape), noise=x_T, cond_fn=cond_fn, model_kwargs=kwargs,
+                                             device=dev, indices=d.timestep_map, order=self.dpm_order)
+            self.last_classes = classes
+            return solver.last_uint8_nhwc, sample
         fn = d.ddim_sample_loop if self.use_ddim else d.p_sample_loop
         try:
             sample = fn(self._model_fn, tuple(x_T.shape), noise=x_T, clip_denoised=self.clip_denoised, model_kwargs=kwargs,
-                        cond_fn=self._cond_fn if self.classifier is not None else None, device=dev)
+                        cond_fn=cond_fn, device=dev)
         finally:
             d.generator = None    # a later direct call of the diffusion object must not draw from this pass's generators
         self.last_classes = classes

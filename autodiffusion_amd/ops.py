@@ -913,3 +913,55 @@ def poly3_sums(x, y=None, out=None):
     check(lib.adm_poly3_sums(px, n, py, m, d, _ptr(work), elems, _ptr(out, torch.float64, "out"), _stream(), int(self_pairs)),
           "adm_poly3_sums")
     return out
+
+
+# ------------------------------------------------------------------ DPM-Solver on the pixel path
+def abs_quantile_work(n: int, per: int, device):
+    """The work buffer adm_abs_quantile / a thresholded adm_pix_dpm_step wants for n images of `per` elements."""
+    nbytes = _lib.load().adm_abs_quantile_work_bytes(n, per)
+    if nbytes < 0:
+        check(-1, "adm_abs_quantile_work_bytes")
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+def abs_quantile(v, q: float, work=None):
+    """torch.quantile(v.abs(), q, dim=1) of fp32 rows v [n, per], exactly (radix selection; no host synchronisation)."""
+    if v.dim() != 2:
+        raise AdmError(f"abs_quantile: expected rows [n, per], got {tuple(v.shape)}")
+    n, per = v.shape
+    if work is None:
+        work = abs_quantile_work(n, per, v.device)
+    out = torch.empty(n, dtype=torch.float32, device=v.device)
+    check(_lib.load().adm_abs_quantile(_ptr(v, torch.float32, "v"), n, per, float(q), _ptr(work), work.numel(), _ptr(out),
+                                       _stream(), 0), "adm_abs_quantile")
+    return out
+
+
+def pix_dpm_step(x_eval, model_out, grad, x_base, h1, h2, *, alpha_s, sigma_s, a=0.0, b0=0.0, b1=0.0, b2=0.0, start_x=False,
+                 predict_x0=True, thresholding=False, q=0.995, max_val=1.0, want_next=True, want_u8=False, want_s=False,
+                 work=None):
+    """One model evaluation of the pixel-space DPM-Solver (adm_pix_dpm_step).  -> (m, x_next | None, uint8 NHWC | None, s | None)"""
+    n, c, h, w = x_eval.shape
+    if model_out.dim() != 4 or model_out.shape[0] != n or tuple(model_out.shape[2:]) != (h, w):
+        raise AdmError(f"pix_dpm_step: model_out shape {tuple(model_out.shape)} does not belong to x {tuple(x_eval.shape)}")
+    for name, t in (("grad", grad), ("x_base", x_base), ("h1", h1), ("h2", h2)):
+        if t is not None and tuple(t.shape) != (n, c, h, w):
+            raise AdmError(f"pix_dpm_step: {name} shape {tuple(t.shape)} != {(n, c, h, w)}")
+    g = _lib.PixDpmArgs()
+    g.x_eval, g.model_out = _ptr(x_eval, torch.float32, "x_eval"), _ptr(model_out, torch.float32, "model_out")
+    g.grad, g.x_base = _ptr(grad, torch.float32, "grad"), _ptr(x_base, torch.float32, "x_base")
+    g.h1, g.h2 = _ptr(h1, torch.float32, "h1"), _ptr(h2, torch.float32, "h2")
+    m = torch.empty_like(x_eval)
+    x_next = torch.empty_like(x_eval) if want_next else None
+    u8 = torch.empty((n, h, w, c), dtype=torch.uint8, device=x_eval.device) if want_u8 else None
+    s = torch.empty(n, dtype=torch.float32, device=x_eval.device) if (want_s and thresholding) else None
+    if thresholding and work is None:
+        work = abs_quantile_work(n, c * h * w, x_eval.device)
+    g.m_out, g.x_next, g.u8_nhwc, g.s_out = _ptr(m), _ptr(x_next), _ptr(u8), _ptr(s)
+    g.work, g.work_bytes = (_ptr(work), work.numel()) if work is not None else (None, 0)
+    g.n, g.c, g.h, g.w, g.model_channels = n, c, h, w, model_out.shape[1]
+    g.start_x, g.predict_x0, g.thresholding = int(start_x), int(predict_x0), int(thresholding)
+    g.alpha_s, g.sigma_s, g.a, g.b0, g.b1, g.b2, g.q, g.max_val = (float(alpha_s), float(sigma_s), float(a), float(b0), float(b1),
+                                                                  float(b2), float(q), float(max_val))
+    check(_lib.load().adm_pix_dpm_step(C.byref(g), _stream(), 0), "adm_pix_dpm_step")
+    return m, x_next, u8, s

@@ -147,18 +147,9 @@ class SpacedDiffusion:
             new_ts = new_ts.float() * (1000.0 / self.original_num_steps)
         return new_ts
 
-    def _step(self, kind, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
-              want_u8=False, index=None):
-        if model_kwargs is None:
-            model_kwargs = {}
-        if index is None:  # direct p_sample / ddim_sample calls: read the index back from the tensor
-            idx = t.tolist()
-            if len(set(idx)) != 1:
-                raise NotImplementedError("per-sample step indices: the sample loops always pass one index per batch")
-            index = int(idx[0])
-        i = index
-        ts = self._mapped(t)
-        x = x.contiguous()
+    def _eval_networks(self, model, x, ts, cond_fn, model_kwargs):
+        """eps(x_t) and, with cond_fn, the guidance gradient at x (contiguous) and the mapped timesteps ts -> (fp32 model_out, fp32
+        grad | None).  Both depend on x_t only: on a GPU they run on two HIP streams (bit-identical to the sequential order)."""
         grad = None
         if cond_fn is not None and self.overlap_guidance and x.is_cuda and self.cu_partition_spec:
             # the two networks on disjoint sets of CUs (cu_partition): both depend on x_t only
@@ -197,6 +188,21 @@ class SpacedDiffusion:
                 grad = cond_fn(x, ts, **model_kwargs).float().contiguous()
         if model_out.dtype != torch.float32:
             model_out = model_out.float()
+        return model_out, grad
+
+    def _step(self, kind, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
+              want_u8=False, index=None):
+        if model_kwargs is None:
+            model_kwargs = {}
+        if index is None:  # direct p_sample / ddim_sample calls: read the index back from the tensor
+            idx = t.tolist()
+            if len(set(idx)) != 1:
+                raise NotImplementedError("per-sample step indices: the sample loops always pass one index per batch")
+            index = int(idx[0])
+        i = index
+        ts = self._mapped(t)
+        x = x.contiguous()
+        model_out, grad = self._eval_networks(model, x, ts, cond_fn, model_kwargs)
         # drawn every step, as the reference does (keeps the RNG stream aligned with it)
         if isinstance(self.generator, (list, tuple)):
             # several reference batches evaluated in one pass (CandidateEvaluator.sample_batches): [(generator, images), ...] --

@@ -237,3 +237,27 @@ def str2bool(v):
     if v.lower() in ("no", "false", "f", "n", "0"):
         return False
     raise argparse.ArgumentTypeError("boolean value expected")
+
+
+DPM_FLAGS = ("dpm_solver", "dpm_order", "dpm_predict_x0", "dpm_thresholding")
+
+
+def add_dpm_flags(parser):
+    """--dpm_solver True: a candidate's K timesteps are K evaluations of multistep DPM-Solver (autodiffusion_amd/dpm_solver.py)
+    instead of DDIM / ancestral steps."""
+    parser.add_argument("--dpm_solver", type=str2bool, default=False)
+    parser.add_argument("--dpm_order", type=int, default=2, choices=[1, 2, 3])
+    parser.add_argument("--dpm_predict_x0", type=str2bool, default=True)
+    parser.add_argument("--dpm_thresholding", type=str2bool, default=False)
+
+
+def dpm_kwargs(args):
+    """The CandidateEvaluator keywords of the flags.  With --dpm_solver off the four attributes are removed from `args`: the
+    argument line of log.txt (str(args)) stays what it was before the flags existed."""
+    if getattr(args, "dpm_solver", False):
+        return dict(sampler="dpm_solver", dpm_order=args.dpm_order, dpm_predict_x0=args.dpm_predict_x0,
+                    dpm_thresholding=args.dpm_thresholding)
+    for k in DPM_FLAGS:
+        if hasattr(args, k):
+            delattr(args, k)
+    return {}

@@ -115,7 +115,7 @@ class EvolutionSearcher(object):
                 model, base_diffusion, classifier, image_size=args.image_size, use_ddim=args.use_ddim,
                 clip_denoised=args.clip_denoised, class_cond=args.class_cond,
                 classifier_scale=getattr(args, "classifier_scale", 1.0), device=dist_util.dev(),
-                use_graph=bool(getattr(args, "use_graph", False)))
+                use_graph=bool(getattr(args, "use_graph", False)), **(getattr(args, "dpm", None) or {}))
             self.active_diffusion = self._ev.active_diffusion
 
     # ------------------------------------------------------------------ evaluate-candidate interface

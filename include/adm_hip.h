@@ -513,6 +513,51 @@ int64_t adm_poly3_work_elems(int64_t n, int64_t m, int self_pairs);
 int adm_poly3_sums(const float* x, int64_t n, const float* y, int64_t m, int d, double* work, int64_t work_elems, double* out,
                    void* stream, int self_pairs);
 
+/* ---------------------------------------------------------------- DPM-Solver on the pixel (ADM) path (K17)
+ * Still ABI 10 (additive).  Reference: ldm/models/diffusion/dpm_solver/dpm_solver.py -- model_wrapper's classifier guidance
+ * :312-335, data_prediction_fn with Imagen's dynamic thresholding :386-399, the multistep updates :504-549 and :755-857.
+ *
+ * adm_abs_quantile: out[i] = torch.quantile(v[i].abs(), q) ('linear') of the fp32 rows v [n][per], exactly: the rank is
+ * float32(q) * (per - 1) in float32, its floor and ceil pick two order statistics by radix selection over the bit patterns of |v|
+ * (the elements a sort would give; -0 is 0), torch's lerp joins them.  Integer LDS atomics only: two calls are bitwise equal.  No
+ * host synchronisation, nothing allocated: `work` (16-byte aligned) holds at least adm_abs_quantile_work_bytes(n, per) bytes (-1
+ * for sizes it refuses).  0 < q < 1.  NaN inputs sort above +inf; where both order statistics are the same value the result is that
+ * value (torch answers NaN for inf - inf).  Only out[0 .. n) and the first adm_abs_quantile_work_bytes bytes of work are written.
+ *
+ * adm_pix_dpm_step: one model evaluation of the solver on fp32 NCHW tensors, in the reference's order of operations:
+ *   eps = model_out[:, :C]  (start_x: eps = (x_eval - alpha_s out) / sigma_s);   grad: eps -= sigma_s grad  (grad carries the
+ *   classifier scale);   predict_x0: m = (x_eval - sigma_s eps) / alpha_s, thresholding: s = max(quantile_q |m|, max_val) per image,
+ *   m = clamp(m, -s, s) / s;   else m = eps;   x_next = a x_base + b0 m + b1 h1 + b2 h2.
+ * Required: x_eval, model_out (model_channels = C or 2C), m_out; x_base with x_next.  grad, h1, h2 (their terms are skipped),
+ * x_next, u8_nhwc (the pack of adm_ddim_step, of x_next, or of m where x_next is NULL) and s_out (written with thresholding only)
+ * may be NULL.  Without thresholding: one launch, work unused.  With it (predict_x0 required): the selection over |x0| computed on
+ * the fly, then the update, which recomputes the same x0; work as for adm_abs_quantile(n, C h w).
+ * Both refuse (nonzero, adm_last_error, nothing launched): null required pointers, thresholding without predict_x0, q outside
+ * (0, 1), max_val <= 0, a work buffer that is too small, sizes whose products overflow.
+ * THE STREAM IS THE SECOND-TO-LAST ARGUMENT of both and `flags` (0) the last, as for adm_poly3_sums: their per-element float64
+ * checks live in tests/test_hip_adm_dpm.py.                                                                                  */
+typedef struct adm_pix_dpm_args {
+  const float* x_eval;
+  const float* model_out;
+  const float* grad;
+  const float* x_base;
+  const float* h1;
+  const float* h2;
+  float* m_out;
+  float* x_next;
+  uint8_t* u8_nhwc;
+  float* s_out;
+  void* work;
+  int64_t work_bytes;
+  int32_t n, c, h, w;
+  int32_t model_channels, start_x, predict_x0, thresholding;
+  float alpha_s, sigma_s, a, b0, b1, b2, q, max_val;
+} adm_pix_dpm_args;
+int64_t adm_abs_quantile_work_bytes(int64_t n, int64_t per);
+int adm_abs_quantile(const float* v, int64_t n, int64_t per, float q, void* work, int64_t work_bytes, float* out, void* stream,
+                     int flags);
+int adm_pix_dpm_step(const adm_pix_dpm_args* args, void* stream, int flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,8 +21,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import dist_util, logger  # noqa: E402
 from autodiffusion_amd.evaluate import CandidateEvaluator, parse_int_list  # noqa: E402
-from autodiffusion_amd.script_util import (add_dict_to_argparser, candidate_from_flags, classifier_defaults,  # noqa: E402
-                                           gather_batches, load_classifier, load_model_and_diffusion,
+from autodiffusion_amd.script_util import (add_dict_to_argparser, add_dpm_flags, candidate_from_flags, classifier_defaults,  # noqa: E402
+                                           dpm_kwargs, gather_batches, load_classifier, load_model_and_diffusion,
                                            model_and_diffusion_defaults)
 
 
@@ -36,12 +36,14 @@ def create_argparser():
     defaults.update(classifier_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
+    add_dpm_flags(parser)
     return parser
 
 
 def main(argv=None):
     t1 = time.time()
     args = create_argparser().parse_args(argv)
+    dpm = dpm_kwargs(args)
     if args.use_mean and args.use_timestep is not None:   # an averaged schedule, space-separated floats: round it
         args.use_timestep = str(parse_int_list(args.use_timestep, "--use_timestep", use_mean=True))
     os.environ.setdefault("MASTER_PORT", args.MASTER_PORT)
@@ -54,7 +56,7 @@ def main(argv=None):
 
     ev = CandidateEvaluator(model, diffusion, classifier, image_size=args.image_size, use_ddim=args.use_ddim,
                             clip_denoised=args.clip_denoised, class_cond=args.class_cond,
-                            classifier_scale=args.classifier_scale, device=dist_util.dev())
+                            classifier_scale=args.classifier_scale, device=dist_util.dev(), **dpm)
     ev.set_candidate(candidate_from_flags(args, diffusion))
 
     logger.log("sampling...")

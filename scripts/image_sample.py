@@ -22,8 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import dist_util, logger  # noqa: E402
 from autodiffusion_amd.evaluate import CandidateEvaluator  # noqa: E402
-from autodiffusion_amd.script_util import (add_dict_to_argparser, candidate_from_flags, gather_batches,  # noqa: E402
-                                           load_model_and_diffusion, model_and_diffusion_defaults)
+from autodiffusion_amd.script_util import (add_dict_to_argparser, add_dpm_flags, candidate_from_flags, dpm_kwargs,  # noqa: E402
+                                           gather_batches, load_model_and_diffusion, model_and_diffusion_defaults)
 
 
 def create_argparser():
@@ -32,11 +32,13 @@ def create_argparser():
     defaults.update(model_and_diffusion_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
+    add_dpm_flags(parser)
     return parser
 
 
 def main(argv=None):
     args = create_argparser().parse_args(argv)
+    dpm = dpm_kwargs(args)
     os.environ.setdefault("MASTER_PORT", args.port)
     dist_util.setup_dist()
     logger.configure(args.save_dir or None)
@@ -44,7 +46,7 @@ def main(argv=None):
     model, diffusion = load_model_and_diffusion(args, log_source=True)
 
     ev = CandidateEvaluator(model, diffusion, None, image_size=args.image_size, use_ddim=args.use_ddim,
-                            clip_denoised=args.clip_denoised, class_cond=args.class_cond, device=dist_util.dev())
+                            clip_denoised=args.clip_denoised, class_cond=args.class_cond, device=dist_util.dev(), **dpm)
     ev.set_candidate(candidate_from_flags(args, diffusion))
 
     logger.log("sampling...")
