@@ -1,0 +1,236 @@
+"""What more than one Stable-Diffusion command line (scripts/sd_*.py) uses: the model builders, the prompt and image loaders, the
+sampling scripts' shared flags and a few helpers -- the latent path's counterpart of script_util.py.  A helper that refuses its input
+raises ``SystemExit`` and takes ``prog``, the running script's name, for the message's prefix."""
+import ast
+import json
+import os
+import random
+
+import numpy as np
+import torch
+
+from . import dist_util, logger, sd_clip
+from .inception import InceptionV3
+from .sd_arch import SD_V1
+from .sd_clip import CLIP_VIT_L14_TEXT, FrozenCLIPEmbedder
+from .sd_sampler import DDIMSampler, DPMSolverSampler, LatentDiffusion, PLMSSampler
+from .sd_unet import UNetModel
+from .sd_vae import SD_V1_VAE, AutoencoderKL
+
+# --synthetic tiny: the smallest networks the test suite runs (a 64-wide two-level UNet, a three-level decoder that turns an
+# h x w latent into a 4h x 4w image, a one-layer text transformer of the UNet's context width over 512 token ids)
+TINY_UNET = dict(in_channels=4, out_channels=4, model_channels=64, attention_resolutions=[1, 2], num_res_blocks=1,
+                 channel_mult=[1, 2], num_heads=2, transformer_depth=1, context_dim=128, legacy=False)
+TINY_VAE = dict(ddconfig=dict(ch=32, out_ch=3, ch_mult=(1, 2, 4), num_res_blocks=1, attn_resolutions=[], dropout=0.0, in_channels=3,
+                              resolution=32, z_channels=4), embed_dim=4)
+TINY_CLIP = dict(vocab_size=512, hidden_size=128, intermediate_size=512, num_hidden_layers=1, num_attention_heads=2,
+                 max_position_embeddings=77)
+
+# ------------------------------------------------------------------ the flags sd_img2img.py and sd_inpaint.py share
+SD_SAMPLING_FLAGS = {
+    "--prompt": dict(type=str, nargs="?", default="a painting of a virus monster playing guitar", help="the prompt to render"),
+    "--init-img": dict(type=str, nargs="?", required=True, help="path to the input image (image file, or uint8 NHWC .npy / .npz)"),
+    "--ddim_eta": dict(type=float, default=0.0, help="ddim eta (eta=0.0 corresponds to deterministic sampling)"),
+    "--n_iter": dict(type=int, default=1, help="sample this often"),
+    "--n_samples": dict(type=int, default=2, help="how many samples to produce for each given prompt. A.k.a batch size"),
+    "--scale": dict(type=float, default=5.0, help="unconditional guidance scale: eps = eps(x, empty) + scale * (eps(x, cond) - eps(x, empty))"),
+    "--config": dict(type=str, default="configs/stable-diffusion/v1-inference.yaml",
+                     help="path to config which constructs model (read when the file exists; else the SD-v1 constants)"),
+    "--ckpt": dict(type=str, default="models/ldm/stable-diffusion-v1/model.ckpt", help="path to checkpoint of model"),
+    "--seed": dict(type=int, default=42, help="the seed (for reproducible sampling)"),
+    "--tokenizer_dir": dict(type=str, default="", help="LOCAL directory of the transformers CLIP tokenizer (nothing is fetched)"),
+    "--prompt_ids": dict(type=str, default="", help=".npy int64 [num, T] token ids (num = 1 or --n_samples); replaces --prompt"),
+    "--torso": dict(choices=["bf16", "fp16"], default="bf16", help="16-bit type of activations and weights between kernels"),
+    "--synthetic": dict(choices=["tiny", "v1"], default="", help="build the networks with randomize_() instead of reading --ckpt"),
+    "--use_timestep": dict(type=str, default="", help="'[t0, t1, ...]': a searched schedule of --ddim_steps timesteps"),
+    "--side_multiple": dict(type=int, default=64, help="an image FILE is resized down to a multiple of this many pixels"),
+}
+
+
+def add_sd_sampling_flags(parser, first, last):
+    """Adds SD_SAMPLING_FLAGS from `first` to `last`, in the table's order.  A script calls it once per run of shared flags and
+    defines its own in between: argparse lists its help and fills the namespace in definition order, which the scripts keep."""
+    names = list(SD_SAMPLING_FLAGS)
+    for name in names[names.index(first):names.index(last) + 1]:
+        parser.add_argument(name, **SD_SAMPLING_FLAGS[name])
+
+
+def read_use_timestep(text, ddim_steps, prog):
+    """--use_timestep "[t0, t1, ...]" -> the sorted int array of --ddim_steps entries, or None when the flag is empty."""
+    if not text:
+        return None
+    sched = np.array(sorted(int(t) for t in ast.literal_eval(text)))
+    if sched.shape[0] != ddim_steps:
+        raise SystemExit(f"{prog}: --use_timestep holds {sched.shape[0]} entries; --ddim_steps is {ddim_steps}")
+    return sched
+
+
+def seed_everything(seed):
+    """pytorch_lightning.seed_everything(seed): random, numpy, torch."""
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+
+
+def require_gpu(prog):
+    """-> this rank's device, made current."""
+    device = dist_util.dev()
+    if device.type != "cuda":
+        raise SystemExit(f"{prog}: no GPU is visible (the HIP path has no CPU fallback)")
+    torch.cuda.set_device(device)
+    return device
+
+
+def save_samples(outdir, arr):
+    """uint8 NHWC `arr` -> OUTDIR/samples_{N}x{H}x{W}x3.npz (``arr_0``); returns `arr`."""
+    os.makedirs(outdir, exist_ok=True)
+    path = os.path.join(outdir, "samples_%s.npz" % "x".join(str(v) for v in arr.shape))
+    np.savez(path, arr)
+    logger.log(f"saved {arr.shape[0]} images to {path}")
+    return arr
+
+
+# ------------------------------------------------------------------ prompts and images
+def read_captions(path):
+    """COCO-style JSON -> annotations[i]['caption'].lower() in file order (ldm/data/coco.py:36-46); otherwise one caption per line."""
+    with open(path, "r", encoding="utf-8") as f:
+        text = f.read()
+    if text.lstrip().startswith("{"):
+        return [a["caption"].lower() for a in json.loads(text)["annotations"]]
+    return [line.strip() for line in text.splitlines() if line.strip()]
+
+
+def read_prompt_ids(path, prog, n_samples=None):
+    """--prompt_ids FILE.npy -> int64 [num, T] token ids (host).  n_samples: the file must then hold one row or that many."""
+    ids = np.load(path, allow_pickle=False)
+    if ids.ndim != 2 or not np.issubdtype(ids.dtype, np.integer) or (n_samples is not None and ids.shape[0] not in (1, n_samples)):
+        raise SystemExit(f"{prog}: --prompt_ids must hold an integer [{'1 | n_samples' if n_samples else 'num'}, T] array, "
+                         f"got {ids.dtype} {ids.shape}")
+    return torch.from_numpy(ids.astype(np.int64))
+
+
+def load_prompts(opt, device, prog):
+    """-> (what get_learned_conditioning takes for the batch, for the empty prompt, T of --prompt_ids | None)."""
+    if opt.prompt_ids:
+        ids = read_prompt_ids(opt.prompt_ids, prog, opt.n_samples).expand(opt.n_samples, -1).contiguous().to(device)   # one row: repeated
+        return ids, opt.n_samples * [""], ids.shape[1]
+    if not opt.tokenizer_dir:
+        raise SystemExit(f"{prog}: --prompt needs --tokenizer_dir (a local CLIP tokenizer directory); or pass token ids with --prompt_ids")
+    return opt.n_samples * [opt.prompt], opt.n_samples * [""], None
+
+
+def load_images(path, n_samples, side_multiple, prog):
+    """-> fp32 NCHW [n_samples, 3, H, W] in [-1, 1] (host), as img2img.py:39-49 load_img builds it."""
+    if path.endswith((".npy", ".npz")):
+        arr = np.load(path, allow_pickle=False)
+        arr = arr["arr_0"] if path.endswith(".npz") else arr
+        if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[3] != 3:
+            raise SystemExit(f"{prog}: --init-img must hold a uint8 [N, H, W, 3] batch, got {arr.dtype} {arr.shape}")
+    else:
+        from PIL import Image
+        image = Image.open(path).convert("RGB")
+        w, h = (v - v % side_multiple for v in image.size)
+        print(f"loaded input image of size {image.size} from {path}, resized to ({w}, {h})")
+        arr = np.asarray(image.resize((w, h), resample=Image.LANCZOS), dtype=np.uint8)[None]
+    if arr.shape[0] == 1:
+        arr = np.repeat(arr, n_samples, axis=0)
+    if arr.shape[0] != n_samples:
+        raise SystemExit(f"{prog}: --init-img holds {arr.shape[0]} images; one or --n_samples {n_samples} expected")
+    x = arr.astype(np.float32) / 255.0
+    return torch.from_numpy(2.0 * x - 1.0).permute(0, 3, 1, 2).contiguous()
+
+
+class EmptyPromptTokenizer:
+    """Stands in for the CLIP tokenizer in a --prompt_ids run, which has one string left to tokenise: the empty prompt of
+    classifier-free guidance.  CLIP's tokenizer turns "" into <|startoftext|> followed by <|endoftext|> up to max_length (its pad
+    token is <|endoftext|>), and those two are the last two ids of its vocabulary (49406 and 49407 of 49408)."""
+
+    def __init__(self, vocab_size, prog="sd_search_ea.py"):
+        self.bos, self.eos, self.prog = int(vocab_size) - 2, int(vocab_size) - 1, prog
+
+    def __call__(self, text, max_length, **kw):
+        if any(t != "" for t in text):
+            raise SystemExit(f"{self.prog}: a --prompt_ids run has no tokenizer for strings; give --tokenizer_dir")
+        ids = torch.full((len(text), max_length), self.eos, dtype=torch.int64)
+        ids[:, 0] = self.bos
+        return {"input_ids": ids}
+
+
+# ------------------------------------------------------------------ networks
+def build_model(opt, device, prompt_len=None, with_encoder=False):
+    """LatentDiffusion (UNet + first stage + cond stage) on `device`: synthetic weights, or --ckpt under --config / the v1 constants.
+    prompt_len: the T of --prompt_ids; without --tokenizer_dir the empty prompt is then built as T ids by EmptyPromptTokenizer.
+    with_encoder: the first stage also gets its image encoder."""
+    unet_cfg = dict(image_size=32, use_spatial_transformer=True, **SD_V1)
+    vae_cfg, clip_cfg, ld_cfg = dict(SD_V1_VAE), dict(config=CLIP_VIT_L14_TEXT), {}
+    if opt.synthetic == "tiny":
+        unet_cfg = dict(image_size=32, use_spatial_transformer=True, **TINY_UNET)
+        vae_cfg, clip_cfg = dict(TINY_VAE), dict(config=TINY_CLIP)
+    elif not opt.synthetic and opt.config and os.path.isfile(opt.config):
+        import yaml
+        with open(opt.config, "r", encoding="utf-8") as f:
+            params = yaml.safe_load(f)["model"]["params"]
+        ld_cfg = {k: params[k] for k in ("timesteps", "linear_start", "linear_end", "scale_factor") if k in params}
+        unet_cfg = dict(params["unet_config"].get("params") or {})
+        vae_cfg = dict(params["first_stage_config"].get("params") or {})
+        clip_cfg = dict(params["cond_stage_config"].get("params") or {})
+        clip_cfg.pop("device", None)
+        logger.log(f"model configuration from {opt.config}")
+    elif not opt.synthetic:
+        logger.log(f"--config {opt.config} is not a file: using the SD-v1 constants of the package")
+    if opt.tokenizer_dir:
+        clip_cfg["version"] = opt.tokenizer_dir
+    unet = UNetModel(**unet_cfg).set_torso(opt.torso)
+    vae = AutoencoderKL(**vae_cfg, with_encoder=with_encoder).set_torso(opt.torso)
+    if prompt_len is not None and not opt.tokenizer_dir:
+        clip_cfg["max_length"] = int(prompt_len)
+    clip = FrozenCLIPEmbedder(device="cpu", **clip_cfg).set_torso(opt.torso)
+    if prompt_len is not None and not opt.tokenizer_dir:
+        clip._tokenizer = EmptyPromptTokenizer(clip.transformer.plan.vocab_size)
+    if opt.synthetic:
+        unet.randomize_(1234)
+        vae.randomize_(4321)
+        clip.randomize_(2468)
+        logger.log(f"--synthetic {opt.synthetic}: the networks hold RANDOM weights (randomize_()); --ckpt is not read")
+    unet.to(device)
+    vae.to(device)
+    clip.to(device)
+    model = LatentDiffusion(unet, device=device, first_stage=vae, cond_stage=clip, **ld_cfg)
+    if not opt.synthetic:
+        print(f"Loading model from {opt.ckpt}")
+        pl_sd = torch.load(opt.ckpt, map_location="cpu")
+        if "global_step" in pl_sd:
+            print(f"Global Step: {pl_sd['global_step']}")
+        model.load_state_dict(pl_sd["state_dict"] if "state_dict" in pl_sd else pl_sd, strict=False)
+    return model
+
+
+def build_inception(opt, device, prog="sd_search_ea.py"):
+    if not opt.inception_path and not opt.allow_random_inception:
+        raise SystemExit(f"{prog}: give --inception_path (the pytorch_fid pt_inception-2015-12-05 state_dict); FID on "
+                         "random Inception weights ranks candidates on a meaningless metric (--allow_random_inception opts in "
+                         "for throughput runs and tests)")
+    net = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[2048]]).to(device)
+    if opt.inception_path:
+        net.load_state_dict(dist_util.load_state_dict(opt.inception_path))
+    else:
+        logger.log("WARNING: FID features come from an Inception-v3 with RANDOM weights (--allow_random_inception): "
+                   "every fid value below is NOT a quality metric")
+    return net
+
+
+def build_clip_scorer(opt, device, prompt_len=None):
+    """--clip_ckpt: the CLIPScorer of both towers from one file (the tiny towers under --synthetic tiny)."""
+    tiny = opt.synthetic == "tiny"
+    return sd_clip.build_clip_scorer(dist_util.load_state_dict(opt.clip_ckpt),
+                                     sd_clip.CLIP_TINY_VISION if tiny else None, sd_clip.CLIP_TINY_TEXT_PROJ if tiny else None,
+                                     device=device, torso=opt.torso, tokenizer_dir=opt.tokenizer_dir or None,
+                                     max_length=77 if prompt_len is None or opt.tokenizer_dir else int(prompt_len))
+
+
+def build_sampler(opt, model):
+    if opt.dpm_solver:
+        return DPMSolverSampler(model)
+    if opt.plms:
+        return PLMSSampler(model)
+    return DDIMSampler(model)

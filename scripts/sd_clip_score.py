@@ -14,7 +14,6 @@ cos_i the cosine of ``encode_image`` of image i -- behind the reference embedder
 prompt i.  ``--synthetic tiny`` builds the tiny towers with random weights instead of reading ``--clip_ckpt``: tests.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -26,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import dist_util, sd_clip  # noqa: E402
 from autodiffusion_amd.evaluator import iter_npz_batches  # noqa: E402
+from autodiffusion_amd.sd_script_util import read_captions, read_prompt_ids, require_gpu  # noqa: E402
 
 
 def create_argparser():
@@ -41,14 +41,6 @@ def create_argparser():
     return p
 
 
-def read_captions(path):
-    with open(path, "r", encoding="utf-8") as f:
-        text = f.read()
-    if text.lstrip().startswith("{"):
-        return [a["caption"].lower() for a in json.loads(text)["annotations"]]
-    return [line.strip() for line in text.splitlines() if line.strip()]
-
-
 def main(argv=None):
     opt = create_argparser().parse_args(argv)
     if bool(opt.prompt_ids) == bool(opt.captions):
@@ -57,15 +49,9 @@ def main(argv=None):
         raise SystemExit("sd_clip_score.py: --captions needs --tokenizer_dir (a local CLIP tokenizer directory)")
     if not opt.synthetic and not opt.clip_ckpt:
         raise SystemExit("sd_clip_score.py: give --clip_ckpt (or --synthetic tiny)")
-    device = dist_util.dev()
-    if device.type != "cuda":
-        raise SystemExit("sd_clip_score.py: no GPU is visible (the HIP path has no CPU fallback)")
-    torch.cuda.set_device(device)
+    device = require_gpu("sd_clip_score.py")
     if opt.prompt_ids:
-        prompts = np.load(opt.prompt_ids, allow_pickle=False)
-        if prompts.ndim != 2 or not np.issubdtype(prompts.dtype, np.integer):
-            raise SystemExit(f"sd_clip_score.py: --prompt_ids must hold an integer [num, T] array, got {prompts.dtype} {prompts.shape}")
-        prompts = torch.from_numpy(prompts.astype(np.int64))
+        prompts = read_prompt_ids(opt.prompt_ids, "sd_clip_score.py")
         max_length = int(prompts.shape[1])
     else:
         prompts, max_length = read_captions(opt.captions), 77

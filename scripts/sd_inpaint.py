@@ -15,31 +15,29 @@ first stage's, image side / latent side).
 noisiest first; a step whose entry is 0 runs one unguided evaluation on the empty prompt instead of the guided pair
 (plms.py:164-171, scripts/txt2img_prompt_mask.py).  Everything else -- ``--init-img --ckpt --config --prompt --prompt_ids
 --tokenizer_dir --scale --ddim_steps --ddim_eta --n_samples --n_iter --seed --torso --synthetic --use_timestep --outdir
---side_multiple`` -- is scripts/sd_img2img.py's.  Output: ``OUTDIR/samples_{N}x{H}x{W}x3.npz`` with ``arr_0`` = uint8 NHWC images.
+--side_multiple`` -- is scripts/sd_img2img.py's; what the two share is autodiffusion_amd/sd_script_util.py's.  Output:
+``OUTDIR/samples_{N}x{H}x{W}x3.npz`` with ``arr_0`` = uint8 NHWC images.
 """
 import argparse
 import ast
 import os
-import random
 import sys
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from autodiffusion_amd import dist_util, logger, ops  # noqa: E402
-from sd_img2img import load_images, load_prompts  # noqa: E402
-from sd_search_ea import build_model  # noqa: E402
+from autodiffusion_amd import logger, ops  # noqa: E402
+from autodiffusion_amd.sd_script_util import (add_sd_sampling_flags, build_model, load_images, load_prompts, read_use_timestep,  # noqa: E402
+                                              require_gpu, save_samples, seed_everything)
 
 F8 = 8   # pixels per latent of the KL-f8 first stage (--synthetic tiny's has two downsamplings: 4)
 
 
 def create_argparser():
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    p.add_argument("--prompt", type=str, nargs="?", default="a painting of a virus monster playing guitar", help="the prompt to render")
-    p.add_argument("--init-img", type=str, nargs="?", required=True, help="path to the input image (image file, or uint8 NHWC .npy / .npz)")
+    add_sd_sampling_flags(p, "--prompt", "--init-img")
     p.add_argument("--mask", type=str, required=True,
                    help="image file, or uint8 [N or 1, H, W] .npy / .npz of the image's size: white (>= 128) means REPAINT (inpaint.py's "
                         "convention); the script inverts it into the samplers' keep mask (1 keeps the image)")
@@ -49,21 +47,7 @@ def create_argparser():
     p.add_argument("--prompt_mask", type=str, default="", help="'[1,1,0,...]', --plms only: one entry per step, noisiest first; 0 = that "
                                                                "step runs unguided on the empty prompt")
     p.add_argument("--no_composite", action="store_true", help="write the decoded images as they are: do not restore the kept pixels")
-    p.add_argument("--ddim_eta", type=float, default=0.0, help="ddim eta (eta=0.0 corresponds to deterministic sampling)")
-    p.add_argument("--n_iter", type=int, default=1, help="sample this often")
-    p.add_argument("--n_samples", type=int, default=2, help="how many samples to produce for each given prompt. A.k.a batch size")
-    p.add_argument("--scale", type=float, default=5.0,
-                   help="unconditional guidance scale: eps = eps(x, empty) + scale * (eps(x, cond) - eps(x, empty))")
-    p.add_argument("--config", type=str, default="configs/stable-diffusion/v1-inference.yaml",
-                   help="path to config which constructs model (read when the file exists; else the SD-v1 constants)")
-    p.add_argument("--ckpt", type=str, default="models/ldm/stable-diffusion-v1/model.ckpt", help="path to checkpoint of model")
-    p.add_argument("--seed", type=int, default=42, help="the seed (for reproducible sampling)")
-    p.add_argument("--tokenizer_dir", type=str, default="", help="LOCAL directory of the transformers CLIP tokenizer (nothing is fetched)")
-    p.add_argument("--prompt_ids", type=str, default="", help=".npy int64 [num, T] token ids (num = 1 or --n_samples); replaces --prompt")
-    p.add_argument("--torso", choices=["bf16", "fp16"], default="bf16", help="16-bit type of activations and weights between kernels")
-    p.add_argument("--synthetic", choices=["tiny", "v1"], default="", help="build the networks with randomize_() instead of reading --ckpt")
-    p.add_argument("--use_timestep", type=str, default="", help="'[t0, t1, ...]': a searched schedule of --ddim_steps timesteps")
-    p.add_argument("--side_multiple", type=int, default=64, help="an image FILE is resized down to a multiple of this many pixels")
+    add_sd_sampling_flags(p, "--ddim_eta", "--side_multiple")
     return p
 
 
@@ -110,26 +94,16 @@ def main(argv=None):
             raise SystemExit(f"sd_inpaint.py: --prompt_mask holds {len(prompt_mask)} entries; --ddim_steps is {opt.ddim_steps}")
         if opt.scale == 1.0 and 0 in prompt_mask:
             raise SystemExit("sd_inpaint.py: --prompt_mask with a 0 entry needs --scale != 1 (the empty prompt is encoded only then)")
-    sched = None
-    if opt.use_timestep:
-        sched = np.array(sorted(int(t) for t in ast.literal_eval(opt.use_timestep)))
-        if sched.shape[0] != opt.ddim_steps:
-            raise SystemExit(f"sd_inpaint.py: --use_timestep holds {sched.shape[0]} entries; --ddim_steps is {opt.ddim_steps}")
-    random.seed(opt.seed)      # pytorch_lightning.seed_everything(opt.seed): random, numpy, torch
-    np.random.seed(opt.seed)
-    torch.manual_seed(opt.seed)
+    sched = read_use_timestep(opt.use_timestep, opt.ddim_steps, "sd_inpaint.py")
+    seed_everything(opt.seed)
     logger.configure(opt.outdir)
-    device = dist_util.dev()
-    if device.type != "cuda":
-        raise SystemExit("sd_inpaint.py: no GPU is visible (the HIP path has no CPU fallback)")
-    torch.cuda.set_device(device)
-    init_image = load_images(opt.init_img, opt.n_samples, opt.side_multiple)
+    device = require_gpu("sd_inpaint.py")
+    init_image = load_images(opt.init_img, opt.n_samples, opt.side_multiple, "sd_inpaint.py")
     n, _, height, width = init_image.shape
     init_u8 = np.rint((init_image.permute(0, 2, 3, 1).numpy() + 1.0) * 127.5).astype(np.uint8)   # load_images' 2 * (u8 / 255) - 1, undone
     repaint = load_mask(opt.mask, opt.n_samples, (height, width), opt.side_multiple)
-    prompts, empty, prompt_len = load_prompts(opt, device)
-    opt.with_encoder = True
-    model = build_model(opt, device, prompt_len=prompt_len)
+    prompts, empty, prompt_len = load_prompts(opt, device, "sd_inpaint.py")
+    model = build_model(opt, device, prompt_len=prompt_len, with_encoder=True)
     sampler = (PLMSSampler if opt.plms else DDIMSampler)(model)
     x0 = model.get_first_stage_encoding(model.encode_first_stage(init_image.to(device)))   # move to latent space
     f = height // x0.shape[2]
@@ -147,12 +121,7 @@ def main(argv=None):
         _, u8 = ops.vae_image_out(model.decode_first_stage(samples), want_unit=False, want_u8=True)
         u8 = u8.cpu().numpy()
         out.append(u8 if opt.no_composite else composite(init_u8, u8, repaint))
-    arr = np.concatenate(out, axis=0)
-    os.makedirs(opt.outdir, exist_ok=True)
-    path = os.path.join(opt.outdir, "samples_%s.npz" % "x".join(str(v) for v in arr.shape))
-    np.savez(path, arr)
-    logger.log(f"saved {arr.shape[0]} images to {path}")
-    return arr
+    return save_samples(opt.outdir, np.concatenate(out, axis=0))
 
 
 if __name__ == "__main__":

@@ -37,9 +37,7 @@ without it the SD-v1 constants of the package are used.
 ``No.i cand fid = v`` and ``total searching time = ... hours`` (ranks > 0 write ``log-rankNNN.txt``).
 """
 import argparse
-import json
 import os
-import random
 import sys
 import time
 
@@ -50,18 +48,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import dist_util, logger  # noqa: E402
 from autodiffusion_amd.script_util import str2bool  # noqa: E402
+from autodiffusion_amd.sd_script_util import (TINY_CLIP, TINY_UNET, TINY_VAE, EmptyPromptTokenizer, build_clip_scorer,  # noqa: E402,F401
+                                              build_inception, build_model, build_sampler, read_captions, read_prompt_ids, require_gpu,
+                                              seed_everything)
 from autodiffusion_amd.sd_search import EvolutionSearcher, dpm_search_params, parse_sd_candidate  # noqa: E402
 
 IGNORED = ("precision", "laion400m", "skip_grid", "skip_save", "n_iter", "n_rows", "prompt", "ddim_steps", "cal_fid", "data_dir")
-
-# --synthetic tiny: the smallest networks the test suite runs (a 64-wide two-level UNet, a three-level decoder that turns an
-# h x w latent into a 4h x 4w image, a one-layer text transformer of the UNet's context width over 512 token ids)
-TINY_UNET = dict(in_channels=4, out_channels=4, model_channels=64, attention_resolutions=[1, 2], num_res_blocks=1,
-                 channel_mult=[1, 2], num_heads=2, transformer_depth=1, context_dim=128, legacy=False)
-TINY_VAE = dict(ddconfig=dict(ch=32, out_ch=3, ch_mult=(1, 2, 4), num_res_blocks=1, attn_resolutions=[], dropout=0.0, in_channels=3,
-                              resolution=32, z_channels=4), embed_dim=4)
-TINY_CLIP = dict(vocab_size=512, hidden_size=128, intermediate_size=512, num_hidden_layers=1, num_attention_heads=2,
-                 max_position_embeddings=77)
 
 
 def create_argparser():
@@ -132,15 +124,6 @@ def create_argparser():
 
 
 # ------------------------------------------------------------------ prompts
-def read_captions(path):
-    """COCO-style JSON -> annotations[i]['caption'].lower() in file order (ldm/data/coco.py:36-46); otherwise one caption per line."""
-    with open(path, "r", encoding="utf-8") as f:
-        text = f.read()
-    if text.lstrip().startswith("{"):
-        return [a["caption"].lower() for a in json.loads(text)["annotations"]]
-    return [line.strip() for line in text.splitlines() if line.strip()]
-
-
 def batch_captions(captions, n_samples):
     """DataLoader(batch_size=n_samples, shuffle=False, drop_last=True) (build_dataloader.py:66-73): batches of {'text': [...]}."""
     return [{"text": list(captions[i:i + n_samples])} for i in range(0, len(captions) - n_samples + 1, n_samples)]
@@ -148,10 +131,7 @@ def batch_captions(captions, n_samples):
 
 def build_loader(opt, device):
     if opt.prompt_ids:
-        ids = np.load(opt.prompt_ids, allow_pickle=False)
-        if ids.ndim != 2 or not np.issubdtype(ids.dtype, np.integer):
-            raise SystemExit(f"sd_search_ea.py: --prompt_ids must hold an integer [num, T] array, got {ids.dtype} {ids.shape}")
-        ids = torch.from_numpy(ids.astype(np.int64)).to(device)
+        ids = read_prompt_ids(opt.prompt_ids, "sd_search_ea.py").to(device)
         loader = [{"text": ids[i:i + opt.n_samples]} for i in range(0, ids.shape[0] - opt.n_samples + 1, opt.n_samples)]
     elif opt.captions:
         if not opt.tokenizer_dir:
@@ -165,22 +145,6 @@ def build_loader(opt, device):
     return loader
 
 
-class EmptyPromptTokenizer:
-    """Stands in for the CLIP tokenizer in a --prompt_ids run, which has one string left to tokenise: the empty prompt of
-    classifier-free guidance.  CLIP's tokenizer turns "" into <|startoftext|> followed by <|endoftext|> up to max_length (its pad
-    token is <|endoftext|>), and those two are the last two ids of its vocabulary (49406 and 49407 of 49408)."""
-
-    def __init__(self, vocab_size):
-        self.bos, self.eos = int(vocab_size) - 2, int(vocab_size) - 1
-
-    def __call__(self, text, max_length, **kw):
-        if any(t != "" for t in text):
-            raise SystemExit("sd_search_ea.py: a --prompt_ids run has no tokenizer for strings; give --tokenizer_dir")
-        ids = torch.full((len(text), max_length), self.eos, dtype=torch.int64)
-        ids[:, 0] = self.bos
-        return {"input_ids": ids}
-
-
 # ------------------------------------------------------------------ reference statistics
 def load_ref_stats(opt):
     if opt.ref_mu.endswith(".npz") and not opt.ref_sigma:
@@ -190,93 +154,6 @@ def load_ref_stats(opt):
         raise SystemExit("sd_search_ea.py: give --ref_mu MU.npy --ref_sigma SIGMA.npy, or --ref_mu STATS.npz holding mu and sigma")
     return (np.asarray(np.load(opt.ref_mu, allow_pickle=False), dtype=np.float64),
             np.asarray(np.load(opt.ref_sigma, allow_pickle=False), dtype=np.float64))
-
-
-# ------------------------------------------------------------------ networks
-def build_model(opt, device, prompt_len=None):
-    """LatentDiffusion (UNet + first stage + cond stage) on `device`: synthetic weights, or --ckpt under --config / the v1 constants.
-    prompt_len: the T of --prompt_ids; without --tokenizer_dir the empty prompt is then built as T ids by EmptyPromptTokenizer."""
-    from autodiffusion_amd.sd_arch import SD_V1
-    from autodiffusion_amd.sd_clip import CLIP_VIT_L14_TEXT, FrozenCLIPEmbedder
-    from autodiffusion_amd.sd_sampler import LatentDiffusion
-    from autodiffusion_amd.sd_unet import UNetModel
-    from autodiffusion_amd.sd_vae import SD_V1_VAE, AutoencoderKL
-    unet_cfg = dict(image_size=32, use_spatial_transformer=True, **SD_V1)
-    vae_cfg, clip_cfg, ld_cfg = dict(SD_V1_VAE), dict(config=CLIP_VIT_L14_TEXT), {}
-    if opt.synthetic == "tiny":
-        unet_cfg = dict(image_size=32, use_spatial_transformer=True, **TINY_UNET)
-        vae_cfg, clip_cfg = dict(TINY_VAE), dict(config=TINY_CLIP)
-    elif not opt.synthetic and opt.config and os.path.isfile(opt.config):
-        import yaml
-        with open(opt.config, "r", encoding="utf-8") as f:
-            params = yaml.safe_load(f)["model"]["params"]
-        ld_cfg = {k: params[k] for k in ("timesteps", "linear_start", "linear_end", "scale_factor") if k in params}
-        unet_cfg = dict(params["unet_config"].get("params") or {})
-        vae_cfg = dict(params["first_stage_config"].get("params") or {})
-        clip_cfg = dict(params["cond_stage_config"].get("params") or {})
-        clip_cfg.pop("device", None)
-        logger.log(f"model configuration from {opt.config}")
-    elif not opt.synthetic:
-        logger.log(f"--config {opt.config} is not a file: using the SD-v1 constants of the package")
-    if opt.tokenizer_dir:
-        clip_cfg["version"] = opt.tokenizer_dir
-    unet = UNetModel(**unet_cfg).set_torso(opt.torso)
-    vae = AutoencoderKL(**vae_cfg, with_encoder=getattr(opt, "with_encoder", False)).set_torso(opt.torso)   # sd_img2img.py asks for the encoder
-    if prompt_len is not None and not opt.tokenizer_dir:
-        clip_cfg["max_length"] = int(prompt_len)
-    clip = FrozenCLIPEmbedder(device="cpu", **clip_cfg).set_torso(opt.torso)
-    if prompt_len is not None and not opt.tokenizer_dir:
-        clip._tokenizer = EmptyPromptTokenizer(clip.transformer.plan.vocab_size)
-    if opt.synthetic:
-        unet.randomize_(1234)
-        vae.randomize_(4321)
-        clip.randomize_(2468)
-        logger.log(f"--synthetic {opt.synthetic}: the networks hold RANDOM weights (randomize_()); --ckpt is not read")
-    unet.to(device)
-    vae.to(device)
-    clip.to(device)
-    model = LatentDiffusion(unet, device=device, first_stage=vae, cond_stage=clip, **ld_cfg)
-    if not opt.synthetic:
-        print(f"Loading model from {opt.ckpt}")
-        pl_sd = torch.load(opt.ckpt, map_location="cpu")
-        if "global_step" in pl_sd:
-            print(f"Global Step: {pl_sd['global_step']}")
-        model.load_state_dict(pl_sd["state_dict"] if "state_dict" in pl_sd else pl_sd, strict=False)
-    return model
-
-
-def build_inception(opt, device):
-    from autodiffusion_amd.inception import InceptionV3
-    if not opt.inception_path and not opt.allow_random_inception:
-        raise SystemExit("sd_search_ea.py: give --inception_path (the pytorch_fid pt_inception-2015-12-05 state_dict); FID on "
-                         "random Inception weights ranks candidates on a meaningless metric (--allow_random_inception opts in "
-                         "for throughput runs and tests)")
-    net = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[2048]]).to(device)
-    if opt.inception_path:
-        net.load_state_dict(dist_util.load_state_dict(opt.inception_path))
-    else:
-        logger.log("WARNING: FID features come from an Inception-v3 with RANDOM weights (--allow_random_inception): "
-                   "every fid value below is NOT a quality metric")
-    return net
-
-
-def build_clip_scorer(opt, device, prompt_len=None):
-    """--clip_ckpt: the CLIPScorer of both towers from one file (the tiny towers under --synthetic tiny)."""
-    from autodiffusion_amd import sd_clip
-    tiny = opt.synthetic == "tiny"
-    return sd_clip.build_clip_scorer(dist_util.load_state_dict(opt.clip_ckpt),
-                                     sd_clip.CLIP_TINY_VISION if tiny else None, sd_clip.CLIP_TINY_TEXT_PROJ if tiny else None,
-                                     device=device, torso=opt.torso, tokenizer_dir=opt.tokenizer_dir or None,
-                                     max_length=77 if prompt_len is None or opt.tokenizer_dir else int(prompt_len))
-
-
-def build_sampler(opt, model):
-    from autodiffusion_amd.sd_sampler import DDIMSampler, DPMSolverSampler, PLMSSampler
-    if opt.dpm_solver:
-        return DPMSolverSampler(model)
-    if opt.plms:
-        return PLMSSampler(model)
-    return DDIMSampler(model)
 
 
 def main(argv=None, *, evaluator=None):
@@ -290,9 +167,7 @@ def main(argv=None, *, evaluator=None):
         # the defaults leave no trace: log.txt's argument line (str(opt) below) stays what it was before the two flags existed
         del opt.fitness, opt.ref_feats
     ignored = [k for k in IGNORED if getattr(opt, k) is not None]
-    random.seed(opt.seed)      # pytorch_lightning.seed_everything(opt.seed): random, numpy, torch
-    np.random.seed(opt.seed)
-    torch.manual_seed(opt.seed)
+    seed_everything(opt.seed)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         dist_util.setup_dist()
     logger.configure(opt.outdir)
@@ -304,10 +179,7 @@ def main(argv=None, *, evaluator=None):
     model = sampler = inception = clip_scorer = None
     dpm_params = None
     if evaluator is None:
-        device = dist_util.dev()
-        if device.type != "cuda":
-            raise SystemExit("sd_search_ea.py: no GPU is visible (the HIP path has no CPU fallback)")
-        torch.cuda.set_device(device)
+        device = require_gpu("sd_search_ea.py")
         loader = build_loader(opt, device)
         ids = loader[0]["text"]
         model = build_model(opt, device, prompt_len=ids.shape[1] if torch.is_tensor(ids) else None)
