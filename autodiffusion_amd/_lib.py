@@ -137,6 +137,8 @@ SIGNATURES = {
     # the stream is second to last here (the integer mode is last): include/adm_hip.h says why
     "adm_poly3_work_elems": (C.c_int64, [C.c_int64, C.c_int64, _I]),
     "adm_poly3_sums": (_I, [_P, C.c_int64, _P, C.c_int64, _I, _P, C.c_int64, _P, _P, _I]),
+    "adm_rbf_work_elems": (C.c_int64, [C.c_int64, C.c_int64, _I]),
+    "adm_rbf_sums": (_I, [_P, C.c_int64, _P, C.c_int64, _I, C.c_double, _P, C.c_int64, _P, _P, _I]),
     # likewise: stream second to last, `flags` last
     "adm_abs_quantile_work_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "adm_abs_quantile": (_I, [_P, C.c_int64, C.c_int64, _F, _P, C.c_int64, _P, _P, _I]),

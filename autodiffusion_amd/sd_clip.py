@@ -678,6 +678,14 @@ class CLIPScorer:
     def cosine(self, images, ids):
         """images: uint8 NHWC or fp32 NCHW in [0, 1]; ids: integer [N, T] (or strings, where the text embedder has a tokenizer)
         -> fp32 [N] on the host."""
+        return self.cosine_and_embeds(images, ids)[0]
+
+    def embeds(self, images):
+        """fp32 device [N, E]: ``encode_image`` of the images (projected, NOT normalised) -- the rows CMMD works on (cmmd.py)."""
+        return self.image_embedder(images, unit=True).to(torch.float32)
+
+    def cosine_and_embeds(self, images, ids):
+        """(cosine(images, ids), embeds(images)) from ONE pass of the image tower."""
         img = self.image_embedder(images, unit=True)
         txt = self.text_embedder.transformer.pooled(self.text_embedder.tokens(ids))   # not normalised: the norms are taken below
         if txt.shape != img.shape:
@@ -686,7 +694,7 @@ class CLIPScorer:
         for i in range(0, img.shape[0], 256):
             dots.append(ops.linear_f32(img[i:i + 256].contiguous(), txt[i:i + 256].contiguous()).diagonal().double().cpu())
         cos = torch.cat(dots) / (_squared_norms(img) * _squared_norms(txt)).sqrt()
-        return cos.to(torch.float32)
+        return cos.to(torch.float32), img.to(torch.float32)
 
     @staticmethod
     def score_of(cosines) -> float:

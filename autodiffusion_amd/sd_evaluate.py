@@ -63,7 +63,8 @@ def inception_features(net, dims: int = 2048, allow_random: bool = False):
 class SDCandidateEvaluator:
     def __init__(self, model, sampler, conditioning=None, ref_mu=None, ref_sigma=None, num_samples: int = None, *, prompts=None,
                  features=None, inception=None, dims: int = 2048, allow_random_inception: bool = False, seed: int = 0,
-                 device=None, image_out=None, accumulator=None, clip_scorer=None, fitness: str = "fid", ref_feats=None):
+                 device=None, image_out=None, accumulator=None, clip_scorer=None, fitness: str = "fid", ref_feats=None,
+                 ref_clip_feats=None, cmmd_sigma: float = 10.0, image_sharded: bool = False):
         """model: ``sd_sampler.LatentDiffusion`` with a first stage (``decode_first_stage``); sampler: one of the
         ``sd_sampler`` samplers around it; conditioning: iterable of per-batch ``(c, uc)`` device tensors (``uc`` may be None
         when ``opt.scale == 1``), re-iterated by every call; prompts (instead of conditioning; the model then needs a cond
@@ -77,15 +78,24 @@ class SDCandidateEvaluator:
         sample_time and begin by waiting for the batch's images).  The FID does not change by a bit.
         fitness="kid" with ref_feats= (fp32 rows [m, dims], an array or the .npz of scripts/evaluator.py --save_ref_feats): the value
         returned is ``kid.KIDReference.fitness`` of the candidate's activation rows -- 1000 x the unbiased cubic-kernel MMD^2 -- and the
-        log line says so; ref_mu / ref_sigma are then not needed."""
+        log line says so; ref_mu / ref_sigma are then not needed.
+        fitness="cmmd" with ref_clip_feats= (fp32 CLIP image embeddings [m, E], an array or the .npz of scripts/sd_clip_score.py
+        --save_clip_feats) and clip_scorer= (it also needs ``cosine_and_embeds(images, prompts) -> ([N], [N, E])``): the value returned
+        is ``cmmd.CMMDReference.fitness`` of the candidate's image embeddings -- 1000 x the unbiased RBF-kernel MMD^2 on the normalised
+        embeddings -- kept on the device batch by batch from the scorer's one tower pass.  No extractor is built or run (``features``
+        is None) and no statistics are accumulated; fid_time is the two kernel sums.  image_sharded (this fitness only): under a
+        process group whose collectives are on, rank r samples the batches r, r + world, ... (the start noise is a function of the
+        batch index, not of the rank) and the rows are pooled over the ranks (``kid.pooled_rows``); False -- the population-parallel
+        search -- keeps every batch and every row on this rank."""
         if (conditioning is None) == (prompts is None):
             raise ValueError("SDCandidateEvaluator: pass exactly one of conditioning= (precomputed (c, uc) batches) and prompts=")
         if clip_scorer is not None and prompts is None:
             raise ValueError("SDCandidateEvaluator: clip_scorer= scores images against their prompts: pass prompts=, not conditioning=")
         self.clip_scorer, self.last_clip = clip_scorer, None
-        if fitness not in ("fid", "kid"):
-            raise ValueError(f"SDCandidateEvaluator: fitness {fitness!r}: expected 'fid' or 'kid'")
+        if fitness not in ("fid", "kid", "cmmd"):
+            raise ValueError(f"SDCandidateEvaluator: fitness {fitness!r}: expected 'fid' or 'kid', or 'cmmd'")
         self.fitness, self.kid_ref, self.last_rows = fitness, None, None
+        self.cmmd_ref, self.cmmd_sigma, self.image_sharded = None, float(cmmd_sigma), bool(image_sharded) and fitness == "cmmd"
         if fitness == "kid":
             if ref_feats is None or (isinstance(ref_feats, str) and not ref_feats) or num_samples is None:
                 raise ValueError("SDCandidateEvaluator: fitness='kid' needs ref_feats= (rows or an .npz with `feats`) and num_samples")
@@ -93,6 +103,17 @@ class SDCandidateEvaluator:
                 from .kid import load_ref_feats
                 ref_feats = load_ref_feats(ref_feats)
             self._ref_feats = ref_feats
+        elif fitness == "cmmd":
+            if ref_clip_feats is None or (isinstance(ref_clip_feats, str) and not ref_clip_feats) or num_samples is None:
+                raise ValueError("SDCandidateEvaluator: fitness='cmmd' needs ref_clip_feats= (rows or an .npz with `clip_feats`) and "
+                                 "num_samples")
+            if clip_scorer is None or not hasattr(clip_scorer, "cosine_and_embeds"):
+                raise ValueError("SDCandidateEvaluator: fitness='cmmd' needs clip_scorer= (an sd_clip.CLIPScorer: its image tower "
+                                 "produces the embeddings CMMD is computed on)")
+            if isinstance(ref_clip_feats, str):
+                from .cmmd import load_ref_clip_feats
+                ref_clip_feats = load_ref_clip_feats(ref_clip_feats)
+            self._ref_clip_feats = ref_clip_feats
         elif ref_mu is None or ref_sigma is None or num_samples is None:
             raise ValueError("SDCandidateEvaluator: ref_mu, ref_sigma and num_samples are required")
         self.model, self.sampler, self.conditioning, self.prompts = model, sampler, conditioning, prompts
@@ -101,13 +122,17 @@ class SDCandidateEvaluator:
                           if ref_mu is not None and ref_sigma is not None else None)
         self.num_samples, self.seed, self.dims = int(num_samples), int(seed), int(dims)
         self.device = torch.device(device) if device is not None else getattr(model, "device", torch.device("cpu"))
-        if features is None:
+        if fitness == "cmmd":
+            features = None          # CMMD needs no Inception pass: no extractor is built, none runs
+        elif features is None:
             if inception is None:
                 raise ValueError("SDCandidateEvaluator: pass features= (a callable) or inception= (an InceptionV3)")
             features = inception_features(inception, dims, allow_random_inception)
         self.features = features
         self.fid_note = (" [FID on RANDOM Inception weights: not a quality metric]"
                          if getattr(features, "random_weights", False) else "")
+        if fitness == "cmmd":
+            self.fid_note += " [fitness: CMMD x 1e3 (unbiased)]"
         self._image_out = image_out or (lambda x, out: ops.vae_image_out(x, unit_out=out)[0])
         if fitness == "kid":
             self.fid_note += " [fitness: KID x 1e3]"
@@ -123,6 +148,13 @@ class SDCandidateEvaluator:
         g = torch.Generator().manual_seed(int(seed))
         x = torch.randn([opt.n_samples, opt.C, opt.H // opt.f, opt.W // opt.f], generator=g, dtype=torch.float32)
         return x.to(self.device)
+
+    def _shard(self):
+        """(world, rank) of the image-sharded CMMD evaluation; (1, 0) everywhere else: every batch is this rank's."""
+        from . import dist_util
+        if self.image_sharded and dist_util.collectives_on():
+            return dist_util.get_world_size(), dist_util.get_rank()
+        return 1, 0
 
     # ------------------------------------------------------------------ search_ea.py:520-526
     def _batches(self, opt):
@@ -148,13 +180,20 @@ class SDCandidateEvaluator:
         fixed = self.start_code(opt, batch_seed(seed0, 0)) if opt.fixed_code else None
         shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
         sampled_timestep = np.array(cand)
-        acc = self._accumulator()
+        use_cmmd = self.fitness == "cmmd"
+        acc = None if use_cmmd else self._accumulator()
         stage, fill, count, plan = None, 0, 0, []
-        cosines, clip_time = [], 0.0
+        cosines, clip_time, embeds = [], 0.0, []
+        world, rank = self._shard()
         with torch.no_grad():
             for itr, (c, uc, prompts) in enumerate(self._batches(opt)):
                 if opt.scale == 1.0:
                     uc = None
+                if itr % world != rank:      # image-sharded CMMD: another rank samples this batch; the count runs on
+                    count += int(opt.n_samples)
+                    if count > self.num_samples:
+                        break
+                    continue
                 seed = batch_seed(seed0, 0 if opt.fixed_code else itr)
                 x_T = fixed if opt.fixed_code else self.start_code(opt, seed)
                 plan.append((itr, seed))
@@ -170,6 +209,14 @@ class SDCandidateEvaluator:
                 while done < x.shape[0]:
                     take = min(x.shape[0] - done, FID_BATCH - fill)
                     self._image_out(x[done:done + take], stage[fill:fill + take])
+                    if use_cmmd:
+                        t0 = time.time()
+                        cos, emb = self.clip_scorer.cosine_and_embeds(stage[fill:fill + take], prompts[done:done + take])
+                        cosines.append(torch.as_tensor(cos).cpu())
+                        embeds.append(emb)
+                        clip_time += time.time() - t0
+                        fill, done = 0, done + take      # nothing is staged for an extractor
+                        continue
                     if self.clip_scorer is not None:
                         t0 = time.time()
                         cosines.append(torch.as_tensor(self.clip_scorer.cosine(stage[fill:fill + take], prompts[done:done + take])).cpu())
@@ -191,7 +238,14 @@ class SDCandidateEvaluator:
             torch.cuda.synchronize(self.device)
         sample_time = time.time() - t1
         t1 = time.time()
-        if self.fitness == "kid":
+        if use_cmmd:
+            from . import cmmd
+            if self.cmmd_ref is None:      # uploads the reference embeddings and computes S_yy once
+                self.cmmd_ref = cmmd.CMMDReference(self._ref_clip_feats, device=self.device, sigma=self.cmmd_sigma)
+            mine = torch.cat(embeds, 0) if embeds else torch.zeros((0, self.cmmd_ref.y.shape[1]), dtype=torch.float32, device=self.device)
+            self.last_rows = cmmd.pooled_rows(mine, None, local=not self.image_sharded)
+            fid = float(self.cmmd_ref.fitness(self.last_rows))                     # fid_time: the two kernel sums
+        elif self.fitness == "kid":
             from .kid import KIDReference
             if self.kid_ref is None:
                 self.kid_ref = KIDReference(self._ref_feats, device=self.device)   # uploads the rows and computes S_yy once
@@ -205,7 +259,7 @@ class SDCandidateEvaluator:
         logger.log('sample_time: ' + str(sample_time) + ', fid_time: ' + str(fid_time))
         self.last_times = {"sample_time": sample_time, "fid_time": fid_time, "images": count, "batches": len(plan)}
         self.last_plan = plan
-        if self.clip_scorer is not None:
+        if self.clip_scorer is not None and cosines:
             cos = torch.cat(cosines)
             self.last_clip = {"score": float(self.clip_scorer.score_of(cos)), "cosines": cos, "clip_time": clip_time}
             logger.log('CLIP score: ' + str(self.last_clip["score"]) + ', clip_time: ' + str(clip_time))

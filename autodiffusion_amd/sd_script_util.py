@@ -228,6 +228,27 @@ def build_clip_scorer(opt, device, prompt_len=None):
                                      max_length=77 if prompt_len is None or opt.tokenizer_dir else int(prompt_len))
 
 
+# ------------------------------------------------------------------ CMMD (autodiffusion_amd/cmmd.py)
+def require_cmmd_flags(opt, prog):
+    """--fitness cmmd: the reference embeddings and the CLIP towers that embed the candidate's images."""
+    if not getattr(opt, "ref_clip_feats", ""):
+        raise SystemExit(f"{prog}: --fitness cmmd needs --ref_clip_feats FILE.npz (scripts/sd_clip_score.py --save_clip_feats writes it)")
+    if not opt.clip_ckpt:
+        raise SystemExit(f"{prog}: --fitness cmmd needs --clip_ckpt CLIP.pt (the image tower produces the embeddings)")
+
+
+def save_clip_feats(path, rows):
+    """fp32 [N, E] image embeddings -> the .npz array `clip_feats` that cmmd.load_ref_clip_feats reads."""
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float32))
+    if rows.ndim != 2 or rows.shape[0] < 2:
+        raise SystemExit(f"--save_clip_feats: need at least 2 images, got rows {rows.shape}")
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "wb") as f:      # an open file: np.savez appends no suffix to the name given
+        np.savez(f, clip_feats=rows)
+    return path
+
+
 def build_sampler(opt, model):
     if opt.dpm_solver:
         return DPMSolverSampler(model)

@@ -84,7 +84,7 @@ class EvolutionSearcher(object):
 
     def __init__(self, opt, model, time_step, ref_mu, ref_sigma, sampler, dataloader_info, batch_size, dpm_params=None, *,
                  evaluator=None, population_parallel=False, inception=None, features=None, allow_random_inception=False,
-                 clip_scorer=None, fitness="fid", ref_feats=None):
+                 clip_scorer=None, fitness="fid", ref_feats=None, ref_clip_feats=None):
         self.opt = opt
         self.model = model
         self.sampler = sampler
@@ -119,7 +119,10 @@ class EvolutionSearcher(object):
                 model, sampler, ref_mu=self.ref_mu, ref_sigma=self.ref_sigma, num_samples=opt.num_sample,
                 prompts=_Texts(dataloader_info['validation_loader']), features=features, inception=inception,
                 allow_random_inception=allow_random_inception, seed=int(getattr(opt, "seed", 0)), clip_scorer=clip_scorer,
-                fitness=fitness, ref_feats=ref_feats)   # 'kid': 1000 x the unbiased cubic-kernel MMD^2 against the rows ref_feats
+                fitness=fitness, ref_feats=ref_feats,   # 'kid': 1000 x the unbiased cubic-kernel MMD^2 against the rows ref_feats
+                # 'cmmd': 1000 x the unbiased RBF-kernel MMD^2 of the CLIP image embeddings against ref_clip_feats; the batches
+                # are sharded over the ranks and the rows pooled unless whole candidates are (population_parallel)
+                ref_clip_feats=ref_clip_feats, image_sharded=not population_parallel)
         self.evaluator = evaluator
         # an extractor on random weights ranks candidates on a meaningless metric: every FID line of log.txt says so
         self.fid_note = getattr(evaluator, "fid_note", "")

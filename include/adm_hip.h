@@ -35,7 +35,7 @@ extern "C" {
                                9: adm_conv_args gained out_scale; CU-partitioned streams (adm_stream_create_cumask / _set_cus / _destroy);
                                10: the evaluation suite's k-NN entry points (adm_knn_smallest / adm_knn_cover);
                                still 10 (additive, nothing existing changed): the VAE decoder's adm_attention_1h512 / adm_vae_latent_in / adm_vae_image_out
-                               and the KID sums adm_poly3_sums / adm_poly3_work_elems */
+                               and the KID sums adm_poly3_sums / adm_poly3_work_elems; the CMMD sums adm_rbf_sums / adm_rbf_work_elems */
 
 #define ADM_E_ARG      (-1)  /* bad pointer / size / flag combination          */
 #define ADM_E_SHAPE    (-2)  /* shape not supported by the gfx950 tiling       */
@@ -512,6 +512,25 @@ int adm_layernorm_f32out(const adm_bf16* x, const float* gamma, const float* bet
 int64_t adm_poly3_work_elems(int64_t n, int64_t m, int self_pairs);
 int adm_poly3_sums(const float* x, int64_t n, const float* y, int64_t m, int d, double* work, int64_t work_elems, double* out,
                    void* stream, int self_pairs);
+
+/* ---------------------------------------------------------------- CMMD (K18: the Gaussian RBF kernel sums on CLIP embeddings)
+ * Still ABI 10 (additive).  Project-defined (the reference has no CMMD; after Jayasumana et al., "Rethinking FID", CVPR 2024):
+ * over fp32 rows x [n][d], y [m][d] (NOT normalised; d % 4 == 0, 16-byte aligned; fp32 in both builds of the library), all in f64,
+ *   r_i = |x_i|^2, s_j = |y_j|^2, c_ij = x_i . y_j / sqrt(r_i s_j), D_ij = max(2 - 2 c_ij, 0), kappa_ij = expm1(-gamma D_ij)
+ *   self_pairs = 0:  out[0] = sum_i sum_j kappa_ij
+ *   self_pairs = 1:  out[0] = sum_{i != j} kappa_ij   (y == x or NULL, m == n; the diagonal is skipped by index)
+ * kappa = k - 1 <= 0 for the kernel k = exp(-gamma |a - b|^2) on unit vectors: the ones cancel in the estimator, not in the sum.
+ * Three launches: the row norms (one wave per row), the 64 x 64 f64 matrix-core Gram tiles with the normalisation, expm1 and the
+ * reduction in their epilogue (the n x m matrix never exists), and a single-block pass over the per-block partials -- no atomics,
+ * two calls on the same inputs are bitwise equal.  `work` (f64) holds at least adm_rbf_work_elems(n, m, self_pairs) = blocks + n + m
+ * elements (-1 for a shape it refuses; nothing is allocated): the partials, then r[n], then s[m], which the caller may read (a row
+ * of norm 0 makes out[0] NaN).  Only out[0] and those elements of work are written.  Refused before any launch: null pointers,
+ * misalignment, n or m < 1, d < 4 or d % 4 != 0, gamma not finite or <= 0, a workspace that is too small, self_pairs with m != n or
+ * y != x.  THE STREAM IS THE SECOND-TO-LAST ARGUMENT and the integer mode the last, as for adm_poly3_sums: the per-element float64
+ * check lives in tests/test_hip_cmmd.py.                                                                                        */
+int64_t adm_rbf_work_elems(int64_t n, int64_t m, int self_pairs);
+int adm_rbf_sums(const float* x, int64_t n, const float* y, int64_t m, int d, double gamma, double* work, int64_t work_elems,
+                 double* out, void* stream, int self_pairs);
 
 /* ---------------------------------------------------------------- DPM-Solver on the pixel (ADM) path (K17)
  * Still ABI 10 (additive).  Reference: ldm/models/diffusion/dpm_solver/dpm_solver.py -- model_wrapper's classifier guidance

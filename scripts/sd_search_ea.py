@@ -19,7 +19,12 @@ CLIP's start- and end-of-text).  FID: ``--inception_path`` is the pytorch_fid ch
 take the reference's ``.npy`` pair; ``--ref_mu`` alone may name an ``.npz`` holding ``mu`` and ``sigma`` (what
 ``scripts/evaluator.py --save_ref_stats`` writes).  ``--fitness kid --ref_feats FILE.npz`` ranks candidates by 1000 x the unbiased
 cubic-kernel MMD^2 (KID, autodiffusion_amd/kid.py) against the rows ``feats`` of FILE.npz (``scripts/evaluator.py --save_ref_feats``)
-instead; the fitness lines then carry "[fitness: KID x 1e3]" and ``--ref_mu`` / ``--ref_sigma`` are not read.  ``--torso {bf16,fp16}`` selects the 16-bit torso; ``--population_parallel``
+instead; the fitness lines then carry "[fitness: KID x 1e3]" and ``--ref_mu`` / ``--ref_sigma`` are not read.
+``--fitness cmmd --ref_clip_feats FILE.npz --clip_ckpt CLIP.pt`` ranks them by 1000 x the unbiased RBF-kernel MMD^2 of their CLIP
+image embeddings (CMMD, autodiffusion_amd/cmmd.py) against the rows ``clip_feats`` of FILE.npz (``scripts/sd_clip_score.py
+--save_clip_feats``); the lines carry "[fitness: CMMD x 1e3 (unbiased)]", no Inception network is built, and ``--ref_mu`` /
+``--ref_sigma`` / ``--inception_path`` are not read; without ``--population_parallel`` the batches of a candidate are sharded over
+the ranks and the embedding rows pooled.  ``--torso {bf16,fp16}`` selects the 16-bit torso; ``--population_parallel``
 shards whole candidates over ranks (candidate i on rank i % world, one all_gather of the FIDs per epoch).
 ``--clip_ckpt PATH`` also scores every candidate's images against their prompts (``sd_clip.CLIPScorer``, a ``CLIP score:`` log line
 per candidate; the fitness stays the FID): PATH is ONE plain state dict holding both CLIP towers, in transformers' ``CLIPModel``
@@ -49,8 +54,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from autodiffusion_amd import dist_util, logger  # noqa: E402
 from autodiffusion_amd.script_util import str2bool  # noqa: E402
 from autodiffusion_amd.sd_script_util import (TINY_CLIP, TINY_UNET, TINY_VAE, EmptyPromptTokenizer, build_clip_scorer,  # noqa: E402,F401
-                                              build_inception, build_model, build_sampler, read_captions, read_prompt_ids, require_gpu,
-                                              seed_everything)
+                                              build_inception, build_model, build_sampler, read_captions, read_prompt_ids, require_cmmd_flags,
+                                              require_gpu, seed_everything)
 from autodiffusion_amd.sd_search import EvolutionSearcher, dpm_search_params, parse_sd_candidate  # noqa: E402
 
 IGNORED = ("precision", "laion400m", "skip_grid", "skip_save", "n_iter", "n_rows", "prompt", "ddim_steps", "cal_fid", "data_dir")
@@ -86,10 +91,14 @@ def create_argparser():
     p.add_argument("--thres", type=float, default=0.2)
     p.add_argument("--ref_mu", type=str, default="", help="reference mean (.npy), or an .npz holding mu and sigma")
     p.add_argument("--ref_sigma", type=str, default="", help="reference covariance (.npy)")
-    p.add_argument("--fitness", default="fid", choices=["fid", "kid"],
-                   help="what ranks a candidate: the Frechet distance, or 1000 x the unbiased cubic-kernel MMD^2 (autodiffusion_amd/kid.py)")
+    p.add_argument("--fitness", default="fid", choices=["fid", "kid", "cmmd"],
+                   help="what ranks a candidate: the Frechet distance, 1000 x the unbiased cubic-kernel MMD^2 (autodiffusion_amd/kid.py), "
+                        "or 1000 x the unbiased RBF-kernel MMD^2 of the CLIP image embeddings (autodiffusion_amd/cmmd.py)")
     p.add_argument("--ref_feats", type=str, default="",
                    help="--fitness kid: .npz with `feats` fp32 [m, 2048] (scripts/evaluator.py --save_ref_feats)")
+    # absent from the namespace unless given: log.txt's argument line of every other run stays what it was
+    p.add_argument("--ref_clip_feats", type=str, default=argparse.SUPPRESS,
+                   help="--fitness cmmd: .npz with `clip_feats` fp32 [m, E] (scripts/sd_clip_score.py --save_clip_feats)")
     p.add_argument("--time_step", type=int, default=50)
     p.add_argument("--use_ddim_init_x", type=str2bool, default=False,
                    help="seed the population with the evenly spaced schedule; parsed as a boolean word (true/false/1/0/...): "
@@ -163,6 +172,9 @@ def main(argv=None, *, evaluator=None):
     fitness, ref_feats = opt.fitness, opt.ref_feats
     if fitness == "kid" and not ref_feats:
         raise SystemExit("sd_search_ea.py: --fitness kid needs --ref_feats FILE.npz (scripts/evaluator.py --save_ref_feats writes it)")
+    ref_clip_feats = getattr(opt, "ref_clip_feats", "")
+    if fitness == "cmmd":
+        require_cmmd_flags(opt, "sd_search_ea.py")
     if fitness == "fid" and not ref_feats:
         # the defaults leave no trace: log.txt's argument line (str(opt) below) stays what it was before the two flags existed
         del opt.fitness, opt.ref_feats
@@ -184,7 +196,7 @@ def main(argv=None, *, evaluator=None):
         ids = loader[0]["text"]
         model = build_model(opt, device, prompt_len=ids.shape[1] if torch.is_tensor(ids) else None)
         sampler = build_sampler(opt, model)
-        inception = build_inception(opt, device)
+        inception = build_inception(opt, device) if fitness != "cmmd" else None
         if opt.clip_ckpt:
             clip_scorer = build_clip_scorer(opt, device, prompt_len=ids.shape[1] if torch.is_tensor(ids) else None)
         alphas_cumprod = model.alphas_cumprod
@@ -199,7 +211,7 @@ def main(argv=None, *, evaluator=None):
                                  dataloader_info={"validation_loader": loader}, batch_size=opt.n_samples, dpm_params=dpm_params,
                                  evaluator=evaluator, population_parallel=opt.population_parallel, inception=inception,
                                  allow_random_inception=opt.allow_random_inception, clip_scorer=clip_scorer, fitness=fitness,
-                                 ref_feats=ref_feats or None)
+                                 ref_feats=ref_feats or None, ref_clip_feats=ref_clip_feats or None)
     if opt.evaluate:
         cand = parse_sd_candidate(opt.evaluate, "--evaluate")
         want = opt.time_step + (1 if opt.dpm_solver else 0)
