@@ -67,6 +67,21 @@ class PixDpmArgs(C.Structure):
                 + [(k, C.c_float) for k in ("alpha_s", "sigma_s", "a", "b0", "b1", "b2", "q", "max_val")])
 
 
+class PixUnipcArgs(C.Structure):
+    """struct adm_pix_unipc_args (include/adm_hip.h)."""
+    _fields_ = ([(k, C.c_void_p) for k in ("x_eval", "model_out", "grad", "x_base", "h1", "h2", "h3", "m_out", "x_corr", "x_pred",
+                                           "u8_nhwc", "s_out", "work")] + [("work_bytes", C.c_int64)]
+                + [(k, C.c_int32) for k in ("n", "c", "h", "w", "model_channels", "start_x", "predict_x0", "thresholding")]
+                + [(k, C.c_float) for k in ("alpha_s", "sigma_s", "ac", "c0", "c1", "c2", "c3", "ap", "p0", "p1", "p2", "q", "max_val")])
+
+
+class UnipcArgs(C.Structure):
+    """struct adm_unipc_args (include/adm_hip.h)."""
+    _fields_ = ([(k, C.c_void_p) for k in ("x_eval", "eps_uncond", "eps_cond", "x_base", "h1", "h2", "h3", "m_out", "x_corr",
+                                           "x_pred")] + [("numel", C.c_int64)]
+                + [(k, C.c_float) for k in ("cfg_scale", "sigma_s", "alpha_s", "ac", "c0", "c1", "c2", "c3", "ap", "p0", "p1", "p2")])
+
+
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 
 # name -> (restype, argtypes); every symbol declared in include/adm_hip.h
@@ -143,6 +158,8 @@ SIGNATURES = {
     "adm_abs_quantile_work_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "adm_abs_quantile": (_I, [_P, C.c_int64, C.c_int64, _F, _P, C.c_int64, _P, _P, _I]),
     "adm_pix_dpm_step": (_I, [C.POINTER(PixDpmArgs), _P, _I]),
+    "adm_pix_unipc_step": (_I, [C.POINTER(PixUnipcArgs), _P, _I]),
+    "adm_unipc_step": (_I, [C.POINTER(UnipcArgs), _P, _I]),
 }
 
 _libs = {}

@@ -2,7 +2,11 @@
 // dynamic thresholding (reference ldm/models/diffusion/dpm_solver/dpm_solver.py: model_wrapper :289-335, data_prediction_fn
 // :386-399, the multistep updates :504-549, :755-857).
 //
-// Two kernels.
+// Three kernels.
+//   * unipc_step_kernel: the same walk and the same model value for UniPC (Zhao et al. 2023; autodiffusion_amd/unipc.py): one
+//     evaluation yields two states, x_c = ac x_base + c0 m + c1 h1 + c2 h2 + c3 h3 (the corrector of the update that arrived
+//     here, m being the value it was waiting for) and x_pred = ap x_c + p0 m + p1 h1 + p2 h2 (the predictor of the next
+//     update), so m -- and with thresholding the per-image selection -- is computed once per evaluation.
 //   * dpm_step_kernel: one thread owns VEC consecutive pixels of one image and walks the C channels, as step_kernel does
 //     (adm_sampler.hip).  eps (the first C of C or 2C model channels, or derived from a START_X output), the guidance term,
 //     the model value m (eps, or x0 = (x - sigma eps) / alpha, thresholded), x_next = a x_base + b0 m + b1 h1 + b2 h2 with
@@ -109,6 +113,99 @@ dpm_step_kernel(const float* __restrict__ x, const float* __restrict__ mo, const
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
           float q = (outv[j] + 1.0f) * 127.5f;
+          q = fminf(fmaxf(q, 0.0f), 255.0f);
+          u8[((long long)img * hw + p + j) * c + ch] = (uint8_t)q;  // truncation, as .to(uint8)
+        }
+      }
+    }
+  }
+}
+
+struct UniK {
+  DpmK d;   // the model value's scalars and flags (a, b0 .. b2 unused)
+  float ac, c0, c1, c2, c3, ap, p0, p1, p2;
+};
+
+// UniPC: m as dpm_step_kernel computes it, then the corrected point of this evaluation and the predicted point of the next.
+// Which of the two states is wanted is a template parameter: as run-time conditions beside the optional operands' the twelve
+// pointers and twenty scalars no longer fit the scalar registers (each hoisted condition holds a 64-bit lane mask).
+template <int VEC, bool CORR, bool PRED>
+__global__ void __launch_bounds__(256)
+unipc_step_kernel(const float* __restrict__ x, const float* __restrict__ mo, const float* __restrict__ grad,
+                  const float* __restrict__ xb, const float* __restrict__ h1, const float* __restrict__ h2,
+                  const float* __restrict__ h3, const float* __restrict__ s_in, float* __restrict__ m_out,
+                  float* __restrict__ x_corr, float* __restrict__ x_pred, uint8_t* __restrict__ u8, int n, int c, int hw,
+                  UniK k) {
+#pragma clang fp contract(off)
+  constexpr bool states = CORR || PRED;
+  const unsigned hwv = (unsigned)(hw / VEC);
+  const unsigned long long groups = (unsigned long long)n * hwv;
+  // the block's first group is split by one 64-bit division, a thread's own by a 32-bit one (its offset is below 256 + hwv)
+  for (unsigned long long g0 = (unsigned long long)blockIdx.x * 256u; g0 < groups; g0 += (unsigned long long)gridDim.x * 256u) {
+    if (g0 + threadIdx.x >= groups) break;
+    const unsigned local = (unsigned)(g0 % hwv) + threadIdx.x;
+    const int img = (int)(g0 / hwv) + (int)(local / hwv);
+    const int p = (int)(local % hwv) * VEC;
+    const float s = k.d.thresholding ? s_in[img] : 1.0f;
+    for (int ch = 0; ch < c; ++ch) {
+      const long long xi = ((long long)img * c + ch) * hw + p;
+      const long long mi = ((long long)img * k.d.mo_c + ch) * hw + p;
+      float xv[VEC], ov[VEC], gv[VEC], bv[VEC], h1v[VEC], h2v[VEC], h3v[VEC], mv[VEC], cv[VEC], pv[VEC];
+      if constexpr (VEC == 4) {
+        *reinterpret_cast<float4*>(xv) = *reinterpret_cast<const float4*>(x + xi);
+        *reinterpret_cast<float4*>(ov) = *reinterpret_cast<const float4*>(mo + mi);
+        if (grad) *reinterpret_cast<float4*>(gv) = *reinterpret_cast<const float4*>(grad + xi);
+        if constexpr (CORR) *reinterpret_cast<float4*>(bv) = *reinterpret_cast<const float4*>(xb + xi);
+        if constexpr (states) {
+          if (h1) *reinterpret_cast<float4*>(h1v) = *reinterpret_cast<const float4*>(h1 + xi);
+          if (h2) *reinterpret_cast<float4*>(h2v) = *reinterpret_cast<const float4*>(h2 + xi);
+          if (CORR && h3) *reinterpret_cast<float4*>(h3v) = *reinterpret_cast<const float4*>(h3 + xi);
+        }
+      } else {
+        xv[0] = x[xi];
+        ov[0] = mo[mi];
+        if (grad) gv[0] = grad[xi];
+        if constexpr (CORR) bv[0] = xb[xi];
+        if constexpr (states) {
+          if (h1) h1v[0] = h1[xi];
+          if (h2) h2v[0] = h2[xi];
+          if (CORR && h3) h3v[0] = h3[xi];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        float m = dpm_model_value(xv[j], ov[j], grad ? gv[j] : 0.0f, grad != nullptr, k.d);
+        if (k.d.thresholding) m = fminf(fmaxf(m, -s), s) / s;
+        mv[j] = m;
+        float xc = xv[j];
+        if constexpr (CORR) {
+          xc = k.ac * bv[j] + k.c0 * m;
+          if (h1) xc = xc + k.c1 * h1v[j];
+          if (h2) xc = xc + k.c2 * h2v[j];
+          if (h3) xc = xc + k.c3 * h3v[j];
+        }
+        cv[j] = xc;
+        float xp = CORR ? xc : m;   // what the pack holds where x_pred is NULL
+        if constexpr (PRED) {
+          xp = k.ap * xc + k.p0 * m;
+          if (h1) xp = xp + k.p1 * h1v[j];
+          if (h2) xp = xp + k.p2 * h2v[j];
+        }
+        pv[j] = xp;
+      }
+      if constexpr (VEC == 4) {
+        *reinterpret_cast<float4*>(m_out + xi) = *reinterpret_cast<float4*>(mv);
+        if constexpr (CORR) *reinterpret_cast<float4*>(x_corr + xi) = *reinterpret_cast<float4*>(cv);
+        if constexpr (PRED) *reinterpret_cast<float4*>(x_pred + xi) = *reinterpret_cast<float4*>(pv);
+      } else {
+        m_out[xi] = mv[0];
+        if constexpr (CORR) x_corr[xi] = cv[0];
+        if constexpr (PRED) x_pred[xi] = pv[0];
+      }
+      if (u8) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          float q = (pv[j] + 1.0f) * 127.5f;
           q = fminf(fmaxf(q, 0.0f), 255.0f);
           u8[((long long)img * hw + p + j) * c + ch] = (uint8_t)q;  // truncation, as .to(uint8)
         }
@@ -322,4 +419,78 @@ extern "C" int adm_pix_dpm_step(const adm_pix_dpm_args* a, void* stream, int fla
   if (vec4) LAUNCH(4); else LAUNCH(1);
 #undef LAUNCH
   return adm_check_launch("adm_pix_dpm_step");
+}
+
+extern "C" int adm_pix_unipc_step(const adm_pix_unipc_args* a, void* stream, int flags) {
+  ADM_REQUIRE(flags == 0, ADM_E_ARG, "adm_pix_unipc_step: flags=%d (must be 0)", flags);
+  ADM_REQUIRE(a, ADM_E_ARG, "adm_pix_unipc_step: null argument block");
+  ADM_REQUIRE(a->x_eval && a->model_out && a->m_out, ADM_E_ARG, "adm_pix_unipc_step: null x_eval / model_out / m_out");
+  ADM_REQUIRE(!a->x_corr || a->x_base, ADM_E_ARG, "adm_pix_unipc_step: x_corr without x_base");
+  ADM_REQUIRE(a->n > 0 && a->c > 0 && a->h > 0 && a->w > 0, ADM_E_ARG, "adm_pix_unipc_step: bad shape %d %d %d %d", a->n, a->c, a->h, a->w);
+  ADM_REQUIRE(a->model_channels == a->c || a->model_channels == 2LL * a->c, ADM_E_ARG,
+              "adm_pix_unipc_step: model_out has %d channels, neither C = %d nor 2C", a->model_channels, a->c);
+  ADM_REQUIRE(!a->thresholding || a->predict_x0, ADM_E_ARG, "adm_pix_unipc_step: thresholding needs predict_x0");
+  long long hw, per, mo_per, total;
+  ADM_REQUIRE(!__builtin_mul_overflow((long long)a->h, (long long)a->w, &hw) && hw <= 0x7fffffffLL &&
+                  !__builtin_mul_overflow(hw, (long long)a->model_channels, &mo_per) && mo_per <= 0x7fffffffLL &&
+                  dpm_sizes(a->n, mo_per, &total),
+              ADM_E_ARG, "adm_pix_unipc_step: the sizes %d x %d x %d x %d overflow", a->n, a->model_channels, a->h, a->w);
+  per = hw * a->c;
+  float* s_work = nullptr;
+  uint32_t k_lo = 0, k_hi = 0;
+  float wq = 0.0f;
+  if (a->thresholding) {
+    ADM_REQUIRE(a->q > 0.0f && a->q < 1.0f, ADM_E_ARG, "adm_pix_unipc_step: q=%g is outside (0, 1)", (double)a->q);
+    ADM_REQUIRE(a->max_val > 0.0f, ADM_E_ARG, "adm_pix_unipc_step: max_val=%g must be positive", (double)a->max_val);
+    const long long need = work_bytes(a->n, per);
+    ADM_REQUIRE(a->work, ADM_E_ARG, "adm_pix_unipc_step: thresholding needs a work buffer");
+    ADM_REQUIRE(a->work_bytes >= need, ADM_E_ARG, "adm_pix_unipc_step: work holds %lld bytes, adm_abs_quantile_work_bytes says %lld",
+                (long long)a->work_bytes, need);
+    ADM_REQUIRE(adm_aligned16(a->work), ADM_E_ALIGN, "adm_pix_unipc_step: work must be 16-byte aligned");
+    s_work = static_cast<float*>(a->work);
+    rank_of(a->q, per, &k_lo, &k_hi, &wq);
+  }
+  UniK k{};
+  k.d.alpha = a->alpha_s;
+  k.d.sigma = a->sigma_s;
+  k.d.max_val = a->max_val;
+  k.d.start_x = a->start_x != 0;
+  k.d.predict_x0 = a->predict_x0 != 0;
+  k.d.thresholding = a->thresholding != 0;
+  k.d.mo_c = a->model_channels;
+  k.ac = a->ac;
+  k.c0 = a->c0;
+  k.c1 = a->c1;
+  k.c2 = a->c2;
+  k.c3 = a->c3;
+  k.ap = a->ap;
+  k.p0 = a->p0;
+  k.p1 = a->p1;
+  k.p2 = a->p2;
+  hipStream_t s = (hipStream_t)stream;
+  if (a->thresholding) {   // the selection launch of adm_pix_dpm_step: the same keys from the same function
+    uint32_t* stash = reinterpret_cast<uint32_t*>(static_cast<char*>(a->work) + ((long long)a->n * 4 + 15) / 16 * 16);
+    hipLaunchKernelGGL((select_kernel<true>), dim3((unsigned)a->n), dim3(QT), 0, s, (const float*)nullptr, a->x_eval, a->model_out,
+                       a->grad, stash, (int)per, (int)mo_per, k_lo, k_hi, wq, k.d, s_work, a->s_out);
+  }
+  const bool states = a->x_corr || a->x_pred;
+  const bool vec4 = (hw % 4 == 0) && adm_aligned16(a->x_eval) && adm_aligned16(a->model_out) && adm_aligned16(a->m_out) &&
+                    (!a->grad || adm_aligned16(a->grad)) && (!a->x_corr || (adm_aligned16(a->x_corr) && adm_aligned16(a->x_base))) &&
+                    (!a->x_pred || adm_aligned16(a->x_pred)) &&
+                    (!states || ((!a->h1 || adm_aligned16(a->h1)) && (!a->h2 || adm_aligned16(a->h2)) &&
+                                 (!a->h3 || adm_aligned16(a->h3))));
+  const long long groups = (long long)a->n * (vec4 ? hw / 4 : hw);
+  int blocks = (int)((groups + 255) / 256 > 4096 ? 4096 : (groups + 255) / 256);
+#define LAUNCH(V, CO, PR)                                                                                                       \
+  hipLaunchKernelGGL((unipc_step_kernel<V, CO, PR>), dim3(blocks), dim3(256), 0, s, a->x_eval, a->model_out, a->grad, a->x_base, a->h1, \
+                     a->h2, a->h3, (const float*)s_work, a->m_out, a->x_corr, a->x_pred, a->u8_nhwc, a->n, a->c, (int)hw, k)
+#define PICK(V)                                          \
+  if (a->x_corr && a->x_pred) LAUNCH(V, true, true);       \
+  else if (a->x_corr) LAUNCH(V, true, false);              \
+  else if (a->x_pred) LAUNCH(V, false, true);              \
+  else LAUNCH(V, false, false)
+  if (vec4) { PICK(4); } else { PICK(1); }
+#undef PICK
+#undef LAUNCH
+  return adm_check_launch("adm_pix_unipc_step");
 }

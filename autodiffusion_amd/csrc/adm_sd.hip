@@ -216,3 +216,104 @@ extern "C" int adm_dpm_step(const float* x, const float* eps_uncond, const float
   hipLaunchKernelGGL(dpm_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
   return adm_check_launch("adm_dpm_step");
 }
+
+// ------------------------------------------------------------------------------------------------
+// One model evaluation of UniPC (Zhao et al. 2023; autodiffusion_amd/unipc.py) in data-prediction form on the
+// latents: adm_dpm_step's guided model value, then two states from host float64 coefficients,
+//   e = eu ? eu + cfg*(ec - eu) : ec;   m = (x_eval - sigma_s*e) / alpha_s
+//   x_c    = x_corr ? ac*x_base + c0*m + c1*h1 + c2*h2 + c3*h3 : x_eval     (the corrector of the update that arrived at x_eval)
+//   x_pred = ap*x_c + p0*m + p1*h1 + p2*h2                                  (the predictor of the next update)
+// fp32, left to right, no contraction: tests/unipc_ref.py restates exactly this sequence.  8-11 streams in one pass; two
+// adm_dpm_step launches for the same two states would read x_eval, eps and the history twice.
+namespace {
+struct UniStep {
+  const float* x; const float* eu; const float* ec; const float* xb; const float* h1; const float* h2; const float* h3;
+  float* m_out; float* x_corr; float* x_pred;
+  long long numel;
+  float cfg, sigma_s, alpha_s, ac, c0, c1, c2, c3, ap, p0, p1, p2;
+};
+
+template <int VEC>
+__global__ void __launch_bounds__(256)
+unipc_step_kernel(const UniStep p) {
+#pragma clang fp contract(off)
+  const long long groups = p.numel / VEC;
+  const bool states = p.x_corr || p.x_pred;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+    const long long i = g * VEC;
+    float xv[VEC], cv[VEC], uv[VEC], bv[VEC], h1v[VEC], h2v[VEC], h3v[VEC], mv[VEC], xcv[VEC], xpv[VEC];
+    if constexpr (VEC == 4) {
+      *reinterpret_cast<float4*>(xv) = *reinterpret_cast<const float4*>(p.x + i);
+      *reinterpret_cast<float4*>(cv) = *reinterpret_cast<const float4*>(p.ec + i);
+      if (p.eu) *reinterpret_cast<float4*>(uv) = *reinterpret_cast<const float4*>(p.eu + i);
+      if (p.x_corr) *reinterpret_cast<float4*>(bv) = *reinterpret_cast<const float4*>(p.xb + i);
+      if (states) {
+        if (p.h1) *reinterpret_cast<float4*>(h1v) = *reinterpret_cast<const float4*>(p.h1 + i);
+        if (p.h2) *reinterpret_cast<float4*>(h2v) = *reinterpret_cast<const float4*>(p.h2 + i);
+        if (p.h3 && p.x_corr) *reinterpret_cast<float4*>(h3v) = *reinterpret_cast<const float4*>(p.h3 + i);
+      }
+    } else {
+      xv[0] = p.x[i];
+      cv[0] = p.ec[i];
+      if (p.eu) uv[0] = p.eu[i];
+      if (p.x_corr) bv[0] = p.xb[i];
+      if (states) {
+        if (p.h1) h1v[0] = p.h1[i];
+        if (p.h2) h2v[0] = p.h2[i];
+        if (p.h3 && p.x_corr) h3v[0] = p.h3[i];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      float e = cv[j];
+      if (p.eu) e = uv[j] + p.cfg * (e - uv[j]);
+      const float m = (xv[j] - p.sigma_s * e) / p.alpha_s;
+      mv[j] = m;
+      float xc = xv[j];
+      if (p.x_corr) {
+        xc = p.ac * bv[j] + p.c0 * m;
+        if (p.h1) xc = xc + p.c1 * h1v[j];
+        if (p.h2) xc = xc + p.c2 * h2v[j];
+        if (p.h3) xc = xc + p.c3 * h3v[j];
+      }
+      xcv[j] = xc;
+      float xp = p.ap * xc + p.p0 * m;
+      if (p.h1) xp = xp + p.p1 * h1v[j];
+      if (p.h2) xp = xp + p.p2 * h2v[j];
+      xpv[j] = xp;
+    }
+    if constexpr (VEC == 4) {
+      *reinterpret_cast<float4*>(p.m_out + i) = *reinterpret_cast<float4*>(mv);
+      if (p.x_corr) *reinterpret_cast<float4*>(p.x_corr + i) = *reinterpret_cast<float4*>(xcv);
+      if (p.x_pred) *reinterpret_cast<float4*>(p.x_pred + i) = *reinterpret_cast<float4*>(xpv);
+    } else {
+      p.m_out[i] = mv[0];
+      if (p.x_corr) p.x_corr[i] = xcv[0];
+      if (p.x_pred) p.x_pred[i] = xpv[0];
+    }
+  }
+}
+}  // namespace
+
+extern "C" int adm_unipc_step(const adm_unipc_args* a, void* stream, int flags) {
+  ADM_REQUIRE(flags == 0, ADM_E_ARG, "adm_unipc_step: flags=%d (must be 0)", flags);
+  ADM_REQUIRE(a, ADM_E_ARG, "adm_unipc_step: null argument block");
+  ADM_REQUIRE(a->x_eval && a->eps_cond && a->m_out, ADM_E_ARG, "adm_unipc_step: null x_eval / eps_cond / m_out");
+  ADM_REQUIRE(!a->x_corr || a->x_base, ADM_E_ARG, "adm_unipc_step: x_corr without x_base");
+  ADM_REQUIRE(a->numel > 0 && a->numel <= (1LL << 60) && a->alpha_s > 0.f, ADM_E_ARG, "adm_unipc_step: numel=%lld or alpha_s <= 0",
+              (long long)a->numel);
+  UniStep p{a->x_eval, a->eps_uncond, a->eps_cond, a->x_base, a->h1, a->h2, a->h3, a->m_out, a->x_corr, a->x_pred,
+            (long long)a->numel, a->cfg_scale, a->sigma_s, a->alpha_s, a->ac, a->c0, a->c1, a->c2, a->c3, a->ap, a->p0, a->p1, a->p2};
+  const bool states = a->x_corr || a->x_pred;
+  const bool vec4 = (a->numel % 4 == 0) && adm_aligned16(a->x_eval) && adm_aligned16(a->eps_cond) && adm_aligned16(a->m_out) &&
+                    (!a->eps_uncond || adm_aligned16(a->eps_uncond)) &&
+                    (!a->x_corr || (adm_aligned16(a->x_corr) && adm_aligned16(a->x_base))) && (!a->x_pred || adm_aligned16(a->x_pred)) &&
+                    (!states || ((!a->h1 || adm_aligned16(a->h1)) && (!a->h2 || adm_aligned16(a->h2)) &&
+                                 (!a->h3 || adm_aligned16(a->h3))));
+  const long long groups = vec4 ? a->numel / 4 : a->numel;
+  long long blocks = (groups + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  if (vec4) hipLaunchKernelGGL((unipc_step_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL((unipc_step_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+  return adm_check_launch("adm_unipc_step");
+}

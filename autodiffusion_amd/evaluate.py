@@ -125,9 +125,13 @@ class CandidateEvaluator:
     def __init__(self, model, base_diffusion, classifier=None, *, image_size: int, use_ddim: bool = True,
                  clip_denoised: bool = True, class_cond: bool = True, classifier_scale: float = 1.0,
                  device=None, use_graph: bool = False, sampler: Optional[str] = None, dpm_order: int = 2,
-                 dpm_predict_x0: bool = True, dpm_thresholding: bool = False):
-        if sampler not in (None, "dpm_solver"):
-            raise ValueError(f"sampler={sampler!r}: None (use_ddim decides between DDIM and ancestral sampling) or 'dpm_solver'")
+                 dpm_predict_x0: bool = True, dpm_thresholding: bool = False, unipc_order: int = 2, unipc_variant: str = "bh2",
+                 unipc_corrector: bool = True, unipc_predict_x0: bool = True, unipc_thresholding: bool = False):
+        if sampler not in (None, "dpm_solver", "unipc"):
+            raise ValueError(f"sampler={sampler!r}: None (use_ddim decides between DDIM and ancestral sampling), 'dpm_solver' or 'unipc'")
+        # sampler="unipc": the same K evaluations as multistep UniPC (unipc.py): every update but the last arrival corrected
+        self.unipc_order, self.unipc_variant, self.unipc_corrector = int(unipc_order), str(unipc_variant), bool(unipc_corrector)
+        self.unipc_predict_x0, self.unipc_thresholding = bool(unipc_predict_x0), bool(unipc_thresholding)
         # sampler="dpm_solver": the candidate's K timesteps are K evaluations of multistep DPM-Solver (dpm_solver.py), not of DDIM
         self.sampler, self.dpm_order = sampler, int(dpm_order)
         self.dpm_predict_x0, self.dpm_thresholding = bool(dpm_predict_x0), bool(dpm_thresholding)
@@ -200,6 +204,14 @@ class CandidateEvaluator:
             solver = DPMSolver(self.base_diffusion, predict_x0=self.dpm_predict_x0, thresholding=self.dpm_thresholding)
             sample = solver.sample_candidate(self._model_fn, tuple(x_T.shape), noise=x_T, cond_fn=cond_fn, model_kwargs=kwargs,
                                              device=dev, indices=d.timestep_map, order=self.dpm_order)
+            self.last_classes = classes
+            return solver.last_uint8_nhwc, sample
+        if getattr(self, "sampler", None) == "unipc":   # the same candidate mapping and integer timesteps
+            from .unipc import UniPC
+            solver = UniPC(self.base_diffusion, predict_x0=self.unipc_predict_x0, thresholding=self.unipc_thresholding,
+                           variant=self.unipc_variant, corrector=self.unipc_corrector)
+            sample = solver.sample_candidate(self._model_fn, tuple(x_T.shape), noise=x_T, cond_fn=cond_fn, model_kwargs=kwargs,
+                                             device=dev, indices=d.timestep_map, order=self.unipc_order)
             self.last_classes = classes
             return solver.last_uint8_nhwc, sample
         fn = d.ddim_sample_loop if self.use_ddim else d.p_sample_loop

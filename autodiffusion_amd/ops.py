@@ -989,3 +989,39 @@ def pix_dpm_step(x_eval, model_out, grad, x_base, h1, h2, *, alpha_s, sigma_s, a
                                                                   float(b2), float(q), float(max_val))
     check(_lib.load().adm_pix_dpm_step(C.byref(g), _stream(), 0), "adm_pix_dpm_step")
     return m, x_next, u8, s
+
+
+def pix_unipc_step(x_eval, model_out, grad, x_base, h1, h2, h3, *, alpha_s, sigma_s, corr=None, pred=None, start_x=False,
+                   predict_x0=True, thresholding=False, q=0.995, max_val=1.0, want_u8=False, want_s=False, work=None):
+    """One model evaluation of the pixel-space UniPC (adm_pix_unipc_step).  corr = (ac, c0, c1, c2, c3) asks for the corrected
+    point x_c = ac x_base + c0 m + c1 h1 + c2 h2 + c3 h3, pred = (ap, p0, p1, p2) for the predicted point ap x_c + p0 m + p1 h1 +
+    p2 h2 (x_c = x_eval without corr); neither: the denoise evaluation.  -> (m, x_corr | None, x_pred | None, uint8 NHWC | None,
+    s | None)"""
+    n, c, h, w = x_eval.shape
+    if model_out.dim() != 4 or model_out.shape[0] != n or tuple(model_out.shape[2:]) != (h, w):
+        raise AdmError(f"pix_unipc_step: model_out shape {tuple(model_out.shape)} does not belong to x {tuple(x_eval.shape)}")
+    for name, t in (("grad", grad), ("x_base", x_base), ("h1", h1), ("h2", h2), ("h3", h3)):
+        if t is not None and tuple(t.shape) != (n, c, h, w):
+            raise AdmError(f"pix_unipc_step: {name} shape {tuple(t.shape)} != {(n, c, h, w)}")
+    g = _lib.PixUnipcArgs()
+    g.x_eval, g.model_out = _ptr(x_eval, torch.float32, "x_eval"), _ptr(model_out, torch.float32, "model_out")
+    g.grad, g.x_base = _ptr(grad, torch.float32, "grad"), _ptr(x_base, torch.float32, "x_base")
+    g.h1, g.h2, g.h3 = _ptr(h1, torch.float32, "h1"), _ptr(h2, torch.float32, "h2"), _ptr(h3, torch.float32, "h3")
+    m = torch.empty_like(x_eval)
+    x_corr = torch.empty_like(x_eval) if corr is not None else None
+    x_pred = torch.empty_like(x_eval) if pred is not None else None
+    u8 = torch.empty((n, h, w, c), dtype=torch.uint8, device=x_eval.device) if want_u8 else None
+    s = torch.empty(n, dtype=torch.float32, device=x_eval.device) if (want_s and thresholding) else None
+    if thresholding and work is None:
+        work = abs_quantile_work(n, c * h * w, x_eval.device)
+    g.m_out, g.x_corr, g.x_pred, g.u8_nhwc, g.s_out = _ptr(m), _ptr(x_corr), _ptr(x_pred), _ptr(u8), _ptr(s)
+    g.work, g.work_bytes = (_ptr(work), work.numel()) if work is not None else (None, 0)
+    g.n, g.c, g.h, g.w, g.model_channels = n, c, h, w, model_out.shape[1]
+    g.start_x, g.predict_x0, g.thresholding = int(start_x), int(predict_x0), int(thresholding)
+    g.alpha_s, g.sigma_s, g.q, g.max_val = float(alpha_s), float(sigma_s), float(q), float(max_val)
+    if corr is not None:
+        g.ac, g.c0, g.c1, g.c2, g.c3 = (float(v) for v in corr)
+    if pred is not None:
+        g.ap, g.p0, g.p1, g.p2 = (float(v) for v in pred)
+    check(_lib.load().adm_pix_unipc_step(C.byref(g), _stream(), 0), "adm_pix_unipc_step")
+    return m, x_corr, x_pred, u8, s

@@ -261,3 +261,32 @@ def dpm_kwargs(args):
         if hasattr(args, k):
             delattr(args, k)
     return {}
+
+
+UNIPC_FLAGS = ("unipc", "unipc_order", "unipc_variant", "unipc_corrector", "unipc_predict_x0", "unipc_thresholding")
+
+
+def add_unipc_flags(parser):
+    """--unipc True: a candidate's K timesteps are K evaluations of multistep UniPC (autodiffusion_amd/unipc.py): DPM-Solver's
+    candidate mapping, every update but the last arrival corrected with the model value the next update computes anyway."""
+    parser.add_argument("--unipc", type=str2bool, default=False)
+    parser.add_argument("--unipc_order", type=int, default=2, choices=[1, 2, 3])
+    parser.add_argument("--unipc_variant", type=str, default="bh2", choices=["bh1", "bh2"])
+    parser.add_argument("--unipc_corrector", type=str2bool, default=True)
+    parser.add_argument("--unipc_predict_x0", type=str2bool, default=True)
+    parser.add_argument("--unipc_thresholding", type=str2bool, default=False)
+
+
+def unipc_kwargs(args):
+    """The CandidateEvaluator keywords of the flags; with --unipc off the six attributes are removed from `args`, as dpm_kwargs
+    removes its own.  Call it before dpm_kwargs: --unipc together with --dpm_solver is refused while both are still there."""
+    if getattr(args, "unipc", False):
+        if getattr(args, "dpm_solver", False):
+            raise SystemExit("--unipc and --dpm_solver both name the sampler of a candidate: give one of them")
+        return dict(sampler="unipc", unipc_order=args.unipc_order, unipc_variant=args.unipc_variant,
+                    unipc_corrector=args.unipc_corrector, unipc_predict_x0=args.unipc_predict_x0,
+                    unipc_thresholding=args.unipc_thresholding)
+    for k in UNIPC_FLAGS:
+        if hasattr(args, k):
+            delattr(args, k)
+    return {}

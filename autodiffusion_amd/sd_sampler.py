@@ -669,3 +669,100 @@ class DPMSolverSampler(_LatentSampler):
                             ns.marginal_std(s), ns.marginal_alpha(s), a, b0, b1)
             m_prev, lam_prev = m, lam_s
         return x, None
+
+
+# ------------------------------------------------------------------ UniPC
+def unipc_step(x_eval, eps, batch, cfg_scale, x_base, hist, sigma_s, alpha_s, corr=None, pred=None):
+    """One model evaluation of UniPC on the latents (adm_unipc_step): m = the guided data prediction at x_eval; corr = (ac, c0, c1,
+    c2, c3) asks for x_corr = ac x_base + c0 m + c1 h1 + c2 h2 + c3 h3, pred = (ap, p0, p1, p2) for x_pred = ap x_c + p0 m + p1 h1 +
+    p2 h2 with x_c = x_corr (x_eval without corr).  hist: up to three earlier model values, newest first.
+    -> (m, x_corr | None, x_pred | None)"""
+    from ._lib import UnipcArgs
+    guided = eps.shape[0] == 2 * batch
+    if not guided and eps.shape[0] != batch:
+        raise AdmError(f"unipc_step: model output batch {eps.shape[0]} is neither {batch} nor {2 * batch}")
+    eps = eps.contiguous()
+    eu, ec = (eps[:batch], eps[batch:]) if guided else (None, eps)
+    for name, t in [("x_base", x_base)] + [("history", h) for h in hist]:
+        if t is not None and tuple(t.shape) != tuple(x_eval.shape):
+            raise AdmError(f"unipc_step: {name} shape {tuple(t.shape)} != {tuple(x_eval.shape)}")
+    h = list(hist) + [None] * (3 - len(hist))
+    a = UnipcArgs()
+    a.x_eval, a.eps_uncond, a.eps_cond = _f32ptr(x_eval, "x"), _f32ptr(eu, "eps"), _f32ptr(ec, "eps")
+    a.x_base = _f32ptr(x_base, "x_base") if corr is not None else None
+    a.h1, a.h2, a.h3 = (_f32ptr(t, "history") for t in h[:3])
+    m = torch.empty_like(x_eval)
+    x_corr = torch.empty_like(x_eval) if corr is not None else None
+    x_pred = torch.empty_like(x_eval) if pred is not None else None
+    a.m_out = m.data_ptr()
+    a.x_corr = None if x_corr is None else x_corr.data_ptr()
+    a.x_pred = None if x_pred is None else x_pred.data_ptr()
+    a.numel, a.cfg_scale, a.sigma_s, a.alpha_s = x_eval.numel(), float(cfg_scale), float(sigma_s), float(alpha_s)
+    if corr is not None:
+        a.ac, a.c0, a.c1, a.c2, a.c3 = (float(v) for v in corr)
+    if pred is not None:
+        a.ap, a.p0, a.p1, a.p2 = (float(v) for v in pred)
+    check(_lib.load().adm_unipc_step(C.byref(a), torch.cuda.current_stream().cuda_stream, 0), "adm_unipc_step")
+    return m, x_corr, x_pred
+
+
+class UniPCSampler(_LatentSampler):
+    """Multistep UniPC (Zhao et al. 2023; unipc.py) in data-prediction form with ``lower_order_final``, over
+    ``DPMSolverSampler``'s time points and model input: K + 1 searched times (``sampled_timestep``) or the uniform grid, K
+    evaluations, classifier-free guidance.  Evaluation j yields, in one launch, the corrected point at its own time and the
+    predicted point at the next; the arrival point is not corrected.  ``order=2, variant="bh2", corrector=False`` is
+    DPM-Solver++(2M)."""
+
+    def __init__(self, model, order=2, variant="bh2", corrector=True, **kwargs):
+        super().__init__(model, **kwargs)
+        self.alphas_cumprod = model.alphas_cumprod.detach().to(torch.float32)
+        self.order, self.variant, self.corrector = int(order), variant, bool(corrector)
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
+               unconditional_conditioning=None, sampled_timestep=None, order=None, variant=None, corrector=None, record=None,
+               **kwargs):
+        from .unipc import plan_evaluations
+        order = self.order if order is None else int(order)
+        variant = self.variant if variant is None else variant
+        corrector = self.corrector if corrector is None else bool(corrector)
+        if mask is not None or x0 is not None:
+            raise NotImplementedError("UniPCSampler: masked sampling is not built (DDIM / PLMS have it)")
+        if conditioning is not None and not isinstance(conditioning, dict) and conditioning.shape[0] != batch_size:
+            print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+        C_, H, W = shape
+        device, x = self._start((batch_size, C_, H, W), x_T)
+        ns = NoiseScheduleVP('discrete', alphas_cumprod=self.alphas_cumprod)
+        steps = int(S)
+        if sampled_timestep is None:
+            ts = [float(v) for v in np.linspace(ns.T, 1.0 / ns.total_N, steps + 1, dtype=np.float32)]
+        else:
+            ea = [v.item() if hasattr(v, "item") else v for v in sampled_timestep]
+            if max(ea) > 1:
+                full = np.linspace(ns.T, 1.0 / ns.total_N, 1000 + 1, dtype=np.float32)[::-1]
+                ts = [float(full[int(e)]) for e in ea]
+            else:
+                ts = [float(np.float32(t)) for t in sorted(ea, reverse=True)]
+        assert len(ts) - 1 == steps
+        plan = plan_evaluations(ns, ts, order, True, variant, True, corrector)   # float64, raises before anything is launched
+        uc, scale = unconditional_conditioning, unconditional_guidance_scale
+        self._begin(conditioning, uc, scale)
+        hist, x_base = [], None      # model values, newest first; the accepted state at the previous time
+        for j, e in enumerate(plan):
+            t_in = torch.full((batch_size,), (ts[j] - 1.0 / ns.total_N) * 1000.0, device=device, dtype=torch.float32)
+            eps = self._eps(x, t_in)
+            depth = max(e["corr"][2] if e["corr"] else 0, e["pred"][2] - 1)
+            corr = None if e["corr"] is None else (e["corr"][0], *e["corr"][1])
+            pred = (e["pred"][0], *e["pred"][1])
+            m, x_corr, x_pred = unipc_step(x, eps, batch_size, scale, x_base if corr else None, hist[:depth],
+                                           ns.marginal_std(ts[j]), ns.marginal_alpha(ts[j]), corr, pred)
+            if record is not None:
+                record.append(dict(j=j, t=ts[j], x=x, eps=eps, x_base=x_base if corr else None, hist=list(hist[:depth]), corr=corr,
+                                   pred=pred, sigma=ns.marginal_std(ts[j]), alpha=ns.marginal_alpha(ts[j]), m=m, x_corr=x_corr,
+                                   x_pred=x_pred))
+            hist = ([m] + hist)[:3]
+            x_base = x_corr if x_corr is not None else x
+            x = x_pred
+        return x, None

@@ -1,6 +1,7 @@
 """What more than one Stable-Diffusion command line (scripts/sd_*.py) uses: the model builders, the prompt and image loaders, the
 sampling scripts' shared flags and a few helpers -- the latent path's counterpart of script_util.py.  A helper that refuses its input
 raises ``SystemExit`` and takes ``prog``, the running script's name, for the message's prefix."""
+import argparse
 import ast
 import json
 import os
@@ -11,9 +12,10 @@ import torch
 
 from . import dist_util, logger, sd_clip
 from .inception import InceptionV3
+from .script_util import str2bool
 from .sd_arch import SD_V1
 from .sd_clip import CLIP_VIT_L14_TEXT, FrozenCLIPEmbedder
-from .sd_sampler import DDIMSampler, DPMSolverSampler, LatentDiffusion, PLMSSampler
+from .sd_sampler import DDIMSampler, DPMSolverSampler, LatentDiffusion, PLMSSampler, UniPCSampler
 from .sd_unet import UNetModel
 from .sd_vae import SD_V1_VAE, AutoencoderKL
 
@@ -249,7 +251,31 @@ def save_clip_feats(path, rows):
     return path
 
 
+def add_unipc_flags(parser):
+    """--unipc [--unipc_order --unipc_variant --unipc_corrector]: sample with UniPCSampler over DPM-Solver's candidate space.  Absent
+    from the namespace unless given: the argument line of log.txt of every other run stays what it was."""
+    parser.add_argument("--unipc", action="store_true", default=argparse.SUPPRESS, help="use UniPC sampling (sd_sampler.UniPCSampler)")
+    parser.add_argument("--unipc_order", type=int, choices=[1, 2, 3], default=argparse.SUPPRESS, help="UniPC order (2)")
+    parser.add_argument("--unipc_variant", choices=["bh1", "bh2"], default=argparse.SUPPRESS, help="UniPC B(h): bh1 = h, bh2 = e^h - 1 (bh2)")
+    parser.add_argument("--unipc_corrector", type=str2bool, default=argparse.SUPPRESS, help="apply the corrector (true)")
+
+
+def unipc_options(opt, prog):
+    """The UniPCSampler keywords of the flags, or None with --unipc off; --unipc with --dpm_solver / --plms is refused."""
+    if not getattr(opt, "unipc", False):
+        given = [k for k in ("unipc_order", "unipc_variant", "unipc_corrector") if hasattr(opt, k)]
+        if given:
+            raise SystemExit(f"{prog}: --{given[0]} needs --unipc")
+        return None
+    if getattr(opt, "dpm_solver", False) or getattr(opt, "plms", False):
+        raise SystemExit(f"{prog}: --unipc and --dpm_solver / --plms all name the sampler: give one of them")
+    return dict(order=getattr(opt, "unipc_order", 2), variant=getattr(opt, "unipc_variant", "bh2"),
+                corrector=getattr(opt, "unipc_corrector", True))
+
+
 def build_sampler(opt, model):
+    if getattr(opt, "unipc", False):
+        return UniPCSampler(model, **unipc_options(opt, "build_sampler"))
     if opt.dpm_solver:
         return DPMSolverSampler(model)
     if opt.plms:

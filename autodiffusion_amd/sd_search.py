@@ -3,7 +3,7 @@
 Drop-in mirror of ``EvolutionSearcher`` of the reference's "Stable Diffusion"/scripts/search_ea.py:184-633.  Two candidate
 spaces, as there: ``time_step`` integers out of ``range(sampler.ddpm_num_timesteps)`` for the DDIM / PLMS samplers, and
 ``time_step + 1`` continuous times out of ``dpm_params['full_timesteps']`` (the 1001-point uniform grid 1 .. 1/1000) under
-``opt.dpm_solver``.  Every operator consumes ``random`` / ``np.random`` in exactly the reference's order (pinned by
+``opt.dpm_solver`` or ``opt.unipc``.  Every operator consumes ``random`` / ``np.random`` in exactly the reference's order (pinned by
 tests/golden/sd_ea_trajectory.npz, captured from the reference's own driver): candidates are sorted ascending and deduplicated
 by ``str(sorted(cand))`` in ``vis_dict``, cross and mutation try ``10 x num`` times, ``keep_top_k = {select_num: [], 50: []}``,
 the search stops before the last epoch's offspring (:613-614), ``use_ddim_init_x`` seeds the init candidate, ``population_num
@@ -107,10 +107,11 @@ class EvolutionSearcher(object):
         self.vis_dict = {}
         self.max_fid = getattr(opt, "max_fid", 3.0)
         self.use_ddim_init_x = opt.use_ddim_init_x
-        self.dpm_solver = bool(getattr(opt, "dpm_solver", False))
+        # opt.unipc searches the same space: time_step + 1 continuous times, the same operators and draws
+        self.dpm_solver = bool(getattr(opt, "dpm_solver", False) or getattr(opt, "unipc", False))
         self.dpm_params = dpm_params
         if self.dpm_solver and dpm_params is None:
-            raise ValueError("EvolutionSearcher: opt.dpm_solver needs dpm_params (dpm_search_params(alphas_cumprod, time_step))")
+            raise ValueError("EvolutionSearcher: opt.dpm_solver / opt.unipc needs dpm_params (dpm_search_params(alphas_cumprod, time_step))")
         self.ref_mu = np.load(ref_mu) if isinstance(ref_mu, (str, os.PathLike)) else ref_mu
         self.ref_sigma = np.load(ref_sigma) if isinstance(ref_sigma, (str, os.PathLike)) else ref_sigma
         if evaluator is None:

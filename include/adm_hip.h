@@ -577,6 +577,61 @@ int adm_abs_quantile(const float* v, int64_t n, int64_t per, float q, void* work
                      int flags);
 int adm_pix_dpm_step(const adm_pix_dpm_args* args, void* stream, int flags);
 
+/* ---------------------------------------------------------------- UniPC (Zhao et al., NeurIPS 2023) on both paths (K18)
+ * Still ABI 10 (additive).  The reference tree has no UniPC: the algorithm is stated in DESIGN.md section 11.1 and
+ * autodiffusion_amd/unipc.py, whose float64 coefficients these kernels apply.  One model evaluation yields two states:
+ *
+ * adm_pix_unipc_step (fp32 NCHW), with m exactly adm_pix_dpm_step's model value (the same inlined function; with thresholding the
+ * same selection launch first, then one update launch):
+ *   x_c    = x_corr given ? ac x_base + c0 m + c1 h1 + c2 h2 + c3 h3 : x_eval      the corrector of the update that arrived at x_eval
+ *   x_pred = ap x_c + p0 m + p1 h1 + p2 h2                                          the predictor of the next update
+ * fp32, left to right, no contraction; the term of a NULL history pointer is skipped.  Required: x_eval, model_out (C or 2C
+ * channels), m_out; x_base with x_corr.  grad, h1, h2, h3, x_corr, x_pred, u8_nhwc and s_out (written with thresholding only) may be
+ * NULL.  u8_nhwc is the pack of x_pred, of x_corr where x_pred is NULL, of m where both are (the denoise evaluation).  work as for
+ * adm_pix_dpm_step.  Refuses (nonzero, adm_last_error, nothing launched, nothing written) what adm_pix_dpm_step refuses, and x_corr
+ * without x_base.
+ *
+ * adm_unipc_step (fp32, numel elements), the guided data prediction of adm_dpm_step:
+ *   e = eps_uncond ? eps_uncond + cfg_scale (eps_cond - eps_uncond) : eps_cond;   m = (x_eval - sigma_s e) / alpha_s
+ * and the same x_c / x_pred.  Required: x_eval, eps_cond, m_out; x_base with x_corr; numel > 0, alpha_s > 0.
+ * THE STREAM IS THE SECOND-TO-LAST ARGUMENT of both and `flags` (0) the last: their per-element float64 checks live in
+ * tests/test_hip_unipc.py and tests/test_hip_sd_unipc.py.                                                                    */
+typedef struct adm_pix_unipc_args {
+  const float* x_eval;
+  const float* model_out;
+  const float* grad;
+  const float* x_base;
+  const float* h1;
+  const float* h2;
+  const float* h3;
+  float* m_out;
+  float* x_corr;
+  float* x_pred;
+  uint8_t* u8_nhwc;
+  float* s_out;
+  void* work;
+  int64_t work_bytes;
+  int32_t n, c, h, w;
+  int32_t model_channels, start_x, predict_x0, thresholding;
+  float alpha_s, sigma_s, ac, c0, c1, c2, c3, ap, p0, p1, p2, q, max_val;
+} adm_pix_unipc_args;
+typedef struct adm_unipc_args {
+  const float* x_eval;
+  const float* eps_uncond;
+  const float* eps_cond;
+  const float* x_base;
+  const float* h1;
+  const float* h2;
+  const float* h3;
+  float* m_out;
+  float* x_corr;
+  float* x_pred;
+  int64_t numel;
+  float cfg_scale, sigma_s, alpha_s, ac, c0, c1, c2, c3, ap, p0, p1, p2;
+} adm_unipc_args;
+int adm_pix_unipc_step(const adm_pix_unipc_args* args, void* stream, int flags);
+int adm_unipc_step(const adm_unipc_args* args, void* stream, int flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,9 +21,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import dist_util, logger  # noqa: E402
 from autodiffusion_amd.evaluate import CandidateEvaluator, parse_int_list  # noqa: E402
-from autodiffusion_amd.script_util import (add_dict_to_argparser, add_dpm_flags, candidate_from_flags, classifier_defaults,  # noqa: E402
-                                           dpm_kwargs, gather_batches, load_classifier, load_model_and_diffusion,
-                                           model_and_diffusion_defaults)
+from autodiffusion_amd.script_util import (add_dict_to_argparser, add_dpm_flags, add_unipc_flags, candidate_from_flags,  # noqa: E402
+                                           classifier_defaults, dpm_kwargs, gather_batches, load_classifier,
+                                           load_model_and_diffusion, model_and_diffusion_defaults, unipc_kwargs)
 
 
 def create_argparser():
@@ -37,13 +37,14 @@ def create_argparser():
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
     add_dpm_flags(parser)
+    add_unipc_flags(parser)
     return parser
 
 
 def main(argv=None):
     t1 = time.time()
     args = create_argparser().parse_args(argv)
-    dpm = dpm_kwargs(args)
+    dpm = {**unipc_kwargs(args), **dpm_kwargs(args)}   # one of the two at most: unipc_kwargs refuses both
     if args.use_mean and args.use_timestep is not None:   # an averaged schedule, space-separated floats: round it
         args.use_timestep = str(parse_int_list(args.use_timestep, "--use_timestep", use_mean=True))
     os.environ.setdefault("MASTER_PORT", args.MASTER_PORT)

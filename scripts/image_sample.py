@@ -22,8 +22,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import dist_util, logger  # noqa: E402
 from autodiffusion_amd.evaluate import CandidateEvaluator  # noqa: E402
-from autodiffusion_amd.script_util import (add_dict_to_argparser, add_dpm_flags, candidate_from_flags, dpm_kwargs,  # noqa: E402
-                                           gather_batches, load_model_and_diffusion, model_and_diffusion_defaults)
+from autodiffusion_amd.script_util import (add_dict_to_argparser, add_dpm_flags, add_unipc_flags, candidate_from_flags,  # noqa: E402
+                                           dpm_kwargs, gather_batches, load_model_and_diffusion, model_and_diffusion_defaults,
+                                           unipc_kwargs)
 
 
 def create_argparser():
@@ -33,12 +34,13 @@ def create_argparser():
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
     add_dpm_flags(parser)
+    add_unipc_flags(parser)
     return parser
 
 
 def main(argv=None):
     args = create_argparser().parse_args(argv)
-    dpm = dpm_kwargs(args)
+    dpm = {**unipc_kwargs(args), **dpm_kwargs(args)}   # one of the two at most: unipc_kwargs refuses both
     os.environ.setdefault("MASTER_PORT", args.port)
     dist_util.setup_dist()
     logger.configure(args.save_dir or None)

@@ -53,9 +53,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import dist_util, logger  # noqa: E402
 from autodiffusion_amd.script_util import str2bool  # noqa: E402
-from autodiffusion_amd.sd_script_util import (TINY_CLIP, TINY_UNET, TINY_VAE, EmptyPromptTokenizer, build_clip_scorer,  # noqa: E402,F401
-                                              build_inception, build_model, build_sampler, read_captions, read_prompt_ids, require_cmmd_flags,
-                                              require_gpu, seed_everything)
+from autodiffusion_amd.sd_script_util import (TINY_CLIP, TINY_UNET, TINY_VAE, EmptyPromptTokenizer, add_unipc_flags,  # noqa: E402,F401
+                                              build_clip_scorer, build_inception, build_model, build_sampler, read_captions,
+                                              read_prompt_ids, require_cmmd_flags, require_gpu, seed_everything, unipc_options)
 from autodiffusion_amd.sd_search import EvolutionSearcher, dpm_search_params, parse_sd_candidate  # noqa: E402
 
 IGNORED = ("precision", "laion400m", "skip_grid", "skip_save", "n_iter", "n_rows", "prompt", "ddim_steps", "cal_fid", "data_dir")
@@ -129,6 +129,7 @@ def create_argparser():
                    help="a CLIP state dict (both towers, CLIPModel or OpenAI layout): also log every candidate's CLIP score")
     p.add_argument("--evaluate", type=str, default="", help="'[t0, t1, ...]': score this one candidate, print its FID and exit")
     p.add_argument("--synthetic", choices=["tiny", "v1"], default="", help="build the networks with randomize_() instead of reading --ckpt")
+    add_unipc_flags(p)
     return p
 
 
@@ -169,6 +170,8 @@ def main(argv=None, *, evaluator=None):
     """Returns the searcher after a search, or the FID under --evaluate.  ``evaluator=`` injects a candidate evaluator (an
     object with ``get_cand_fid(cand, opt)``) in place of the networks: host tests of the command line."""
     opt = create_argparser().parse_args(argv)
+    unipc = unipc_options(opt, "sd_search_ea.py") is not None   # refuses --unipc beside --dpm_solver / --plms
+    continuous = opt.dpm_solver or unipc                        # a candidate is time_step + 1 continuous times
     fitness, ref_feats = opt.fitness, opt.ref_feats
     if fitness == "kid" and not ref_feats:
         raise SystemExit("sd_search_ea.py: --fitness kid needs --ref_feats FILE.npz (scripts/evaluator.py --save_ref_feats writes it)")
@@ -204,7 +207,7 @@ def main(argv=None, *, evaluator=None):
         loader = []
         sampler = type("Sampler", (), {"ddpm_num_timesteps": 1000})()
         alphas_cumprod = range(1000)
-    if opt.dpm_solver:
+    if continuous:
         dpm_params = dpm_search_params(alphas_cumprod, opt.time_step)
     t = time.time()
     searcher = EvolutionSearcher(opt=opt, model=model, time_step=opt.time_step, ref_mu=ref_mu, ref_sigma=ref_sigma, sampler=sampler,
@@ -214,10 +217,10 @@ def main(argv=None, *, evaluator=None):
                                  ref_feats=ref_feats or None, ref_clip_feats=ref_clip_feats or None)
     if opt.evaluate:
         cand = parse_sd_candidate(opt.evaluate, "--evaluate")
-        want = opt.time_step + (1 if opt.dpm_solver else 0)
+        want = opt.time_step + (1 if continuous else 0)
         if len(cand) != want:
             raise SystemExit(f"sd_search_ea.py: --evaluate holds {len(cand)} entries; --time_step {opt.time_step} "
-                             f"{'with --dpm_solver ' if opt.dpm_solver else ''}needs {want}")
+                             f"{'with --dpm_solver / --unipc ' if continuous else ''}needs {want}")
         fid = searcher.get_cand_fid(cand=cand, opt=opt)
         logger.log('cand: {}, fid: {}'.format(cand, fid) + searcher.fid_note)
         return fid

@@ -43,8 +43,8 @@ from autodiffusion_amd import dist_util, logger  # noqa: E402
 from autodiffusion_amd.schedule import space_timesteps  # noqa: E402
 from autodiffusion_amd.evaluate import batch_plan, graph_auto, parse_int_list  # noqa: E402
 from autodiffusion_amd.script_util import (add_dict_to_argparser, classifier_defaults, load_classifier,  # noqa: E402
-                                           add_dpm_flags, dpm_kwargs, load_model_and_diffusion, model_and_diffusion_defaults,
-                                           str2bool)
+                                           add_dpm_flags, add_unipc_flags, dpm_kwargs, load_model_and_diffusion,
+                                           model_and_diffusion_defaults, str2bool, unipc_kwargs)
 from autodiffusion_amd.search import DynamicEvolutionSearcher, EvolutionSearcher  # noqa: E402
 
 
@@ -65,6 +65,7 @@ def create_argparser():
                         help="what ranks a candidate: the Frechet distance, or 1000 x the unbiased cubic-kernel MMD^2 (autodiffusion_amd/kid.py)")
     parser.add_argument("--ref_feats", default="", help="--fitness kid: .npz with `feats` fp32 [m, 2048] (scripts/evaluator.py --save_ref_feats)")
     add_dpm_flags(parser)
+    add_unipc_flags(parser)
     return parser
 
 
@@ -83,7 +84,7 @@ def build_search_space(args, diffusion):
 
 def main(argv=None):
     args = create_argparser().parse_args(argv)
-    args.dpm = dpm_kwargs(args)
+    args.dpm = {**unipc_kwargs(args), **dpm_kwargs(args)}   # the evaluator's sampler keywords; unipc_kwargs refuses both at once
     if not args.dpm:
         del args.dpm
     if args.fitness == "fid" and not args.ref_feats:
