@@ -32,12 +32,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import ops
-from ._lib import AdmError
-from .kid import pooled_rows  # noqa: F401  (multi-rank pooling of the embedding rows is KID's)
+from . import mmd, ops
+from .mmd import mmd2_from_sums, pooled_rows, reduction_chain  # noqa: F401
+from .mmd import pair_blocks as rbf_blocks  # blocks of adm_rbf_sums's tile pass
 
-TILE = 64            # csrc/adm_cmmd.hip: a block owns one 64 x 64 tile of the Gram
-FINAL_THREADS = 256  # ... and the last pass is one block of 256 threads
 SIGMA = 10.0         # the paper's bandwidth
 SCALE = 1000.0       # the paper's scaling of the reported value; the fitness uses the same
 SAVE_FLAG = "scripts/sd_clip_score.py --save_clip_feats"
@@ -50,24 +48,9 @@ def gamma_of(sigma: float) -> float:
     return 1.0 / (2.0 * sigma * sigma)
 
 
-def rbf_blocks(n: int, m: int, self_pairs: bool) -> int:
-    """Blocks of adm_rbf_sums's tile pass: the tiles of the rectangle, or of the triangle on and above the diagonal."""
-    ti, tj = -(-n // TILE), -(-m // TILE)
-    return ti * (ti + 1) // 2 if self_pairs else ti * tj
-
-
 def work_elems(n: int, m: int, self_pairs: bool) -> int:
     """Workspace doubles of adm_rbf_sums: one partial per block, then the n + m squared norms."""
     return rbf_blocks(n, m, self_pairs) + n + m
-
-
-def reduction_chain(n: int, m: int, self_pairs: bool) -> int:
-    """The longest chain of rounding float64 additions behind adm_rbf_sums's out[0] (the L of the tests' error bound): 16 per lane
-    (2 x 2 MFMA tiles x 4 results), 6 xor shuffles across the wave, 3 across the block's 4 waves, then ceil(blocks / 256) per thread
-    and an 8-level tree in the last pass -- and never more than the number of pairs summed: a masked entry enters as an exact 0.0,
-    and adding zero does not round.  The doubling of a tile above the diagonal is exact."""
-    pairs = n * (n - 1) if self_pairs else n * m
-    return min(16 + 6 + 3 + -(-rbf_blocks(n, m, self_pairs) // FINAL_THREADS) + 8, pairs)
 
 
 def norm_chain(d: int) -> int:
@@ -76,35 +59,17 @@ def norm_chain(d: int) -> int:
     return min(4 * -(-d // 256) + 6, d)
 
 
-def _rows(t, name: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise AdmError(f"{name}: expected fp32 device rows [n, d] (the CMMD kernel has no CPU fallback)")
-    return t.to(torch.float32).contiguous()
-
-
 def rbf_sums(x: torch.Tensor, y: Optional[torch.Tensor] = None, sigma: float = SIGMA) -> float:
     """S_xy of fp32 device rows x [n, d], y [m, d] (not normalised); with y None, S_xx (pairs i != j).  d % 4 == 0.  A row whose
     squared norm is 0 (or not finite) raises ValueError."""
     g = gamma_of(sigma)
-    out, norms = ops.rbf_sums(_rows(x, "x"), None if y is None else _rows(y, "y"), g, return_norms=True)
+    out, norms = ops.rbf_sums(mmd.device_rows(x, "x", "CMMD"), None if y is None else mmd.device_rows(y, "y", "CMMD"), g,
+                              return_norms=True)
     s, lo, hi = torch.stack([out[0], norms.min(), norms.max()]).tolist()
     if not (lo > 0.0 and math.isfinite(hi)):
         raise ValueError(f"CMMD: an embedding row has squared norm {lo if not lo > 0.0 else hi}: a row without a direction cannot be "
                          "normalised")
     return float(s)
-
-
-def mmd2_from_sums(s_xx: float, n: int, s_yy: float, m: int, s_xy: float, unbiased: bool = False) -> float:
-    """MMD^2_v (unbiased False) or MMD^2_u from the three sums of k - 1.  The two self terms are added first, so swapping the sets
-    changes nothing but S_xy's own summation order."""
-    n, m = int(n), int(m)
-    if unbiased:
-        if n < 2 or m < 2:
-            raise ValueError(f"the unbiased MMD^2 needs at least 2 rows in each set (n={n}, m={m})")
-        return (s_xx / (n * (n - 1.0)) + s_yy / (m * (m - 1.0))) - 2.0 * s_xy / (float(n) * m)
-    if n < 1 or m < 1:
-        raise ValueError(f"MMD^2 needs at least 1 row in each set (n={n}, m={m})")
-    return (s_xx / (float(n) * n) + s_yy / (float(m) * m)) - 2.0 * s_xy / (float(n) * m)
 
 
 def _self_sum(x: torch.Tensor, sigma: float) -> float:
@@ -128,29 +93,19 @@ def cmmd(x: torch.Tensor, y: torch.Tensor, sigma: float = SIGMA) -> float:
 
 def load_ref_clip_feats(path: str) -> np.ndarray:
     """The `clip_feats` array (fp32 [m >= 2, d]) of the .npz that scripts/sd_clip_score.py --save_clip_feats writes."""
-    with np.load(path, allow_pickle=False) as z:
-        if "clip_feats" not in z.files:
-            raise KeyError(f"{path}: no array 'clip_feats' (members: {sorted(z.files)}); write it with {SAVE_FLAG}")
-        feats = np.asarray(z["clip_feats"], dtype=np.float32)
-    if feats.ndim != 2 or feats.shape[0] < 2:
-        raise ValueError(f"{path}: clip_feats must be [m >= 2, d], got {feats.shape}")
-    return feats
+    return mmd.load_ref_rows(path, "clip_feats", SAVE_FLAG)
 
 
-class CMMDReference:
+class CMMDReference(mmd.PairSumReference):
     """The reference embeddings on the device with their self sum S_yy, computed once: a candidate then costs two kernel sums."""
 
     def __init__(self, feats, device=None, sigma: float = SIGMA):
-        if isinstance(feats, torch.Tensor) and device is None:
-            device = feats.device
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
         self.sigma = float(sigma)
         gamma_of(self.sigma)
-        self.y = torch.as_tensor(feats).to(device=device, dtype=torch.float32).contiguous()
-        if self.y.dim() != 2 or self.y.shape[0] < 2:
-            raise ValueError(f"CMMDReference: reference rows must be [m >= 2, d], got {tuple(self.y.shape)}")
-        self.s_yy = rbf_sums(self.y, None, self.sigma)
+        super().__init__(feats, device)
+
+    def self_sum(self) -> float:
+        return rbf_sums(self.y, None, self.sigma)
 
     def mmd2(self, rows: torch.Tensor, unbiased: bool = False) -> float:
         return mmd2(rows, self.y, self.sigma, unbiased, s_yy=self.s_yy)

@@ -3,127 +3,28 @@
 //
 //   k(a, b) = (a . b / d + 1)^3        S_xy = sum_i sum_j k(x_i, y_j)        S_xx = sum_{i != j} k(x_i, x_j)
 //
-// One f64 GEMM  G[i][j] = x_i . y_j  on v_mfma_f64_16x16x4_f64 (fp32 rows widened to f64: every product is exact, the
-// accumulation is f64 -- the operand and C/D maps are those of gram_mfma_kernel, adm_fid.hip) with the cube and the sum in its
-// epilogue: the n x m matrix never exists in memory (0.1 .. 2.5 G entries at a 10 000 .. 50 000-row reference set).
-//   * block = one 64 x 64 tile of G, 4 waves of 32 x 32 (2 x 2 MFMA tiles); the feature axis is staged 64 wide through LDS
-//     (pitch 68 floats: 16-byte aligned rows, 17 16-byte units apart, so the 16 rows x 4 segments of a ds_read_b128 spread
-//     over the banks), the next chunk's global loads in flight under the MFMAs.  A lane reads 4 consecutive features at once
-//     and feeds element e to MFMA e: MFMA e of a 16-feature group sums features 16 g + 4 kq + e -- a fixed permutation of
-//     the summation order, the same for both operands.
-//   * epilogue: t = G / d + 1 (a true f64 division), t * t * t, masked BY INDEX: a zero-filled row past n or m would add
-//     k = (0 + 1)^3 = 1, not 0; in self mode i == j is skipped inside diagonal tiles.  Lane sum (16 values, fixed order), wave
-//     sum (6 xor shuffles), block sum (4 waves through LDS, in wave order), one partial per block into work[block].
-//   * self mode computes the tiles on and above the diagonal only; a tile above it counts twice (the partial times 2: exact).
-//   * a second, single-block kernel adds the partials: thread t adds work[t], work[t + 256], ... in index order, then a
-//     fixed 8-level tree.  No floating-point atomics anywhere: two calls on the same inputs are bitwise equal.
+// The f64 Gram  G[i][j] = x_i . y_j,  its 64 x 64 tile loop, the block and final reductions and the workspace are adm_pairsum.h's
+// (shared with K18, adm_cmmd.hip; the tile, the masking rule and the reduction chain are described there).  This file adds
+//   * the epilogue: t = G / d + 1 (a true f64 division), t * t * t, masked BY INDEX: a zero-filled row past n or m would add
+//     k = (0 + 1)^3 = 1, not 0; in self mode i == j is skipped inside diagonal tiles.  Lane sum: 16 values in the order ti, tj, q.
 // Longest chain of additions behind out[0]: 16 + 6 + 3 + ceil(blocks / 256) + 8 (kid.reduction_chain restates it).
-// Algorithmic work: 2 n m d FLOP (self mode: n (n + 64) d), all on the f64 matrix pipe.
-#include "adm_common.h"
+#include "adm_pairsum.h"
 
 namespace {
-
-constexpr int PT = 64;         // tile edge (rows of x and rows of y per block)
-constexpr int PK = 64;         // features staged per step
-constexpr int PP = PK + 4;     // LDS row pitch in floats
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// global -> registers of the 64 x 64 chunk of each operand: 256 threads x 4 x 16 B each; rows past the set and features past d
-// (d % 4 == 0: a float4 is inside or outside as a whole) read as zero
-struct Stage {
-  float4 x[4], y[4];
-};
-
-__device__ __forceinline__ void load_stage(Stage& s, const float* __restrict__ x, long long n, long long r0,
-                                           const float* __restrict__ y, long long m, long long c0, int d, int k0, int tid) {
-#pragma unroll
-  for (int v = 0; v < 4; ++v) {
-    const int e = tid + 256 * v, row = e >> 4, seg = (e & 15) * 4;
-    s.x[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-    s.y[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (k0 + seg < d) {
-      if (r0 + row < n) s.x[v] = *reinterpret_cast<const float4*>(x + (r0 + row) * d + k0 + seg);
-      if (c0 + row < m) s.y[v] = *reinterpret_cast<const float4*>(y + (c0 + row) * d + k0 + seg);
-    }
-  }
-}
-
-__device__ __forceinline__ void store_stage(const Stage& s, float* Xs, float* Ys, int tid) {
-#pragma unroll
-  for (int v = 0; v < 4; ++v) {
-    const int e = tid + 256 * v, row = e >> 4, seg = (e & 15) * 4;
-    *reinterpret_cast<float4*>(Xs + row * PP + seg) = s.x[v];
-    *reinterpret_cast<float4*>(Ys + row * PP + seg) = s.y[v];
-  }
-}
 
 __global__ void __launch_bounds__(256)
 poly3_tile_kernel(const float* __restrict__ x, long long n, const float* __restrict__ y, long long m, int d,
                   double* __restrict__ work, int tiles_j, int self_pairs) {
-  __shared__ __attribute__((aligned(16))) float Xs[PT * PP];
-  __shared__ __attribute__((aligned(16))) float Ys[PT * PP];
-  __shared__ double wsum[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wi = wave >> 1, wj = wave & 1, kq = lane >> 4, c = lane & 15;
-  // block -> tile: row-major over the rectangle, or over the rows of the upper triangle (row bi holds tiles_j - bi tiles)
-  int bi, bj;
-  if (self_pairs) {
-    int rem = (int)blockIdx.x;
-    bi = 0;
-    while (rem >= tiles_j - bi) {
-      rem -= tiles_j - bi;
-      ++bi;
-    }
-    bj = bi + rem;
-  } else {
-    bi = (int)(blockIdx.x / (unsigned)tiles_j);
-    bj = (int)(blockIdx.x % (unsigned)tiles_j);
-  }
-  const long long i0 = (long long)bi * PT, j0 = (long long)bj * PT;
-
+  const PairTile tile = pair_tile_of_block(tiles_j, self_pairs);
+  const long long i0 = tile.i0, j0 = tile.j0;
   f64x4 acc[2][2];
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj) acc[ti][tj] = f64x4{0.0, 0.0, 0.0, 0.0};
-
-  const int nch = (d + PK - 1) / PK;
-  Stage st;
-  load_stage(st, x, n, i0, y, m, j0, d, 0, tid);
-  for (int ch = 0; ch < nch; ++ch) {
-    store_stage(st, Xs, Ys, tid);
-    __syncthreads();
-    if (ch + 1 < nch) load_stage(st, x, n, i0, y, m, j0, d, (ch + 1) * PK, tid);
-    const int left = d - ch * PK;                                   // features left from this chunk on
-    const int groups = left >= PK ? PK / 16 : (left + 15) / 16;     // 16-feature groups with anything in them (block-uniform)
-#pragma unroll
-    for (int g = 0; g < PK / 16; ++g) {
-      if (g < groups) {
-        float4 a[2], b[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          a[t] = *reinterpret_cast<const float4*>(Xs + ((2 * wi + t) * 16 + c) * PP + g * 16 + 4 * kq);
-          b[t] = *reinterpret_cast<const float4*>(Ys + ((2 * wj + t) * 16 + c) * PP + g * 16 + 4 * kq);
-        }
-        const float ae[2][4] = {{a[0].x, a[0].y, a[0].z, a[0].w}, {a[1].x, a[1].y, a[1].z, a[1].w}};
-        const float be[2][4] = {{b[0].x, b[0].y, b[0].z, b[0].w}, {b[1].x, b[1].y, b[1].z, b[1].w}};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const double af[2] = {(double)ae[0][e], (double)ae[1][e]}, bf[2] = {(double)be[0][e], (double)be[1][e]};
-#pragma unroll
-          for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-              acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[ti], bf[tj], acc[ti][tj], 0, 0, 0);
-        }
-      }
-    }
-    __syncthreads();
-  }
+  pair_gram_tile(acc, x, n, y, m, d, i0, j0);
 
   // epilogue: a lane's 4 results of an MFMA tile are rows kq + 4 q, column c (the f64 C/D map)
   const double dd = (double)d;
-  const bool diag = self_pairs && bi == bj;
+  const bool diag = self_pairs && tile.bi == tile.bj;
   double s = 0.0;
 #pragma unroll
   for (int ti = 0; ti < 2; ++ti)
@@ -137,68 +38,26 @@ poly3_tile_kernel(const float* __restrict__ x, long long n, const float* __restr
         const bool live = i < n && j < m && !(diag && i == j);
         s += live ? k3 : 0.0;
       }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  if (lane == 0) wsum[wave] = s;
-  __syncthreads();
-  if (tid == 0) {
-    const double tot = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-    work[blockIdx.x] = (self_pairs && bi != bj) ? 2.0 * tot : tot;
-  }
-}
-
-__global__ void __launch_bounds__(256)
-poly3_final_kernel(const double* __restrict__ work, long long blocks, double* __restrict__ out) {
-  __shared__ double red[256];
-  const int tid = threadIdx.x;
-  double s = 0.0;
-  for (long long i = tid; i < blocks; i += 256) s += work[i];
-  red[tid] = s;
-  __syncthreads();
-#pragma unroll
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) red[tid] += red[tid + off];
-    __syncthreads();
-  }
-  if (tid == 0) out[0] = red[0];
-}
-
-constexpr long long POLY3_MAX_ROWS = 1LL << 30;     // tile counts and the triangle's block count stay far inside int64
-constexpr long long POLY3_MAX_BLOCKS = 0x7fffffffLL;   // one grid dimension
-
-long long poly3_blocks(long long n, long long m, int self_pairs) {
-  if (n < 1 || m < 1 || n > POLY3_MAX_ROWS || m > POLY3_MAX_ROWS || (self_pairs && m != n)) return -1;
-  const long long ti = (n + PT - 1) / PT, tj = (m + PT - 1) / PT;
-  const long long b = self_pairs ? ti * (ti + 1) / 2 : ti * tj;
-  return b <= POLY3_MAX_BLOCKS ? b : -1;
+  pair_block_sum(s, work, self_pairs && tile.bi != tile.bj);
 }
 
 }  // namespace
 
 extern "C" int64_t adm_poly3_work_elems(int64_t n, int64_t m, int self_pairs) {
-  const long long b = poly3_blocks(n, m, self_pairs != 0);
+  const long long b = pair_blocks(n, m, self_pairs != 0);
   if (b < 0) adm_set_error("adm_poly3_work_elems: unsupported shape n=%lld m=%lld self_pairs=%d", (long long)n, (long long)m, self_pairs);
   return b;
 }
 
 extern "C" int adm_poly3_sums(const float* x, int64_t n, const float* y, int64_t m, int d, double* work, int64_t work_elems,
                               double* out, void* stream, int self_pairs) {
-  ADM_REQUIRE(self_pairs == 0 || self_pairs == 1, ADM_E_ARG, "adm_poly3_sums: self_pairs=%d is neither 0 nor 1", self_pairs);
-  ADM_REQUIRE(x && work && out && (y || self_pairs), ADM_E_ARG, "adm_poly3_sums: null pointer");
-  ADM_REQUIRE(n >= 1 && m >= 1, ADM_E_ARG, "adm_poly3_sums: need n >= 1 and m >= 1 (n=%lld m=%lld)", (long long)n, (long long)m);
-  ADM_REQUIRE(!self_pairs || ((y == nullptr || y == x) && m == n), ADM_E_ARG,
-              "adm_poly3_sums: self_pairs needs y == x (or NULL) and m == n (n=%lld m=%lld)", (long long)n, (long long)m);
-  ADM_REQUIRE(d >= 4 && d % 4 == 0, ADM_E_SHAPE, "adm_poly3_sums: d=%d must be a positive multiple of 4", d);
-  const long long blocks = poly3_blocks(n, m, self_pairs);
-  ADM_REQUIRE(blocks > 0, ADM_E_SHAPE, "adm_poly3_sums: n=%lld m=%lld too large for the grid", (long long)n, (long long)m);
-  ADM_REQUIRE(work_elems >= blocks, ADM_E_ARG, "adm_poly3_sums: work holds %lld doubles, adm_poly3_work_elems says %lld",
-              (long long)work_elems, blocks);
-  ADM_REQUIRE(adm_aligned16(x) && (y == nullptr || adm_aligned16(y)), ADM_E_ALIGN, "adm_poly3_sums: 16-byte aligned rows required");
-  ADM_REQUIRE((((uintptr_t)work) & 7u) == 0 && (((uintptr_t)out) & 7u) == 0, ADM_E_ALIGN, "adm_poly3_sums: 8-byte aligned work / out required");
+  long long blocks;
+  const int rc = pair_check_args("poly3", x, n, y, m, d, work, work_elems, 0, out, self_pairs, &blocks);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int tiles_j = (int)((m + PT - 1) / PT);
   hipLaunchKernelGGL(poly3_tile_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, (long long)n, y ? y : x, (long long)m, d, work,
                      tiles_j, self_pairs);
-  hipLaunchKernelGGL(poly3_final_kernel, dim3(1), dim3(256), 0, s, (const double*)work, blocks, out);
+  hipLaunchKernelGGL(pair_final_kernel, dim3(1), dim3(256), 0, s, (const double*)work, blocks, out);
   return adm_check_launch("adm_poly3_sums");
 }

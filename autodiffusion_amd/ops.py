@@ -892,51 +892,41 @@ def resize_bilinear(images, oh: int, ow: int, cpad: int, layout: str, half_pixel
     return out
 
 
-# ------------------------------------------------------------------ Kernel Inception Distance
-def poly3_sums(x, y=None, out=None):
-    """float64 device tensor [1]: sum_i sum_j (x_i . y_j / d + 1)^3 over fp32 rows x [n, d], y [m, d]; with y None the sum over the
-    pairs i != j of x alone (adm_poly3_sums: an f64 matrix-core Gram with the cube and the reduction in its epilogue).  The
-    workspace is sized by the library and allocated here; no host synchronisation."""
+# ------------------------------------------------------------------ pair sums: Kernel Inception Distance, CMMD
+def _pair_sums(stem, x, y, out, *extra):
+    """The launch of adm_<stem>_sums(x, n, y, m, d, *extra, work, elems, out, stream, self_pairs) -> (out, work, n, m)."""
     self_pairs = y is None
     if x.dim() != 2 or (not self_pairs and (y.dim() != 2 or y.shape[1] != x.shape[1])):
-        raise AdmError(f"poly3_sums: expected rows [n, d] and [m, d], got {tuple(x.shape)}" + ("" if self_pairs else f" and {tuple(y.shape)}"))
+        raise AdmError(f"{stem}_sums: expected rows [n, d] and [m, d], got {tuple(x.shape)}" + ("" if self_pairs else f" and {tuple(y.shape)}"))
     px, py = _ptr(x, torch.float32, "x"), _ptr(y, torch.float32, "y")
     n, d = x.shape
     m = n if self_pairs else y.shape[0]
     lib = _lib.load()
-    elems = lib.adm_poly3_work_elems(n, m, int(self_pairs))
+    elems = getattr(lib, f"adm_{stem}_work_elems")(n, m, int(self_pairs))
     if elems < 0:
-        check(-2, "adm_poly3_work_elems")
+        check(-2, f"adm_{stem}_work_elems")
     work = torch.empty(elems, dtype=torch.float64, device=x.device)
     if out is None:
         out = torch.empty(1, dtype=torch.float64, device=x.device)
-    check(lib.adm_poly3_sums(px, n, py, m, d, _ptr(work), elems, _ptr(out, torch.float64, "out"), _stream(), int(self_pairs)),
-          "adm_poly3_sums")
-    return out
+    check(getattr(lib, f"adm_{stem}_sums")(px, n, py, m, d, *extra, _ptr(work), elems, _ptr(out, torch.float64, "out"), _stream(),
+                                           int(self_pairs)), f"adm_{stem}_sums")
+    return out, work, n, m
 
 
-# ------------------------------------------------------------------ CMMD
+def poly3_sums(x, y=None, out=None):
+    """float64 device tensor [1]: sum_i sum_j (x_i . y_j / d + 1)^3 over fp32 rows x [n, d], y [m, d]; with y None the sum over the
+    pairs i != j of x alone (adm_poly3_sums: an f64 matrix-core Gram with the cube and the reduction in its epilogue).  The
+    workspace is sized by the library and allocated here; no host synchronisation."""
+    return _pair_sums("poly3", x, y, out)[0]
+
+
 def rbf_sums(x, y=None, gamma=0.005, out=None, return_norms=False):
     """float64 device tensor [1]: sum_i sum_j expm1(-gamma max(2 - 2 cos(x_i, y_j), 0)) over fp32 rows x [n, d], y [m, d] (not
     normalised: the kernel does that in f64); with y None the sum over the pairs i != j of x alone (adm_rbf_sums: an f64
     matrix-core Gram with the normalisation, expm1 and the reduction in its epilogue).  The workspace is sized by the library and
     allocated here; no host synchronisation.  return_norms: also the f64 squared norms the kernel used, [n + m] (x's, then y's)."""
-    self_pairs = y is None
-    if x.dim() != 2 or (not self_pairs and (y.dim() != 2 or y.shape[1] != x.shape[1])):
-        raise AdmError(f"rbf_sums: expected rows [n, d] and [m, d], got {tuple(x.shape)}" + ("" if self_pairs else f" and {tuple(y.shape)}"))
-    px, py = _ptr(x, torch.float32, "x"), _ptr(y, torch.float32, "y")
-    n, d = x.shape
-    m = n if self_pairs else y.shape[0]
-    lib = _lib.load()
-    elems = lib.adm_rbf_work_elems(n, m, int(self_pairs))
-    if elems < 0:
-        check(-2, "adm_rbf_work_elems")
-    work = torch.empty(elems, dtype=torch.float64, device=x.device)
-    if out is None:
-        out = torch.empty(1, dtype=torch.float64, device=x.device)
-    check(lib.adm_rbf_sums(px, n, py, m, d, float(gamma), _ptr(work), elems, _ptr(out, torch.float64, "out"), _stream(),
-                           int(self_pairs)), "adm_rbf_sums")
-    return (out, work[elems - n - m:]) if return_norms else out
+    out, work, n, m = _pair_sums("rbf", x, y, out, float(gamma))
+    return (out, work[work.numel() - n - m:]) if return_norms else out
 
 
 # ------------------------------------------------------------------ DPM-Solver on the pixel path

@@ -113,6 +113,16 @@ def test_chains_and_workspace_match_the_library():
             cmmd.gamma_of(bad)
 
 
+def test_kid_and_cmmd_share_one_tile_geometry():
+    """adm_pairsum.h and mmd.py each define the block count once: the two libraries' entry points and the two modules agree on it."""
+    from autodiffusion_amd import kid
+    lib = _lib.load()
+    for n, m, sp in ((1, 1, 0), (2, 2, 1), (64, 64, 0), (65, 129, 0), (130, 70, 0), (65, 65, 1), (257, 257, 1), (30000, 30000, 1)):
+        blocks = lib.adm_poly3_work_elems(n, m, sp)
+        assert blocks == lib.adm_rbf_work_elems(n, m, sp) - n - m == kid.poly3_blocks(n, m, bool(sp)) == cmmd.rbf_blocks(n, m, bool(sp)), (n, m, sp)
+        assert blocks > 0
+
+
 @pytest.mark.parametrize("sigma", [1.0, 10.0])
 def test_every_planted_defect_falls_outside_the_bound(sigma):
     n, m, d = 65, 129, 36
