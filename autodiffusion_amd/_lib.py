@@ -84,6 +84,8 @@ class UnipcArgs(C.Structure):
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 
+PARAMS = {"eps": 0, "x0": 1, "v": 2}   # ADM_PARAM_* (include/adm_hip.h): what a latent model's output is
+
 # name -> (restype, argtypes); every symbol declared in include/adm_hip.h
 SIGNATURES = {
     "adm_abi_version": (_I, []),
@@ -160,6 +162,11 @@ SIGNATURES = {
     "adm_pix_dpm_step": (_I, [C.POINTER(PixDpmArgs), _P, _I]),
     "adm_pix_unipc_step": (_I, [C.POINTER(PixUnipcArgs), _P, _I]),
     "adm_unipc_step": (_I, [C.POINTER(UnipcArgs), _P, _I]),
+    # the parameterised steps (`param` last) and the exact GELU (`flags` last)
+    "adm_sd_step_p": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(SdStepCoefs), _P, _I]),
+    "adm_dpm_step_p": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, _F, _F, _F, _F, _F, _F, _P, _I]),
+    "adm_unipc_step_p": (_I, [C.POINTER(UnipcArgs), _P, _I]),
+    "adm_gelu": (_I, [_P, _P, C.c_int64, _I, _P, _I]),
 }
 
 _libs = {}

@@ -4,6 +4,7 @@
 //   adm_clip_embed         token_embedding[ids] + position_embedding[:T] -> 16-bit rows [N][pitch][C], pad rows zero
 //   adm_attention_causal   softmax(q k^T / 8 + causal mask) v over 64-wide heads of a fused q | k | v projection
 //   adm_quick_gelu         u * sigmoid(1.702 u)
+//   adm_gelu               0.5 u (1 + erf(u / sqrt 2)): the exact GELU of the OpenCLIP text tower (Stable Diffusion 2.x)
 //   adm_layernorm_f32out   the final LayerNorm, written as compact fp32 rows [N][T][C]
 //
 // Causal attention: one block of 4 waves per (prompt, head).  The head's K and V rows [0, T) are staged once, row-major, in LDS
@@ -195,6 +196,18 @@ quick_gelu_kernel(const uint16_t* __restrict__ u, uint16_t* __restrict__ out, lo
   }
 }
 
+// the exact GELU 0.5 u (1 + erf(u / sqrt 2)) in fp32, adm_geglu's gate factor (adm_sd.hip), rounded once to the element type
+__global__ void __launch_bounds__(256)
+gelu_kernel(const uint16_t* __restrict__ u, uint16_t* __restrict__ out, long long items) {
+  for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (long long)gridDim.x * blockDim.x) {
+    float a[8], y[8];
+    unpack8(*reinterpret_cast<const uint4*>(u + it * 8), a);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] = 0.5f * a[j] * (1.0f + erff(a[j] * 0.70710678118654752f));
+    *reinterpret_cast<uint4*>(out + it * 8) = pack8(y);
+  }
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
@@ -303,6 +316,16 @@ extern "C" int adm_quick_gelu(const adm_bf16* u, adm_bf16* out, int64_t rows, in
   const long long items = (long long)rows * (inner / 8);
   hipLaunchKernelGGL(quick_gelu_kernel, dim3(grid_for(items, 256)), dim3(256), 0, (hipStream_t)stream, u, out, items);
   return adm_check_launch("adm_quick_gelu");
+}
+
+extern "C" int adm_gelu(const adm_bf16* u, adm_bf16* out, int64_t rows, int inner, void* stream, int flags) {
+  ADM_REQUIRE(flags == 0, ADM_E_ARG, "adm_gelu: flags=%d (must be 0)", flags);
+  ADM_REQUIRE(u && out, ADM_E_ARG, "adm_gelu: null pointer");
+  ADM_REQUIRE(rows > 0 && inner > 0 && inner % 8 == 0, ADM_E_SHAPE, "adm_gelu: rows=%lld inner=%d unsupported", (long long)rows, inner);
+  ADM_REQUIRE(adm_aligned16(u) && adm_aligned16(out), ADM_E_ALIGN, "adm_gelu: unaligned pointer");
+  const long long items = (long long)rows * (inner / 8);
+  hipLaunchKernelGGL(gelu_kernel, dim3(grid_for(items, 256)), dim3(256), 0, (hipStream_t)stream, u, out, items);
+  return adm_check_launch("adm_gelu");
 }
 
 extern "C" int adm_layernorm_f32out(const adm_bf16* x, const float* gamma, const float* beta, float* out, int n, int t, int pitch,

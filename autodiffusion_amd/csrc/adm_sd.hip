@@ -131,6 +131,15 @@ extern "C" int adm_geglu(const adm_bf16* u, adm_bf16* out, int64_t rows, int inn
 // One latent sampler update ("Stable Diffusion"/ldm/models/diffusion/ddim.py:165-203 p_sample_ddim,
 // plms.py:195-258 p_sample_plms): classifier-free guidance combine, multistep eps blend, pred_x0 and x_prev in one
 // pass over the latents (fp32, 5-7 streams instead of ~12 separate elementwise launches).
+//
+// Parameterisations (adm_sd_step_p; PARAM is a template argument, so the eps instantiation is the kernel adm_sd_step always
+// launched).  o = the guided RAW model output, combined by the expression above; then, each line one fp32 operation, left to
+// right, compiled with fp contract(off):
+//   ADM_PARAM_V    t1 = sqrt_at * o;  t2 = sqrt_one_minus_at * x;  e = t1 + t2
+//                  pred_x0 without history and with w0 == 1 (DDIM):  s1 = sqrt_at * x;  s2 = sqrt_one_minus_at * o;  x0 = s1 - s2
+//   ADM_PARAM_X0   t1 = sqrt_at * o;  t2 = x - t1;  e = t2 / sqrt_one_minus_at
+//                  pred_x0 without history and with w0 == 1 (DDIM):  x0 = o
+// e_out holds e (the PLMS history is eps); e', x_prev and pred_x0 with a history come from e by the eps expressions.
 namespace {
 struct SdStep {
   const float* x; const float* eu; const float* ec; const float* h1; const float* h2; const float* h3; const float* noise;
@@ -139,14 +148,40 @@ struct SdStep {
   float cfg, w0, w1, w2, w3, sqrt_one_minus_at, sqrt_at, sqrt_a_prev, dir_coef, sigma;
 };
 
+// e from the raw output o under V / X0, every operation rounded on its own
+template <int PARAM>
+__device__ __forceinline__ float sd_eps_of(float o, float x, float sqrt_at, float sqrt_one_minus_at) {
+#pragma clang fp contract(off)
+  if constexpr (PARAM == ADM_PARAM_V) {
+    const float t1 = sqrt_at * o;
+    const float t2 = sqrt_one_minus_at * x;
+    return t1 + t2;
+  } else {
+    const float t1 = sqrt_at * o;
+    const float t2 = x - t1;
+    return t2 / sqrt_one_minus_at;
+  }
+}
+
+__device__ __forceinline__ float sd_x0_of_v(float o, float x, float sqrt_at, float sqrt_one_minus_at) {
+#pragma clang fp contract(off)
+  const float s1 = sqrt_at * x;
+  const float s2 = sqrt_one_minus_at * o;
+  return s1 - s2;
+}
+
+template <int PARAM>
 __global__ void __launch_bounds__(256)
 sd_step_kernel(const SdStep p) {
+  const bool direct_x0 = PARAM != ADM_PARAM_EPS && !p.h1 && !p.h2 && !p.h3 && p.w0 == 1.0f;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < p.numel; i += (long long)gridDim.x * blockDim.x) {
     float e = p.ec[i];
     if (p.eu) {
       const float u = p.eu[i];
       e = u + p.cfg * (e - u);
     }
+    const float o = e;
+    if constexpr (PARAM != ADM_PARAM_EPS) e = sd_eps_of<PARAM>(o, p.x[i], p.sqrt_at, p.sqrt_one_minus_at);
     if (p.e_out) p.e_out[i] = e;
     float ep = p.w0 * e;
     if (p.h1) ep += p.w1 * p.h1[i];
@@ -156,23 +191,51 @@ sd_step_kernel(const SdStep p) {
     float xp = p.sqrt_a_prev * x0 + p.dir_coef * ep;
     if (p.noise) xp += p.sigma * p.noise[i];
     p.x_prev[i] = xp;
-    if (p.pred_x0) p.pred_x0[i] = x0;
+    if (p.pred_x0) {
+      float px0 = x0;
+      if constexpr (PARAM == ADM_PARAM_V) {
+        if (direct_x0) px0 = sd_x0_of_v(o, p.x[i], p.sqrt_at, p.sqrt_one_minus_at);
+      } else if constexpr (PARAM == ADM_PARAM_X0) {
+        if (direct_x0) px0 = o;
+      }
+      p.pred_x0[i] = px0;
+    }
   }
+}
+
+int sd_step_launch(const char* who, const float* x, const float* eps_uncond, const float* eps_cond, const float* h1, const float* h2,
+                   const float* h3, const float* noise, float* x_prev, float* pred_x0, float* e_out, int64_t numel,
+                   const adm_sd_step_coefs* c, int param, void* stream) {
+  ADM_REQUIRE(param == ADM_PARAM_EPS || param == ADM_PARAM_X0 || param == ADM_PARAM_V, ADM_E_ARG,
+              "%s: param=%d (0 eps, 1 x0, 2 v)", who, param);
+  ADM_REQUIRE(x && eps_cond && x_prev && c, ADM_E_ARG, "%s: null pointer", who);
+  ADM_REQUIRE(numel > 0, ADM_E_ARG, "%s: empty tensor", who);
+  ADM_REQUIRE(c->sqrt_at > 0.f, ADM_E_ARG, "%s: sqrt(alpha_t) must be positive", who);
+  ADM_REQUIRE(param != ADM_PARAM_X0 || c->sqrt_one_minus_at > 0.f, ADM_E_ARG,
+              "%s: sqrt(1 - alpha_t) must be positive under the x0 parameterisation", who);
+  SdStep p{x, eps_uncond, eps_cond, h1, h2, h3, noise, x_prev, pred_x0, e_out, (long long)numel,
+           c->cfg_scale, c->w[0], c->w[1], c->w[2], c->w[3], c->sqrt_one_minus_at, c->sqrt_at, c->sqrt_a_prev, c->dir_coef, c->sigma};
+  long long blocks = (numel + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  const dim3 grid((unsigned)blocks);
+  hipStream_t s = (hipStream_t)stream;
+  if (param == ADM_PARAM_V) hipLaunchKernelGGL((sd_step_kernel<ADM_PARAM_V>), grid, dim3(256), 0, s, p);
+  else if (param == ADM_PARAM_X0) hipLaunchKernelGGL((sd_step_kernel<ADM_PARAM_X0>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((sd_step_kernel<ADM_PARAM_EPS>), grid, dim3(256), 0, s, p);
+  return adm_check_launch(who);
 }
 }  // namespace
 
 extern "C" int adm_sd_step(const float* x, const float* eps_uncond, const float* eps_cond, const float* h1, const float* h2,
                            const float* h3, const float* noise, float* x_prev, float* pred_x0, float* e_out, int64_t numel,
                            const adm_sd_step_coefs* c, void* stream) {
-  ADM_REQUIRE(x && eps_cond && x_prev && c, ADM_E_ARG, "adm_sd_step: null pointer");
-  ADM_REQUIRE(numel > 0, ADM_E_ARG, "adm_sd_step: empty tensor");
-  ADM_REQUIRE(c->sqrt_at > 0.f, ADM_E_ARG, "adm_sd_step: sqrt(alpha_t) must be positive");
-  SdStep p{x, eps_uncond, eps_cond, h1, h2, h3, noise, x_prev, pred_x0, e_out, (long long)numel,
-           c->cfg_scale, c->w[0], c->w[1], c->w[2], c->w[3], c->sqrt_one_minus_at, c->sqrt_at, c->sqrt_a_prev, c->dir_coef, c->sigma};
-  long long blocks = (numel + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(sd_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-  return adm_check_launch("adm_sd_step");
+  return sd_step_launch("adm_sd_step", x, eps_uncond, eps_cond, h1, h2, h3, noise, x_prev, pred_x0, e_out, numel, c, ADM_PARAM_EPS, stream);
+}
+
+extern "C" int adm_sd_step_p(const float* x, const float* out_uncond, const float* out_cond, const float* h1, const float* h2,
+                             const float* h3, const float* noise, float* x_prev, float* pred_x0, float* e_out, int64_t numel,
+                             const adm_sd_step_coefs* c, void* stream, int param) {
+  return sd_step_launch("adm_sd_step_p", x, out_uncond, out_cond, h1, h2, h3, noise, x_prev, pred_x0, e_out, numel, c, param, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -180,6 +243,10 @@ extern "C" int adm_sd_step(const float* x, const float* eps_uncond, const float*
 // model_wrapper's classifier-free guidance + data_prediction_fn :289-330, 380-400):
 //   e = eu ? eu + cfg*(ec - eu) : ec;   m = (x - sigma_s*e) / alpha_s          (kept: the next step's model_prev)
 //   x_next = a*x + b0*m + b1*m_prev
+// Parameterisations (adm_dpm_step_p, model_wrapper's noise_pred_fn :297-306 folded into the data prediction); o = the guided raw
+// output by the expression of e, then with fp contract(off), one fp32 operation each:
+//   ADM_PARAM_V    t1 = alpha_s * x;  t2 = sigma_s * o;  m = t1 - t2
+//   ADM_PARAM_X0   m = o
 namespace {
 struct DpmStep {
   const float* x; const float* eu; const float* ec; const float* m_prev;
@@ -187,6 +254,21 @@ struct DpmStep {
   long long numel;
   float cfg, sigma_s, alpha_s, a, b0, b1;
 };
+
+// the data prediction of a guided raw output o under V / X0 (adm_dpm_step_p, adm_unipc_step_p)
+template <int PARAM>
+__device__ __forceinline__ float dpm_m_of(float o, float x, float alpha_s, float sigma_s) {
+#pragma clang fp contract(off)
+  if constexpr (PARAM == ADM_PARAM_V) {
+    const float t1 = alpha_s * x;
+    const float t2 = sigma_s * o;
+    return t1 - t2;
+  } else {
+    return o;
+  }
+}
+
+template <int PARAM>
 __global__ void __launch_bounds__(256)
 dpm_step_kernel(const DpmStep p) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < p.numel; i += (long long)gridDim.x * blockDim.x) {
@@ -196,25 +278,47 @@ dpm_step_kernel(const DpmStep p) {
       e = u + p.cfg * (e - u);
     }
     const float x = p.x[i];
-    const float m = (x - p.sigma_s * e) / p.alpha_s;
+    float m;
+    if constexpr (PARAM == ADM_PARAM_EPS) m = (x - p.sigma_s * e) / p.alpha_s;
+    else m = dpm_m_of<PARAM>(e, x, p.alpha_s, p.sigma_s);
     float xn = p.a * x + p.b0 * m;
     if (p.m_prev) xn += p.b1 * p.m_prev[i];
     p.x_next[i] = xn;
     if (p.m_out) p.m_out[i] = m;
   }
 }
+
+int dpm_step_launch(const char* who, const float* x, const float* eps_uncond, const float* eps_cond, const float* m_prev, float* x_next,
+                    float* m_out, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float a, float b0, float b1, int param,
+                    void* stream) {
+  ADM_REQUIRE(param == ADM_PARAM_EPS || param == ADM_PARAM_X0 || param == ADM_PARAM_V, ADM_E_ARG,
+              "%s: param=%d (0 eps, 1 x0, 2 v)", who, param);
+  ADM_REQUIRE(x && eps_cond && x_next, ADM_E_ARG, "%s: null pointer", who);
+  ADM_REQUIRE(numel > 0 && alpha_s > 0.f, ADM_E_ARG, "%s: empty tensor or alpha_s <= 0", who);
+  DpmStep p{x, eps_uncond, eps_cond, m_prev, x_next, m_out, (long long)numel, cfg_scale, sigma_s, alpha_s, a, b0, b1};
+  long long blocks = (numel + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  const dim3 grid((unsigned)blocks);
+  hipStream_t s = (hipStream_t)stream;
+  if (param == ADM_PARAM_V) hipLaunchKernelGGL((dpm_step_kernel<ADM_PARAM_V>), grid, dim3(256), 0, s, p);
+  else if (param == ADM_PARAM_X0) hipLaunchKernelGGL((dpm_step_kernel<ADM_PARAM_X0>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((dpm_step_kernel<ADM_PARAM_EPS>), grid, dim3(256), 0, s, p);
+  return adm_check_launch(who);
+}
 }  // namespace
 
 extern "C" int adm_dpm_step(const float* x, const float* eps_uncond, const float* eps_cond, const float* m_prev, float* x_next,
                             float* m_out, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float a, float b0,
                             float b1, void* stream) {
-  ADM_REQUIRE(x && eps_cond && x_next, ADM_E_ARG, "adm_dpm_step: null pointer");
-  ADM_REQUIRE(numel > 0 && alpha_s > 0.f, ADM_E_ARG, "adm_dpm_step: empty tensor or alpha_s <= 0");
-  DpmStep p{x, eps_uncond, eps_cond, m_prev, x_next, m_out, (long long)numel, cfg_scale, sigma_s, alpha_s, a, b0, b1};
-  long long blocks = (numel + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(dpm_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-  return adm_check_launch("adm_dpm_step");
+  return dpm_step_launch("adm_dpm_step", x, eps_uncond, eps_cond, m_prev, x_next, m_out, numel, cfg_scale, sigma_s, alpha_s, a, b0, b1,
+                         ADM_PARAM_EPS, stream);
+}
+
+extern "C" int adm_dpm_step_p(const float* x, const float* out_uncond, const float* out_cond, const float* m_prev, float* x_next,
+                              float* m_out, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float a, float b0,
+                              float b1, void* stream, int param) {
+  return dpm_step_launch("adm_dpm_step_p", x, out_uncond, out_cond, m_prev, x_next, m_out, numel, cfg_scale, sigma_s, alpha_s, a, b0, b1,
+                         param, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -225,6 +329,8 @@ extern "C" int adm_dpm_step(const float* x, const float* eps_uncond, const float
 //   x_pred = ap*x_c + p0*m + p1*h1 + p2*h2                                  (the predictor of the next update)
 // fp32, left to right, no contraction: tests/unipc_ref.py restates exactly this sequence.  8-11 streams in one pass; two
 // adm_dpm_step launches for the same two states would read x_eval, eps and the history twice.
+// adm_unipc_step_p: m from the guided raw output as adm_dpm_step_p's (dpm_m_of above: V  t1 = alpha_s * x_eval; t2 = sigma_s * o;
+// m = t1 - t2.  X0  m = o); everything after m, both VEC routes, is the same code.
 namespace {
 struct UniStep {
   const float* x; const float* eu; const float* ec; const float* xb; const float* h1; const float* h2; const float* h3;
@@ -233,7 +339,7 @@ struct UniStep {
   float cfg, sigma_s, alpha_s, ac, c0, c1, c2, c3, ap, p0, p1, p2;
 };
 
-template <int VEC>
+template <int VEC, int PARAM>
 __global__ void __launch_bounds__(256)
 unipc_step_kernel(const UniStep p) {
 #pragma clang fp contract(off)
@@ -267,7 +373,9 @@ unipc_step_kernel(const UniStep p) {
     for (int j = 0; j < VEC; ++j) {
       float e = cv[j];
       if (p.eu) e = uv[j] + p.cfg * (e - uv[j]);
-      const float m = (xv[j] - p.sigma_s * e) / p.alpha_s;
+      float m;
+      if constexpr (PARAM == ADM_PARAM_EPS) m = (xv[j] - p.sigma_s * e) / p.alpha_s;
+      else m = dpm_m_of<PARAM>(e, xv[j], p.alpha_s, p.sigma_s);
       mv[j] = m;
       float xc = xv[j];
       if (p.x_corr) {
@@ -295,12 +403,20 @@ unipc_step_kernel(const UniStep p) {
 }
 }  // namespace
 
-extern "C" int adm_unipc_step(const adm_unipc_args* a, void* stream, int flags) {
-  ADM_REQUIRE(flags == 0, ADM_E_ARG, "adm_unipc_step: flags=%d (must be 0)", flags);
-  ADM_REQUIRE(a, ADM_E_ARG, "adm_unipc_step: null argument block");
-  ADM_REQUIRE(a->x_eval && a->eps_cond && a->m_out, ADM_E_ARG, "adm_unipc_step: null x_eval / eps_cond / m_out");
-  ADM_REQUIRE(!a->x_corr || a->x_base, ADM_E_ARG, "adm_unipc_step: x_corr without x_base");
-  ADM_REQUIRE(a->numel > 0 && a->numel <= (1LL << 60) && a->alpha_s > 0.f, ADM_E_ARG, "adm_unipc_step: numel=%lld or alpha_s <= 0",
+namespace {
+template <int PARAM>
+void unipc_launch(bool vec4, unsigned blocks, hipStream_t s, const UniStep& p) {
+  if (vec4) hipLaunchKernelGGL((unipc_step_kernel<4, PARAM>), dim3(blocks), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((unipc_step_kernel<1, PARAM>), dim3(blocks), dim3(256), 0, s, p);
+}
+
+int unipc_step_launch(const char* who, const adm_unipc_args* a, int param, void* stream) {
+  ADM_REQUIRE(param == ADM_PARAM_EPS || param == ADM_PARAM_X0 || param == ADM_PARAM_V, ADM_E_ARG,
+              "%s: param=%d (0 eps, 1 x0, 2 v)", who, param);
+  ADM_REQUIRE(a, ADM_E_ARG, "%s: null argument block", who);
+  ADM_REQUIRE(a->x_eval && a->eps_cond && a->m_out, ADM_E_ARG, "%s: null x_eval / eps_cond / m_out", who);
+  ADM_REQUIRE(!a->x_corr || a->x_base, ADM_E_ARG, "%s: x_corr without x_base", who);
+  ADM_REQUIRE(a->numel > 0 && a->numel <= (1LL << 60) && a->alpha_s > 0.f, ADM_E_ARG, "%s: numel=%lld or alpha_s <= 0", who,
               (long long)a->numel);
   UniStep p{a->x_eval, a->eps_uncond, a->eps_cond, a->x_base, a->h1, a->h2, a->h3, a->m_out, a->x_corr, a->x_pred,
             (long long)a->numel, a->cfg_scale, a->sigma_s, a->alpha_s, a->ac, a->c0, a->c1, a->c2, a->c3, a->ap, a->p0, a->p1, a->p2};
@@ -313,7 +429,19 @@ extern "C" int adm_unipc_step(const adm_unipc_args* a, void* stream, int flags) 
   const long long groups = vec4 ? a->numel / 4 : a->numel;
   long long blocks = (groups + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  if (vec4) hipLaunchKernelGGL((unipc_step_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL((unipc_step_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-  return adm_check_launch("adm_unipc_step");
+  hipStream_t s = (hipStream_t)stream;
+  if (param == ADM_PARAM_V) unipc_launch<ADM_PARAM_V>(vec4, (unsigned)blocks, s, p);
+  else if (param == ADM_PARAM_X0) unipc_launch<ADM_PARAM_X0>(vec4, (unsigned)blocks, s, p);
+  else unipc_launch<ADM_PARAM_EPS>(vec4, (unsigned)blocks, s, p);
+  return adm_check_launch(who);
+}
+}  // namespace
+
+extern "C" int adm_unipc_step(const adm_unipc_args* a, void* stream, int flags) {
+  ADM_REQUIRE(flags == 0, ADM_E_ARG, "adm_unipc_step: flags=%d (must be 0)", flags);
+  return unipc_step_launch("adm_unipc_step", a, ADM_PARAM_EPS, stream);
+}
+
+extern "C" int adm_unipc_step_p(const adm_unipc_args* a, void* stream, int param) {
+  return unipc_step_launch("adm_unipc_step_p", a, param, stream);
 }

@@ -608,6 +608,15 @@ def quick_gelu(u):
     return out
 
 
+def gelu(u):
+    """16-bit [..., I] -> the exact GELU 0.5 u (1 + erf(u / sqrt 2)) (fp32 math, one rounding), same type."""
+    _act16(u, "gelu: u")
+    inner = u.shape[-1]
+    out = torch.empty_like(u)
+    check(_L(u).adm_gelu(_ptr(u, u.dtype, "u"), _ptr(out), u.numel() // inner, inner, _stream(), 0), "adm_gelu")
+    return out
+
+
 def layernorm_f32out(x, t: int, gamma, beta, eps: float = 1e-5):
     """16-bit [N, pitch, C] -> fp32 [N, t, C]: LayerNorm over C (fp32 statistics) of the first t rows of every prompt."""
     _act16(x, "layernorm_f32out: x")

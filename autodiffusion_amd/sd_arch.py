@@ -51,13 +51,16 @@ class SDResBlockSpec:
 
 @dataclass(frozen=True)
 class SDTransformerSpec:
-    """SpatialTransformer: GroupNorm(eps 1e-6) - 1x1 proj_in - depth x BasicTransformerBlock - 1x1 proj_out (+x)."""
+    """SpatialTransformer: GroupNorm(eps 1e-6) - 1x1 proj_in - depth x BasicTransformerBlock - 1x1 proj_out (+x).
+    ``linear`` (SD 2.x's ``use_linear_in_transformer``): proj_in / proj_out are stored as nn.Linear weights [out, in] and applied
+    after / before the rearrange to tokens -- per pixel the same matrix product as the 1x1 conv, so only the stored shape differs."""
     prefix: str
     channels: int
     heads: int
     d_head: int
     context_dim: int
     depth: int = 1
+    linear: bool = False
 
     @property
     def inner(self) -> int:
@@ -66,8 +69,8 @@ class SDTransformerSpec:
     def param_shapes(self):
         p, c, i = self.prefix, self.channels, self.inner
         s = {f"{p}.norm.weight": (c,), f"{p}.norm.bias": (c,),
-             f"{p}.proj_in.weight": (i, c, 1, 1), f"{p}.proj_in.bias": (i,),
-             f"{p}.proj_out.weight": (c, i, 1, 1), f"{p}.proj_out.bias": (c,)}
+             f"{p}.proj_in.weight": (i, c) if self.linear else (i, c, 1, 1), f"{p}.proj_in.bias": (i,),
+             f"{p}.proj_out.weight": (c, i) if self.linear else (c, i, 1, 1), f"{p}.proj_out.bias": (c,)}
         for d in range(self.depth):
             b = f"{p}.transformer_blocks.{d}"
             for a, kv in (("attn1", i), ("attn2", self.context_dim)):
@@ -143,7 +146,7 @@ class SDUNetPlan:
 def sd_unet_plan(in_channels: int, model_channels: int, out_channels: int, num_res_blocks: int,
                  attention_resolutions: Sequence[int], channel_mult: Sequence[int] = (1, 2, 4, 8),
                  num_heads: int = -1, num_head_channels: int = -1, transformer_depth: int = 1,
-                 context_dim: int = None, legacy: bool = True) -> SDUNetPlan:
+                 context_dim: int = None, legacy: bool = True, use_linear_in_transformer: bool = False) -> SDUNetPlan:
     assert context_dim is not None, "the latent UNet is built with use_spatial_transformer=True: context_dim is required"
     assert (num_heads == -1) != (num_head_channels == -1), "set exactly one of num_heads / num_head_channels"
     emb = model_channels * 4
@@ -160,7 +163,7 @@ def sd_unet_plan(in_channels: int, model_channels: int, out_channels: int, num_r
 
     def transformer(prefix, ch):
         h, d = heads_for(ch)
-        return SDTransformerSpec(prefix, ch, h, d, context_dim, transformer_depth)
+        return SDTransformerSpec(prefix, ch, h, d, context_dim, transformer_depth, bool(use_linear_in_transformer))
 
     plan.input_blocks.append([SDStemSpec("input_blocks.0.0", in_channels, model_channels)])
     chans = [model_channels]
@@ -199,3 +202,7 @@ def sd_unet_plan(in_channels: int, model_channels: int, out_channels: int, num_r
 
 SD_V1 = dict(in_channels=4, out_channels=4, model_channels=320, attention_resolutions=(4, 2, 1), num_res_blocks=2,
              channel_mult=(1, 2, 4, 4), num_heads=8, transformer_depth=1, context_dim=768, legacy=False)
+# Stable Diffusion 2.0 / 2.1 (Stability's v2-inference*.yaml): 64-wide heads, linear proj_in / proj_out, OpenCLIP ViT-H/14 context
+SD_V2 = dict(in_channels=4, out_channels=4, model_channels=320, attention_resolutions=(4, 2, 1), num_res_blocks=2,
+             channel_mult=(1, 2, 4, 4), num_head_channels=64, use_linear_in_transformer=True, transformer_depth=1, context_dim=1024,
+             legacy=False)

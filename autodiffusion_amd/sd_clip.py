@@ -13,8 +13,10 @@ attention output's dead rows are zeros) and never meet a live row: every launch 
 reads and writes rows < T only.
   entry      adm_clip_embed: token_embedding[ids] + position_embedding[:T], one rounding
   layer      layernorm -> fused q | k | v 1x1 -> adm_attention_causal -> out_proj 1x1 (+x)
-             layernorm -> fc1 1x1 -> adm_quick_gelu -> fc2 1x1 (+x)
+             layernorm -> fc1 1x1 -> adm_quick_gelu (hidden_act "gelu": adm_gelu, the exact GELU) -> fc2 1x1 (+x)
   exit       adm_layernorm_f32out: final_layer_norm of the T live rows as fp32 [N, T, C] (no second rounding)
+``FrozenOpenCLIPEmbedder`` (Stable Diffusion 2.x: OpenCLIP ViT-H/14's text tower, exact GELU, the "penultimate" exit that runs all
+layers but the last before ``ln_final``, pad id 0) is the same engine under OpenCLIP's state-dict keys.
 Tokenisation is host plumbing: ``transformers.CLIPTokenizer`` from a LOCAL directory, imported lazily, or any callable with its
 interface passed as ``tokenizer=``; integer tensors [N, T] of token ids enter ``forward`` directly.  Nothing is ever fetched.
 Attention masks are not built (the reference passes no mask: pad tokens are attended).
@@ -80,13 +82,14 @@ def _run_layers(x, layers, plan, n, rows, attend):
     """The pre-LN encoder layers of both towers on x 16-bit [maps, h, w, C] holding [n, rows, C]; attend(qkv [n, rows, 3 C]) is
     the tower's attention -> [n, rows, C]."""
     c, inner, eps = plan.hidden_size, plan.intermediate_size, plan.layer_norm_eps
+    act = ops.gelu if getattr(plan, "hidden_act", "quick_gelu") == "gelu" else ops.quick_gelu
     for L in layers:
         y = ops.layernorm(x, *L["ln1"], eps=eps)
         qkv = ops.conv(y, L["wqkv"], L["bqkv"], 3 * c, 1).view(n, rows, 3 * c)
         a = attend(qkv)
         x = ops.conv(a.view(x.shape), L["wo"], L["bo"], c, 1, res=x)
         y = ops.layernorm(x, *L["ln2"], eps=eps)
-        u = ops.quick_gelu(ops.conv(y, L["w1"], L["b1"], inner, 1))
+        u = act(ops.conv(y, L["w1"], L["b1"], inner, 1))
         x = ops.conv(u, L["w2"], L["b2"], c, 1, res=x)
     return x
 
@@ -101,6 +104,8 @@ class CLIPTextPlan:
     max_position_embeddings: int = 77
     layer_norm_eps: float = 1e-5
     projection_dim: int = 0   # > 0: ``text_projection.weight`` [E, C] of CLIPTextModelWithProjection / CLIPModel (absent in SD checkpoints)
+    hidden_act: str = "quick_gelu"   # "gelu": the exact GELU (OpenCLIP's towers)
+    run_layers: int = 0       # > 0: only the first run_layers encoder layers run before final_layer_norm (all are still loaded)
 
     def param_shapes(self) -> "OrderedDict[str, tuple]":
         """name -> shape under ``text_model.``, in CLIPTextModel's state-dict order (``text_projection.weight`` last)."""
@@ -133,9 +138,14 @@ class CLIPTextTransformer(HipModule):
     ZERO_INIT = ()
 
     def __init__(self, vocab_size, hidden_size, intermediate_size, num_hidden_layers, num_attention_heads,
-                 max_position_embeddings=77, layer_norm_eps=1e-5, projection_dim=0):
+                 max_position_embeddings=77, layer_norm_eps=1e-5, projection_dim=0, hidden_act="quick_gelu", run_layers=None):
+        if hidden_act not in ("quick_gelu", "gelu"):
+            raise ValueError(f"CLIP text transformer: hidden_act {hidden_act!r} (\"quick_gelu\" or \"gelu\")")
+        if run_layers is not None and not 1 <= int(run_layers) <= int(num_hidden_layers):
+            raise ValueError(f"CLIP text transformer: run_layers {run_layers} outside 1 .. {num_hidden_layers}")
         plan = CLIPTextPlan(int(vocab_size), int(hidden_size), int(intermediate_size), int(num_hidden_layers),
-                            int(num_attention_heads), int(max_position_embeddings), float(layer_norm_eps), int(projection_dim or 0))
+                            int(num_attention_heads), int(max_position_embeddings), float(layer_norm_eps), int(projection_dim or 0),
+                            hidden_act, int(run_layers or 0))
         if plan.projection_dim < 0:
             raise ValueError("CLIP text transformer: projection_dim must be positive (or 0 / None for no text_projection)")
         if plan.hidden_size != 64 * plan.num_attention_heads:
@@ -200,7 +210,8 @@ class CLIPTextTransformer(HipModule):
             x = ops.clip_embed(ids, pr.tok, pr.pos, rows, self.compute_dtype).view(n, hh, ww, c)
             # one attention output for all layers: its dead rows are zeroed once and never written
             a = torch.zeros((n, rows, c), dtype=self.compute_dtype, device=x.device)
-            x = _run_layers(x, pr.layers, plan, n, rows, lambda qkv: ops.attention_causal(qkv, heads, t, out=a))
+            layers = pr.layers[:plan.run_layers] if plan.run_layers else pr.layers
+            x = _run_layers(x, layers, plan, n, rows, lambda qkv: ops.attention_causal(qkv, heads, t, out=a))
             return ops.layernorm_f32out(x.view(n, rows, c), t, *pr.lnf, eps=eps)
 
     def pooled(self, ids):
@@ -314,6 +325,88 @@ class FrozenCLIPEmbedder:
 
     def __call__(self, text):
         return self.forward(text)
+
+
+# ====================================================================== the SD 2.x cond stage
+# OpenCLIP ViT-H/14 (laion2b_s32b_b79k), the text tower: CLIP's BPE vocabulary, 16 heads of 64, the exact GELU
+OPENCLIP_VIT_H14_TEXT = dict(vocab_size=49408, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16,
+                             max_position_embeddings=77, hidden_act="gelu")
+_OPENCLIP_IGNORED = ("text_projection", "logit_scale", "attn_mask")   # and visual.*: not on the path to the UNet's context
+
+
+def openclip_pad(ids, eos: int):
+    """OpenCLIP's tokenizer pads with id 0 where CLIP's pads with end-of-text: every id after the first ``eos`` of a row becomes 0
+    (a row without ``eos`` is left as it is).  The causal attention lets the pad rows see their prefix and the UNet attends to
+    all 77 rows, so the pad id changes the context."""
+    ids = torch.as_tensor(ids).clone()
+    is_eos = ids == int(eos)
+    after = (is_eos.to(torch.int64).cumsum(dim=-1) - is_eos.to(torch.int64)) > 0
+    ids[after] = 0
+    return ids
+
+
+class FrozenOpenCLIPEmbedder(FrozenCLIPEmbedder):
+    """Stable Diffusion 2.x's cond stage (Stability's ldm/modules/encoders/modules.py FrozenOpenCLIPEmbedder): OpenCLIP's text
+    tower up to ``ln_final`` of the last (``layer="last"``) or the last-but-one (``"penultimate"``: ``text_transformer_forward``
+    with ``layer_idx = 1``) resblock.  ``version`` names the pretrained tag there; here, as in FrozenCLIPEmbedder, it is only read
+    as a LOCAL tokenizer directory when strings arrive (OpenCLIP's BPE is CLIP's; the padding is rewritten by ``openclip_pad``).
+    ``load_state_dict`` takes the ``cond_stage_model.*`` tensors of an SD 2 checkpoint, prefix stripped: ``model.*``."""
+
+    LAYERS = ("last", "penultimate")
+
+    def __init__(self, arch="ViT-H-14", version="laion2b_s32b_b79k", device="cuda", max_length=77, freeze=True, layer="last",
+                 tokenizer=None, config=None):
+        if layer not in self.LAYERS:
+            raise ValueError(f"FrozenOpenCLIPEmbedder: layer {layer!r} (one of {self.LAYERS})")
+        if config is None:
+            if arch != "ViT-H-14":
+                raise NotImplementedError(f"FrozenOpenCLIPEmbedder: arch {arch!r}; pass \"ViT-H-14\" or config= (the tower's arguments)")
+            config = OPENCLIP_VIT_H14_TEXT
+        config = dict(config)
+        config.setdefault("hidden_act", "gelu")
+        if layer == "penultimate":
+            if int(config["num_hidden_layers"]) < 2:
+                raise ValueError("FrozenOpenCLIPEmbedder: layer=\"penultimate\" needs at least two layers")
+            config["run_layers"] = int(config["num_hidden_layers"]) - 1
+        self.arch, self.layer = arch, layer
+        super().__init__(version, device, max_length, tokenizer, config)
+
+    def state_dict(self):
+        raise NotImplementedError("FrozenOpenCLIPEmbedder: state_dict() in OpenCLIP's layout is not built; the tower's own is "
+                                  ".transformer.state_dict()")
+
+    def load_state_dict(self, sd, strict=True):
+        """``model.token_embedding.weight``, ``model.positional_embedding``, ``model.transformer.resblocks.N.*``, ``model.ln_final.*``
+        (remapped by ``openai_to_hf``); ``model.text_projection``, ``model.logit_scale``, ``model.attn_mask`` and ``model.visual.*``
+        are not on this path and are ignored, also under ``strict``."""
+        inner, unexpected = {}, []
+        for k, v in sd.items():
+            if not k.startswith("model."):
+                unexpected.append(k)
+                continue
+            name = k[len("model."):]
+            if name in _OPENCLIP_IGNORED or name.startswith("visual."):
+                continue
+            if name.startswith("transformer.resblocks.") or name in ("token_embedding.weight", "positional_embedding", "ln_final.weight",
+                                                                     "ln_final.bias"):
+                inner[name] = v
+            else:
+                unexpected.append(k)
+        if strict and unexpected:
+            raise RuntimeError(f"Error(s) in loading state_dict for FrozenOpenCLIPEmbedder: unexpected keys {unexpected[:5]}...")
+        self.transformer.load_state_dict(openai_to_hf(inner)[1], strict=strict)
+        return [], unexpected
+
+    def forward(self, text):
+        if torch.is_tensor(text):
+            tokens = text          # ids enter unchanged: the caller pads them
+        else:
+            if isinstance(text, tuple):
+                text = list(text)
+            tokens = self.tokenizer(text, truncation=True, max_length=self.max_length, return_length=True,
+                                    return_overflowing_tokens=False, padding="max_length", return_tensors="pt")["input_ids"]
+            tokens = openclip_pad(tokens, self.transformer.plan.vocab_size - 1)   # <|endoftext|> is the vocabulary's last id
+        return self.transformer(tokens.to(self.device))
 
 
 # ====================================================================== the image tower

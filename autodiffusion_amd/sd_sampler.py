@@ -9,6 +9,10 @@ apply_model(x, t, c)`` -- e.g. ``LatentDiffusion`` below around the HIP latent U
 
 Every update (classifier-free-guidance combine, PLMS multistep blend, pred_x0, x_prev) is ONE ``adm_sd_step`` launch; the
 per-step scalars are computed on the host in float32 exactly as the reference's float32 tables hold them.
+
+A model whose output is not eps (``model.parameterization`` "v" -- Stable Diffusion 2.x -- or "x0"; a model without the attribute
+predicts eps) goes through the ``_p`` twins of the three fused steps: the guidance combine is applied to the raw
+output and the conversion to eps / to the data prediction happens inside the same launch.
 """
 from __future__ import annotations
 
@@ -75,7 +79,10 @@ class LatentDiffusion:
     parameterization = "eps"
 
     def __init__(self, unet, timesteps=1000, beta_schedule="linear", linear_start=0.00085, linear_end=0.0120,
-                 cosine_s=8e-3, device=None, first_stage=None, scale_factor=0.18215, cond_stage=None):
+                 cosine_s=8e-3, device=None, first_stage=None, scale_factor=0.18215, cond_stage=None, parameterization="eps"):
+        if parameterization not in _lib.PARAMS:
+            raise ValueError(f"LatentDiffusion: parameterization {parameterization!r} (one of {sorted(_lib.PARAMS)})")
+        self.parameterization = parameterization   # what the UNet's output is: ddpm.py's "eps" / "x0", SD 2.x's "v"
         betas = make_beta_schedule(beta_schedule, timesteps, linear_start=linear_start, linear_end=linear_end,
                                    cosine_s=cosine_s)
         ac = np.cumprod(1.0 - betas, axis=0)
@@ -220,10 +227,18 @@ def _f32ptr(t, name):
     return t.data_ptr()
 
 
-def sd_step(x, eps, batch, cfg_scale, weights, hist, a_t, a_prev, sigma, noise=None, want_e=True):
+def _param_id(param, who):
+    if param not in _lib.PARAMS:
+        raise ValueError(f"{who}: param {param!r} (one of {sorted(_lib.PARAMS)})")
+    return _lib.PARAMS[param]
+
+
+def sd_step(x, eps, batch, cfg_scale, weights, hist, a_t, a_prev, sigma, noise=None, want_e=True, param="eps"):
     """One fused update.  eps: model output, [2*batch, ...] (unconditional half first) under guidance, else [batch, ...].
     weights/hist: multistep blend e' = w[0]*e + sum w[k]*hist[k-1].  a_t, a_prev, sigma: float32 scalars.
+    param: what the model output is ("eps", "x0", "v"); anything but "eps" goes through adm_sd_step_p, e is eps in every case.
     Returns (x_prev, pred_x0, e)."""
+    pid = _param_id(param, "sd_step")
     guided = eps.shape[0] == 2 * batch
     if not guided and eps.shape[0] != batch:
         raise AdmError(f"sd_step: model output batch {eps.shape[0]} is neither {batch} nor {2 * batch}")
@@ -243,10 +258,14 @@ def sd_step(x, eps, batch, cfg_scale, weights, hist, a_t, a_prev, sigma, noise=N
     co.dir_coef = float(np.sqrt(one - a_prev - sigma * sigma))
     co.sigma = float(sigma)
     h = list(hist) + [None] * (3 - len(hist))
-    check(_lib.load().adm_sd_step(_f32ptr(x, "x"), _f32ptr(eu, "eps"), _f32ptr(ec, "eps"), _f32ptr(h[0], "old_eps"),
-                                  _f32ptr(h[1], "old_eps"), _f32ptr(h[2], "old_eps"), _f32ptr(noise, "noise"),
-                                  x_prev.data_ptr(), pred.data_ptr(), None if e_out is None else e_out.data_ptr(),
-                                  x.numel(), C.byref(co), torch.cuda.current_stream().cuda_stream), "adm_sd_step")
+    args = (_f32ptr(x, "x"), _f32ptr(eu, "eps"), _f32ptr(ec, "eps"), _f32ptr(h[0], "old_eps"), _f32ptr(h[1], "old_eps"),
+            _f32ptr(h[2], "old_eps"), _f32ptr(noise, "noise"), x_prev.data_ptr(), pred.data_ptr(),
+            None if e_out is None else e_out.data_ptr(), x.numel(), C.byref(co))
+    stream = torch.cuda.current_stream().cuda_stream
+    if pid == 0:
+        check(_lib.load().adm_sd_step(*args, stream), "adm_sd_step")
+    else:
+        check(_lib.load().adm_sd_step_p(*args, stream, pid), "adm_sd_step_p")
     return x_prev, pred, e_out
 
 
@@ -309,6 +328,11 @@ class _LatentSampler:
         self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev = make_ddim_sampling_parameters(
             self.alphas_cumprod_host, self.ddim_timesteps, ddim_eta, verbose)
         self.ddim_sqrt_one_minus_alphas = np.sqrt(np.float32(1.0) - self.ddim_alphas)
+
+    @property
+    def _param(self):
+        """What the model's output is; a model without the attribute (the reference's toy and v1 models) predicts eps."""
+        return getattr(self.model, "parameterization", "eps")
 
     def _unsupported(self, **kw):
         bad = [k for k, v in kw.items() if v]
@@ -454,7 +478,7 @@ class DDIMSampler(_LatentSampler):
             sigma = self.ddim_sigmas[index]
             noise = torch.randn(shape, device=device) * temperature if sigma != 0 else None  # ddim.py:198 noise_like
             img, pred_x0, _ = sd_step(img, eps, b, unconditional_guidance_scale, (1.0,), (), self.ddim_alphas[index],
-                                      self.ddim_alphas_prev[index], sigma, noise, want_e=False)
+                                      self.ddim_alphas_prev[index], sigma, noise, want_e=False, param=self._param)
             if callback:
                 callback(i)
             if img_callback:
@@ -495,7 +519,7 @@ class DDIMSampler(_LatentSampler):
             sigma = self.ddim_sigmas[index]
             noise = torch.randn(img.shape, device=device) if sigma != 0 else None
             img, _, _ = sd_step(img, eps, b, unconditional_guidance_scale, (1.0,), (), self.ddim_alphas[index],
-                                self.ddim_alphas_prev[index], sigma, noise, want_e=False)
+                                self.ddim_alphas_prev[index], sigma, noise, want_e=False, param=self._param)
         return img
 
 
@@ -519,6 +543,16 @@ class PLMSSampler(_LatentSampler):
             raise AdmError("PLMSSampler: a prompt_mask entry of 0 needs unconditional_conditioning")
         return pm
 
+    def _plms_second(self, img, x_mid, out2, b, scale, e_t, a_t, a_prev, sigma, t_next, param):
+        """The second half of the first step: e' = (e_t + e_next) / 2 applied to img.  Under "v" / "x0" SD 2's plms.py converts the
+        second output at the point and time it was evaluated at (x_mid, t_next), not at (img, t): one adm_sd_step_p launch for
+        that eps (its x_prev is not used), then the eps blend, already guided, as an unguided adm_sd_step."""
+        if param == "eps":
+            return sd_step(img, out2, b, scale, (0.5, 0.5), (e_t,), a_t, a_prev, sigma, want_e=False)
+        a_next = self.alphas_cumprod_host[t_next]
+        _, _, e_next = sd_step(x_mid, out2, b, scale, (1.0,), (), a_next, a_next, 0.0, param=param)
+        return sd_step(img, e_next, b, 1.0, (0.5, 0.5), (e_t,), a_t, a_prev, sigma, want_e=False)
+
     def _loop(self, cond, shape, x_T, callback, img_callback, log_every_t, temperature, unconditional_guidance_scale,
               unconditional_conditioning):
         device, img = self._start(shape, x_T)
@@ -529,7 +563,7 @@ class PLMSSampler(_LatentSampler):
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         uc, scale = unconditional_conditioning, unconditional_guidance_scale
         self._begin(cond, uc, scale)
-        old_eps = []
+        old_eps, param = [], self._param
         for i, step in enumerate(time_range):
             index = total - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
@@ -544,12 +578,12 @@ class PLMSSampler(_LatentSampler):
             scale = 1.0 if un else unconditional_guidance_scale
             eps = self._eps(img, ts, un)
             if len(old_eps) == 0:    # pseudo improved Euler (2nd order): a second model call at the predicted point
-                x_mid, _, e_t = sd_step(img, eps, b, scale, (1.0,), (), a_t, a_prev, sigma)
+                x_mid, _, e_t = sd_step(img, eps, b, scale, (1.0,), (), a_t, a_prev, sigma, param=param)
                 eps2 = self._eps(x_mid, ts_next, un)
-                img, pred_x0, _ = sd_step(img, eps2, b, scale, (0.5, 0.5), (e_t,), a_t, a_prev, sigma, want_e=False)
+                img, pred_x0, _ = self._plms_second(img, x_mid, eps2, b, scale, e_t, a_t, a_prev, sigma, int(ts_next[0]), param)
             else:                    # Adams-Bashforth of order 2 / 3 / 4 over the kept eps history (newest first)
                 w = {1: (3 / 2, -1 / 2), 2: (23 / 12, -16 / 12, 5 / 12), 3: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}[len(old_eps)]
-                img, pred_x0, e_t = sd_step(img, eps, b, scale, w, tuple(reversed(old_eps)), a_t, a_prev, sigma)
+                img, pred_x0, e_t = sd_step(img, eps, b, scale, w, tuple(reversed(old_eps)), a_t, a_prev, sigma, param=param)
             old_eps.append(e_t)
             if len(old_eps) >= 4:
                 old_eps.pop(0)
@@ -594,18 +628,23 @@ class NoiseScheduleVP:
         return lm - 0.5 * float(np.log(1.0 - np.exp(2.0 * lm)))
 
 
-def dpm_step(x, eps, batch, cfg_scale, m_prev, sigma_s, alpha_s, a, b0, b1):
-    """One fused multistep update; returns (x_next, m) with m the data prediction at the current point."""
+def dpm_step(x, eps, batch, cfg_scale, m_prev, sigma_s, alpha_s, a, b0, b1, param="eps"):
+    """One fused multistep update; returns (x_next, m) with m the data prediction at the current point.  param: what the model
+    output is ("eps", "x0", "v"); anything but "eps" goes through adm_dpm_step_p."""
+    pid = _param_id(param, "dpm_step")
     guided = eps.shape[0] == 2 * batch
     if not guided and eps.shape[0] != batch:
         raise AdmError(f"dpm_step: model output batch {eps.shape[0]} is neither {batch} nor {2 * batch}")
     eps = eps.contiguous()
     eu, ec = (eps[:batch], eps[batch:]) if guided else (None, eps)
     x_next, m = torch.empty_like(x), torch.empty_like(x)
-    check(_lib.load().adm_dpm_step(_f32ptr(x, "x"), _f32ptr(eu, "eps"), _f32ptr(ec, "eps"), _f32ptr(m_prev, "model_prev"),
-                                   x_next.data_ptr(), m.data_ptr(), x.numel(), float(cfg_scale), float(sigma_s),
-                                   float(alpha_s), float(a), float(b0), float(b1),
-                                   torch.cuda.current_stream().cuda_stream), "adm_dpm_step")
+    args = (_f32ptr(x, "x"), _f32ptr(eu, "eps"), _f32ptr(ec, "eps"), _f32ptr(m_prev, "model_prev"), x_next.data_ptr(), m.data_ptr(),
+            x.numel(), float(cfg_scale), float(sigma_s), float(alpha_s), float(a), float(b0), float(b1))
+    stream = torch.cuda.current_stream().cuda_stream
+    if pid == 0:
+        check(_lib.load().adm_dpm_step(*args, stream), "adm_dpm_step")
+    else:
+        check(_lib.load().adm_dpm_step_p(*args, stream, pid), "adm_dpm_step_p")
     return x_next, m
 
 
@@ -666,18 +705,20 @@ class DPMSolverSampler(_LatentSampler):
             else:
                 b0, b1 = -phi, 0.0
             x, m = dpm_step(x, eps_at(x, s), batch_size, scale, m_prev if step_order == 2 else None,
-                            ns.marginal_std(s), ns.marginal_alpha(s), a, b0, b1)
+                            ns.marginal_std(s), ns.marginal_alpha(s), a, b0, b1, param=self._param)
             m_prev, lam_prev = m, lam_s
         return x, None
 
 
 # ------------------------------------------------------------------ UniPC
-def unipc_step(x_eval, eps, batch, cfg_scale, x_base, hist, sigma_s, alpha_s, corr=None, pred=None):
+def unipc_step(x_eval, eps, batch, cfg_scale, x_base, hist, sigma_s, alpha_s, corr=None, pred=None, param="eps"):
     """One model evaluation of UniPC on the latents (adm_unipc_step): m = the guided data prediction at x_eval; corr = (ac, c0, c1,
     c2, c3) asks for x_corr = ac x_base + c0 m + c1 h1 + c2 h2 + c3 h3, pred = (ap, p0, p1, p2) for x_pred = ap x_c + p0 m + p1 h1 +
-    p2 h2 with x_c = x_corr (x_eval without corr).  hist: up to three earlier model values, newest first.
+    p2 h2 with x_c = x_corr (x_eval without corr).  hist: up to three earlier model values, newest first.  param: what the model
+    output is ("eps", "x0", "v"); anything but "eps" goes through adm_unipc_step_p.
     -> (m, x_corr | None, x_pred | None)"""
     from ._lib import UnipcArgs
+    pid = _param_id(param, "unipc_step")
     guided = eps.shape[0] == 2 * batch
     if not guided and eps.shape[0] != batch:
         raise AdmError(f"unipc_step: model output batch {eps.shape[0]} is neither {batch} nor {2 * batch}")
@@ -702,7 +743,10 @@ def unipc_step(x_eval, eps, batch, cfg_scale, x_base, hist, sigma_s, alpha_s, co
         a.ac, a.c0, a.c1, a.c2, a.c3 = (float(v) for v in corr)
     if pred is not None:
         a.ap, a.p0, a.p1, a.p2 = (float(v) for v in pred)
-    check(_lib.load().adm_unipc_step(C.byref(a), torch.cuda.current_stream().cuda_stream, 0), "adm_unipc_step")
+    if pid == 0:
+        check(_lib.load().adm_unipc_step(C.byref(a), torch.cuda.current_stream().cuda_stream, 0), "adm_unipc_step")
+    else:
+        check(_lib.load().adm_unipc_step_p(C.byref(a), torch.cuda.current_stream().cuda_stream, pid), "adm_unipc_step_p")
     return m, x_corr, x_pred
 
 
@@ -757,7 +801,7 @@ class UniPCSampler(_LatentSampler):
             corr = None if e["corr"] is None else (e["corr"][0], *e["corr"][1])
             pred = (e["pred"][0], *e["pred"][1])
             m, x_corr, x_pred = unipc_step(x, eps, batch_size, scale, x_base if corr else None, hist[:depth],
-                                           ns.marginal_std(ts[j]), ns.marginal_alpha(ts[j]), corr, pred)
+                                           ns.marginal_std(ts[j]), ns.marginal_alpha(ts[j]), corr, pred, param=self._param)
             if record is not None:
                 record.append(dict(j=j, t=ts[j], x=x, eps=eps, x_base=x_base if corr else None, hist=list(hist[:depth]), corr=corr,
                                    pred=pred, sigma=ns.marginal_std(ts[j]), alpha=ns.marginal_alpha(ts[j]), m=m, x_corr=x_corr,

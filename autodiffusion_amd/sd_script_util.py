@@ -13,8 +13,8 @@ import torch
 from . import dist_util, logger, sd_clip
 from .inception import InceptionV3
 from .script_util import str2bool
-from .sd_arch import SD_V1
-from .sd_clip import CLIP_VIT_L14_TEXT, FrozenCLIPEmbedder
+from .sd_arch import SD_V1, SD_V2
+from .sd_clip import CLIP_VIT_L14_TEXT, OPENCLIP_VIT_H14_TEXT, FrozenCLIPEmbedder, FrozenOpenCLIPEmbedder
 from .sd_sampler import DDIMSampler, DPMSolverSampler, LatentDiffusion, PLMSSampler, UniPCSampler
 from .sd_unet import UNetModel
 from .sd_vae import SD_V1_VAE, AutoencoderKL
@@ -27,6 +27,12 @@ TINY_VAE = dict(ddconfig=dict(ch=32, out_ch=3, ch_mult=(1, 2, 4), num_res_blocks
                               resolution=32, z_channels=4), embed_dim=4)
 TINY_CLIP = dict(vocab_size=512, hidden_size=128, intermediate_size=512, num_hidden_layers=1, num_attention_heads=2,
                  max_position_embeddings=77)
+# --synthetic tiny2: the same sizes in the Stable Diffusion 2.x form -- 64-wide heads named by num_head_channels, linear proj_in /
+# proj_out, a two-layer OpenCLIP-style tower (exact GELU, penultimate exit, pad id 0) and a v-predicting UNet
+TINY2_UNET = dict({k: v for k, v in TINY_UNET.items() if k != "num_heads"}, num_head_channels=64, use_linear_in_transformer=True)
+TINY2_CLIP = dict(vocab_size=512, hidden_size=128, intermediate_size=512, num_hidden_layers=2, num_attention_heads=2,
+                  max_position_embeddings=77, hidden_act="gelu")
+COND_STAGES = {"FrozenCLIPEmbedder": FrozenCLIPEmbedder, "FrozenOpenCLIPEmbedder": FrozenOpenCLIPEmbedder}
 
 # ------------------------------------------------------------------ the flags sd_img2img.py and sd_inpaint.py share
 SD_SAMPLING_FLAGS = {
@@ -43,7 +49,8 @@ SD_SAMPLING_FLAGS = {
     "--tokenizer_dir": dict(type=str, default="", help="LOCAL directory of the transformers CLIP tokenizer (nothing is fetched)"),
     "--prompt_ids": dict(type=str, default="", help=".npy int64 [num, T] token ids (num = 1 or --n_samples); replaces --prompt"),
     "--torso": dict(choices=["bf16", "fp16"], default="bf16", help="16-bit type of activations and weights between kernels"),
-    "--synthetic": dict(choices=["tiny", "v1"], default="", help="build the networks with randomize_() instead of reading --ckpt"),
+    "--synthetic": dict(choices=["tiny", "v1", "tiny2", "v2"], default="",
+                        help="build the networks with randomize_() instead of reading --ckpt (tiny2 / v2: the SD 2.x family, v-prediction)"),
     "--use_timestep": dict(type=str, default="", help="'[t0, t1, ...]': a searched schedule of --ddim_steps timesteps"),
     "--side_multiple": dict(type=int, default=64, help="an image FILE is resized down to a multiple of this many pixels"),
 }
@@ -145,16 +152,19 @@ def load_images(path, n_samples, side_multiple, prog):
 class EmptyPromptTokenizer:
     """Stands in for the CLIP tokenizer in a --prompt_ids run, which has one string left to tokenise: the empty prompt of
     classifier-free guidance.  CLIP's tokenizer turns "" into <|startoftext|> followed by <|endoftext|> up to max_length (its pad
-    token is <|endoftext|>), and those two are the last two ids of its vocabulary (49406 and 49407 of 49408)."""
+    token is <|endoftext|>), and those two are the last two ids of its vocabulary (49406 and 49407 of 49408).  pad: the id behind the
+    first <|endoftext|> (None: <|endoftext|> itself, CLIP's; 0 for OpenCLIP's tokenizer: [bos, eos, 0, 0, ...])."""
 
-    def __init__(self, vocab_size, prog="sd_search_ea.py"):
+    def __init__(self, vocab_size, prog="sd_search_ea.py", pad=None):
         self.bos, self.eos, self.prog = int(vocab_size) - 2, int(vocab_size) - 1, prog
+        self.pad = self.eos if pad is None else int(pad)
 
     def __call__(self, text, max_length, **kw):
         if any(t != "" for t in text):
             raise SystemExit(f"{self.prog}: a --prompt_ids run has no tokenizer for strings; give --tokenizer_dir")
-        ids = torch.full((len(text), max_length), self.eos, dtype=torch.int64)
+        ids = torch.full((len(text), max_length), self.pad, dtype=torch.int64)
         ids[:, 0] = self.bos
+        ids[:, 1:2] = self.eos
         return {"input_ids": ids}
 
 
@@ -165,18 +175,32 @@ def build_model(opt, device, prompt_len=None, with_encoder=False):
     with_encoder: the first stage also gets its image encoder."""
     unet_cfg = dict(image_size=32, use_spatial_transformer=True, **SD_V1)
     vae_cfg, clip_cfg, ld_cfg = dict(SD_V1_VAE), dict(config=CLIP_VIT_L14_TEXT), {}
+    cond_cls = FrozenCLIPEmbedder
     if opt.synthetic == "tiny":
         unet_cfg = dict(image_size=32, use_spatial_transformer=True, **TINY_UNET)
         vae_cfg, clip_cfg = dict(TINY_VAE), dict(config=TINY_CLIP)
+    elif opt.synthetic == "tiny2":
+        unet_cfg = dict(image_size=32, use_spatial_transformer=True, **TINY2_UNET)
+        vae_cfg, clip_cfg, cond_cls = dict(TINY_VAE), dict(config=TINY2_CLIP, layer="penultimate"), FrozenOpenCLIPEmbedder
+        ld_cfg = dict(parameterization="v")
+    elif opt.synthetic == "v2":
+        unet_cfg = dict(image_size=32, use_spatial_transformer=True, **SD_V2)
+        clip_cfg, cond_cls = dict(config=OPENCLIP_VIT_H14_TEXT, layer="penultimate"), FrozenOpenCLIPEmbedder
+        ld_cfg = dict(parameterization="v")
     elif not opt.synthetic and opt.config and os.path.isfile(opt.config):
         import yaml
         with open(opt.config, "r", encoding="utf-8") as f:
             params = yaml.safe_load(f)["model"]["params"]
-        ld_cfg = {k: params[k] for k in ("timesteps", "linear_start", "linear_end", "scale_factor") if k in params}
+        ld_cfg = {k: params[k] for k in ("timesteps", "linear_start", "linear_end", "scale_factor", "parameterization") if k in params}
         unet_cfg = dict(params["unet_config"].get("params") or {})
         vae_cfg = dict(params["first_stage_config"].get("params") or {})
         clip_cfg = dict(params["cond_stage_config"].get("params") or {})
         clip_cfg.pop("device", None)
+        clip_cfg.pop("freeze", None)
+        target = str(params["cond_stage_config"].get("target") or "FrozenCLIPEmbedder")
+        if target.rsplit(".", 1)[-1] not in COND_STAGES:
+            raise SystemExit(f"build_model: cond_stage_config.target {target!r} is not built (one of {sorted(COND_STAGES)})")
+        cond_cls = COND_STAGES[target.rsplit(".", 1)[-1]]
         logger.log(f"model configuration from {opt.config}")
     elif not opt.synthetic:
         logger.log(f"--config {opt.config} is not a file: using the SD-v1 constants of the package")
@@ -186,9 +210,9 @@ def build_model(opt, device, prompt_len=None, with_encoder=False):
     vae = AutoencoderKL(**vae_cfg, with_encoder=with_encoder).set_torso(opt.torso)
     if prompt_len is not None and not opt.tokenizer_dir:
         clip_cfg["max_length"] = int(prompt_len)
-    clip = FrozenCLIPEmbedder(device="cpu", **clip_cfg).set_torso(opt.torso)
+    clip = cond_cls(device="cpu", **clip_cfg).set_torso(opt.torso)
     if prompt_len is not None and not opt.tokenizer_dir:
-        clip._tokenizer = EmptyPromptTokenizer(clip.transformer.plan.vocab_size)
+        clip._tokenizer = EmptyPromptTokenizer(clip.transformer.plan.vocab_size, pad=0 if cond_cls is FrozenOpenCLIPEmbedder else None)
     if opt.synthetic:
         unet.randomize_(1234)
         vae.randomize_(4321)
@@ -222,8 +246,8 @@ def build_inception(opt, device, prog="sd_search_ea.py"):
 
 
 def build_clip_scorer(opt, device, prompt_len=None):
-    """--clip_ckpt: the CLIPScorer of both towers from one file (the tiny towers under --synthetic tiny)."""
-    tiny = opt.synthetic == "tiny"
+    """--clip_ckpt: the CLIPScorer of both towers from one file (the tiny towers under --synthetic tiny / tiny2)."""
+    tiny = opt.synthetic in ("tiny", "tiny2")
     return sd_clip.build_clip_scorer(dist_util.load_state_dict(opt.clip_ckpt),
                                      sd_clip.CLIP_TINY_VISION if tiny else None, sd_clip.CLIP_TINY_TEXT_PROJ if tiny else None,
                                      device=device, torso=opt.torso, tokenizer_dir=opt.tokenizer_dir or None,

@@ -73,7 +73,7 @@ class UNetModel(HipModule):
                  num_classes=None, use_checkpoint=False, use_fp16=False, num_heads=-1, num_head_channels=-1,
                  num_heads_upsample=-1, use_scale_shift_norm=False, resblock_updown=False,
                  use_new_attention_order=False, use_spatial_transformer=False, transformer_depth=1, context_dim=None,
-                 n_embed=None, legacy=True):
+                 n_embed=None, legacy=True, use_linear_in_transformer=False):
         unsupported = dict(conv_resample=not conv_resample, dims=dims != 2, num_classes=num_classes is not None,
                            use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown,
                            use_spatial_transformer=not use_spatial_transformer, n_embed=n_embed is not None,
@@ -85,7 +85,7 @@ class UNetModel(HipModule):
         plan = sd_unet_plan(in_channels, model_channels, out_channels, num_res_blocks, tuple(attention_resolutions),
                             tuple(channel_mult), num_heads, num_head_channels, transformer_depth,
                             int(context_dim) if not isinstance(context_dim, (list, tuple)) else int(context_dim[0]),
-                            legacy)
+                            legacy, bool(use_linear_in_transformer))
         super().__init__(plan, use_fp16)
         self.image_size = image_size
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
@@ -121,6 +121,7 @@ class UNetModel(HipModule):
                 pr.blocks[p] = blocks.upsample_weights(P, f32, pack, f"{p}.conv", self.compute_dtype)
             elif isinstance(b, SDTransformerSpec):
                 h, dh, dp = b.heads, b.d_head, _padded_head(b.d_head)
+                # proj_in / proj_out: [out, in, 1, 1] or, with use_linear_in_transformer, nn.Linear's [out, in] -- one packed 1x1 conv
                 d = dict(g=f32(f"{p}.norm.weight"), b=f32(f"{p}.norm.bias"), dp=dp,
                          w_in=pack(P[f"{p}.proj_in.weight"]), b_in=f32(f"{p}.proj_in.bias"),
                          w_out=pack(P[f"{p}.proj_out.weight"]), b_out=f32(f"{p}.proj_out.bias"), layers=[])

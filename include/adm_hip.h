@@ -307,6 +307,32 @@ int adm_dpm_step(const float* x, const float* eps_uncond, const float* eps_cond,
                  float* m_out, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float a, float b0, float b1,
                  void* stream);
 
+/* The same two updates (and adm_unipc_step_p below) for a model that predicts something other than eps (Stable Diffusion 2.x:
+ * v).  `param` names what the model output is; any other value is refused before the launch.  The guidance combine is applied to
+ * the RAW output, o = out_uncond ? out_uncond + cfg_scale*(out_cond - out_uncond) : out_cond, as SD 2's samplers do; with
+ * ADM_PARAM_EPS each symbol launches exactly what its eps-only twin launches.  Each line below is one fp32 operation, rounded on
+ * its own (no contraction), in this order:
+ *   adm_sd_step_p   V   t1 = sqrt_at*o;  t2 = sqrt_one_minus_at*x;  e = t1 + t2
+ *                   X0  t1 = sqrt_at*o;  t2 = x - t1;  e = t2 / sqrt_one_minus_at        (refused: sqrt_one_minus_at <= 0)
+ *                   e_out holds e (the PLMS history is eps, as in SD 2's plms.py); e', x0 and x_prev are adm_sd_step's from e.
+ *                   pred_x0 when h1 = h2 = h3 = NULL and w[0] == 1 (DDIM) is the direct form instead:
+ *                   V   s1 = sqrt_at*x;  s2 = sqrt_one_minus_at*o;  x0 = s1 - s2           (predict_start_from_z_and_v)
+ *                   X0  x0 = o
+ *   adm_dpm_step_p  V   t1 = alpha_s*x;  t2 = sigma_s*o;  m = t1 - t2                      (dpm_solver.py:297-306 noise_pred_fn
+ *                   X0  m = o                                                               folded into data_prediction_fn)
+ *                   x_next from m as adm_dpm_step's.
+ * Refusals are those of the eps-only symbols.  THE STREAM IS THE SECOND-TO-LAST ARGUMENT and `param` the last, as for
+ * adm_poly3_sums: their per-element float64 checks live in tests/test_hip_sd_param.py.                                       */
+#define ADM_PARAM_EPS 0
+#define ADM_PARAM_X0 1
+#define ADM_PARAM_V 2
+int adm_sd_step_p(const float* x, const float* out_uncond, const float* out_cond, const float* h1, const float* h2,
+                  const float* h3, const float* noise, float* x_prev, float* pred_x0, float* e_out, int64_t numel,
+                  const adm_sd_step_coefs* coefs_host, void* stream, int param);
+int adm_dpm_step_p(const float* x, const float* out_uncond, const float* out_cond, const float* m_prev, float* x_next,
+                   float* m_out, int64_t numel, float cfg_scale, float sigma_s, float alpha_s, float a, float b0, float b1,
+                   void* stream, int param);
+
 /* ---------------------------------------------------------------- classifier guidance, backward-data (K10, A9)
  * The reference gets grad_x log p(y|x,t) from torch.autograd over EncoderUNetModel
  * (search_imagenet64_classifier_guidance.py:319-326, unet.py:685-896).  Here the backward network
@@ -488,11 +514,16 @@ int adm_vae_image_out(const float* x, float* unit, uint8_t* u8, int n, int h, in
  *                         rows >= t of qkv are never read and rows >= t of out never written; a prompt's result does not depend
  *                         on n.
  *   adm_quick_gelu        16-bit [rows][inner] -> u * sigmoid(1.702 u) in fp32, same type (inner % 8 == 0)
+ *   adm_gelu              16-bit [rows][inner] -> 0.5 u (1 + erf(u / sqrt 2)) in fp32, rounded once to the same type (inner % 8 == 0):
+ *                         the exact GELU of the OpenCLIP text tower (Stable Diffusion 2.x); checks as adm_quick_gelu's.  THE STREAM
+ *                         IS ITS SECOND-TO-LAST ARGUMENT and `flags` (0) the last, as for adm_poly3_sums: its per-element float64
+ *                         check lives in tests/test_hip_sd_param.py
  *   adm_layernorm_f32out  LayerNorm (fp32 two-pass statistics) of rows < t of x 16-bit [n][pitch][c] -> fp32 [n][t][c]        */
 int adm_clip_embed(const int64_t* ids, const float* tok, const float* pos, adm_bf16* out, int n, int t, int pitch, int c, int vocab,
                    int positions, void* stream);
 int adm_attention_causal(const adm_bf16* qkv, adm_bf16* out, int n, int t, int pitch, int heads, int d, void* stream);
 int adm_quick_gelu(const adm_bf16* u, adm_bf16* out, int64_t rows, int inner, void* stream);
+int adm_gelu(const adm_bf16* u, adm_bf16* out, int64_t rows, int inner, void* stream, int flags);
 int adm_layernorm_f32out(const adm_bf16* x, const float* gamma, const float* beta, float* out, int n, int t, int pitch, int c,
                          float eps, void* stream);
 
@@ -631,6 +662,9 @@ typedef struct adm_unipc_args {
 } adm_unipc_args;
 int adm_pix_unipc_step(const adm_pix_unipc_args* args, void* stream, int flags);
 int adm_unipc_step(const adm_unipc_args* args, void* stream, int flags);
+/* adm_unipc_step for a model output named by `param` (ADM_PARAM_*, above): m as adm_dpm_step_p's with x = x_eval (V: t1 =
+ * alpha_s*x_eval; t2 = sigma_s*o; m = t1 - t2.  X0: m = o), everything after m unchanged; `param` stands where `flags` does. */
+int adm_unipc_step_p(const adm_unipc_args* args, void* stream, int param);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ ddim_steps)`` of the DDIM table (``DDIMSampler.stochastic_encode``), denoised fr
 The reference's flags keep their names and defaults: ``--init-img --strength --ddim_steps --ddim_eta --scale --n_samples --n_iter
 --seed --ckpt --config --outdir --prompt``; ``--plms`` is refused as the reference refuses it.  Loading and prompts are those of
 autodiffusion_amd/sd_script_util.py: ``--prompt`` needs the LOCAL ``--tokenizer_dir``; ``--prompt_ids FILE.npy`` holds int64 [num, T] token ids
-instead (one row for every sample of a batch, or ``--n_samples`` rows); ``--torso {bf16,fp16}``; ``--synthetic {tiny,v1}`` builds the
+instead (one row for every sample of a batch, or ``--n_samples`` rows); ``--torso {bf16,fp16}``; ``--synthetic {tiny,v1,tiny2,v2}`` (tiny2 / v2: the v-predicting SD 2.x family) builds the
 networks with ``randomize_()`` instead of reading ``--ckpt``.  ``--use_timestep "[t0, t1, ...]"`` (read with ``ast.literal_eval``)
 runs on a searched schedule of ``--ddim_steps`` timesteps, sorted as ``DDIMSampler.sample`` sorts it, instead of the uniform one.
 

@@ -30,7 +30,7 @@ shards whole candidates over ranks (candidate i on rank i % world, one all_gathe
 per candidate; the fitness stays the FID): PATH is ONE plain state dict holding both CLIP towers, in transformers' ``CLIPModel``
 layout or the OpenAI layout, read with ``dist_util.load_state_dict`` (ViT-L/14; under ``--synthetic tiny`` the tiny towers).
 ``--evaluate "[t0, t1, ...]"`` scores that one candidate over ``--num_sample`` images, prints the FID and exits (the reference's
-txt2img_fid.py use of a searched schedule).  ``--synthetic {tiny,v1}`` builds the networks with ``randomize_()`` instead of
+txt2img_fid.py use of a searched schedule).  ``--synthetic {tiny,v1,tiny2,v2}`` (tiny2 / v2: the v-predicting SD 2.x family) builds the networks with ``randomize_()`` instead of
 reading ``--ckpt``: tests and throughput runs.
 
 Loading: ``--ckpt`` is read with ``torch.load(map_location="cpu")`` and its ``"state_dict"`` (or the dict itself) goes through
@@ -128,7 +128,8 @@ def create_argparser():
     p.add_argument("--clip_ckpt", type=str, default="",
                    help="a CLIP state dict (both towers, CLIPModel or OpenAI layout): also log every candidate's CLIP score")
     p.add_argument("--evaluate", type=str, default="", help="'[t0, t1, ...]': score this one candidate, print its FID and exit")
-    p.add_argument("--synthetic", choices=["tiny", "v1"], default="", help="build the networks with randomize_() instead of reading --ckpt")
+    p.add_argument("--synthetic", choices=["tiny", "v1", "tiny2", "v2"], default="",
+                   help="build the networks with randomize_() instead of reading --ckpt (tiny2 / v2: the SD 2.x family, v-prediction)")
     add_unipc_flags(p)
     return p
 
