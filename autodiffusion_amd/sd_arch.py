@@ -9,7 +9,7 @@ Interpreted by the HIP engine (``sd_unet.py``) and by the CPU oracle (``oracle/s
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, Sequence, Tuple, Union
 
 
@@ -29,6 +29,7 @@ class SDResBlockSpec:
     cin: int
     cout: int
     emb_dim: int
+    layer_id: int = -1   # position among the ResBlocks and transformers in construction order: what a skip list names
 
     @property
     def has_skip_conv(self) -> bool:
@@ -61,6 +62,7 @@ class SDTransformerSpec:
     context_dim: int
     depth: int = 1
     linear: bool = False
+    layer_id: int = -1   # as SDResBlockSpec.layer_id
 
     @property
     def inner(self) -> int:
@@ -124,6 +126,7 @@ class SDUNetPlan:
     input_blocks: List[List[SDBlock]] = field(default_factory=list)
     middle_block: List[SDBlock] = field(default_factory=list)
     output_blocks: List[List[SDBlock]] = field(default_factory=list)
+    layer_num: int = 0   # ResBlocks + transformers: the ids a per-step layer-skip list may hold are range(layer_num)
 
     def all_blocks(self):
         for seq in self.input_blocks:
@@ -197,6 +200,13 @@ def sd_unet_plan(in_channels: int, model_channels: int, out_channels: int, num_r
                 ds //= 2
             plan.output_blocks.append(seq)
     assert ch == model_channels
+    # layer ids as guided_diffusion/dynamic_unet.py:507-655 counts them: ResBlocks and attention-type layers in construction order
+    # (input blocks, middle block, output blocks); the stem and the plain Downsample / Upsample convs carry none
+    for seq in plan.input_blocks + [plan.middle_block] + plan.output_blocks:
+        for j, b in enumerate(seq):
+            if isinstance(b, (SDResBlockSpec, SDTransformerSpec)):
+                seq[j] = replace(b, layer_id=plan.layer_num)
+                plan.layer_num += 1
     return plan
 
 

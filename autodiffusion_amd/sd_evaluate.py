@@ -18,6 +18,11 @@ is fed ``prompts=`` (``sd_clip.FrozenCLIPEmbedder`` as the model's cond stage); 
 Different by design: the empty prompt of classifier-free guidance is encoded once per evaluator, not once per batch (the encoder
 is deterministic, so the value is the same), and the start noise always comes from a CPU generator seeded from (seed, candidate,
 batch index) and is passed as ``x_T`` -- a candidate's score does not depend on what was evaluated before it.
+
+A candidate is a timestep list or, with per-step layer skipping, ``{'timesteps': [...], 'skip_layers': [[ids], ...]}``
+as ``evaluate.py`` / ``search.py`` carry it on the ADM path: ``skip_layers[i]`` names the UNet layers (``sd_arch`` ids) that every
+evaluation at ``timesteps[i]`` bypasses.  Its start noise is seeded from its timesteps alone, so candidates that differ only in
+their skip lists share their noise and a dict of empty lists scores bitwise what the plain list scores.
 """
 from __future__ import annotations
 
@@ -173,9 +178,53 @@ class SDCandidateEvaluator:
                 prompts = list(prompts)
             yield self.model.get_learned_conditioning(prompts), uc, prompts
 
+    # ------------------------------------------------------------------ layer-skip candidates
+    @property
+    def layer_num(self) -> int:
+        """Layers of the UNet a skip list may name (0: the model's UNet does not take skip lists)."""
+        return int(getattr(getattr(self.model, "model", None), "layer_num", 0) or 0)
+
+    def split_candidate(self, cand):
+        """-> (timesteps, skip_layers | None).  A dict candidate is checked here, before anything is launched: as many lists as
+        timesteps, every id an int in range(layer_num), no id twice in one list."""
+        if not isinstance(cand, dict):
+            return cand, None
+        if set(cand) != {"timesteps", "skip_layers"}:
+            raise ValueError(f"SDCandidateEvaluator: a dict candidate holds 'timesteps' and 'skip_layers', got {sorted(cand)}")
+        ts, sk = list(cand["timesteps"]), [list(s) for s in cand["skip_layers"]]
+        if len(ts) != len(sk):
+            raise ValueError(f"SDCandidateEvaluator: {len(sk)} skip lists for {len(ts)} timesteps")
+        L = self.layer_num
+        if L <= 0:
+            raise ValueError("SDCandidateEvaluator: the model's UNet has no layer_num: it does not take layer-skip lists")
+        for i, lst in enumerate(sk):
+            for v in lst:
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < L:
+                    raise ValueError(f"SDCandidateEvaluator: skip_layers[{i}] holds {v!r}: layer ids are ints in range({L})")
+            if len(set(int(v) for v in lst)) != len(lst):
+                raise ValueError(f"SDCandidateEvaluator: skip_layers[{i}] = {lst} names a layer twice")
+        return ts, [[int(v) for v in lst] for lst in sk]
+
+    def candidate_cost(self, cand) -> int:
+        """UNet layer evaluations per image (search.py's candidate_cost): every step costs layer_num minus its skipped layers."""
+        if isinstance(cand, dict):
+            return sum(self.layer_num - len(sk) for sk in cand["skip_layers"])
+        return len(cand) * max(1, self.layer_num)
+
+    def _announce(self, skips):
+        """Tell the UNet how many captured launch sequences this candidate's skipped evaluations need, before sampling: one per
+        distinct non-empty set and, under split guidance, per stream."""
+        unet = getattr(self.model, "model", None)
+        if hasattr(unet, "plan_graphs"):
+            sets = {tuple(sorted(s)) for s in (skips or []) if len(s)}
+            unet.plan_graphs(len(sets), streams=2 if getattr(self.sampler, "split_guidance", False) else 1)
+
     # ------------------------------------------------------------------ search_ea.py:504-566
     def get_cand_fid(self, cand=None, opt=None, device=None):
         t1 = time.time()
+        cand, skips = self.split_candidate(cand)
+        self._announce(skips)
+        extra = {} if skips is None else {"skip_layers": skips}
         seed0 = candidate_seed(self.seed, cand)
         fixed = self.start_code(opt, batch_seed(seed0, 0)) if opt.fixed_code else None
         shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
@@ -200,7 +249,7 @@ class SDCandidateEvaluator:
                 samples, _ = self.sampler.sample(S=opt.time_step, conditioning=c, batch_size=opt.n_samples, shape=shape,
                                                  verbose=False, unconditional_guidance_scale=opt.scale,
                                                  unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T,
-                                                 sampled_timestep=sampled_timestep)
+                                                 sampled_timestep=sampled_timestep, **extra)
                 x = self.model.decode_first_stage(samples)
                 # clamp((x + 1) / 2, 0, 1) straight into the extractor's staging batch of 320 images
                 if stage is None:

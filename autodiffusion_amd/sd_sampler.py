@@ -211,10 +211,15 @@ class LatentDiffusion:
             out["cond_stage_model"] = len(parts["cond_stage_model"])
         return out
 
-    def apply_model(self, x_noisy, t, cond, context_key=None):
+    def apply_model(self, x_noisy, t, cond, context_key=None, skip_layer=()):
+        """skip_layer: the layer ids this evaluation bypasses (sd_unet.UNetModel.forward); forwarded only when there are any, so
+        that a UNet without the keyword keeps working."""
+        kw = {}
         if context_key is not None and getattr(self.model, "accepts_context_key", False):
-            return self.model(x_noisy, t, context=cond, context_key=context_key)
-        return self.model(x_noisy, t, context=cond)
+            kw["context_key"] = context_key
+        if skip_layer is not None and len(skip_layer):
+            kw["skip_layer"] = skip_layer
+        return self.model(x_noisy, t, context=cond, **kw)
 
     accepts_context_key = True
 
@@ -355,15 +360,18 @@ class _LatentSampler:
         self._c_in = torch.cat([uc, c]) if (self._guided and not self._split) else c
         self._key = ("sample", next(_CALL_IDS)) if getattr(self.model, "accepts_context_key", False) else None
 
-    def _eps(self, x, t, uncond_only=False):
+    def _eps(self, x, t, uncond_only=False, skip=None):
+        """skip: the layer-skip list of the timestep this evaluation is at -- every UNet call made here carries it (both halves
+        of the guidance, split or batched, and the unguided call of a prompt_mask step); handed on only when it holds ids."""
+        kw = {"skip_layer": skip} if skip is not None and len(skip) else {}
         if uncond_only:
             # plms.py:164-171: one evaluation of N on the unconditional conditioning, on the CURRENT stream.  sd_unet.py keeps one
             # set of conditioning projections and one graph per shape PER LAUNCHING STREAM, so this call never touches what the
             # side stream holds under the same key (split guidance); it replaces the current stream's projections (the guided
             # step that follows recomputes them) and replays the current stream's own graph, in stream order.
             if self._key is not None:
-                return self.model.apply_model(x, t, self._uc, context_key=(self._key, "u"))
-            return self.model.apply_model(x, t, self._uc)
+                return self.model.apply_model(x, t, self._uc, context_key=(self._key, "u"), **kw)
+            return self.model.apply_model(x, t, self._uc, **kw)
         if self._guided and self._split:
             cur = torch.cuda.current_stream(x.device)
             side = _SIDE_STREAMS.get(x.device)
@@ -371,16 +379,32 @@ class _LatentSampler:
                 side = _SIDE_STREAMS[x.device] = torch.cuda.Stream(device=x.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                eu = self.model.apply_model(x, t, self._uc, context_key=(self._key, "u"))
-            ec = self.model.apply_model(x, t, self._c, context_key=(self._key, "c"))
+                eu = self.model.apply_model(x, t, self._uc, context_key=(self._key, "u"), **kw)
+            ec = self.model.apply_model(x, t, self._c, context_key=(self._key, "c"), **kw)
             cur.wait_stream(side)
             eu.record_stream(cur)
             return torch.cat([eu, ec])
         if self._guided:
             x, t = torch.cat([x] * 2), torch.cat([t] * 2)
         if self._key is not None:
-            return self.model.apply_model(x, t, self._c_in, context_key=self._key)
-        return self.model.apply_model(x, t, self._c_in)
+            return self.model.apply_model(x, t, self._c_in, context_key=self._key, **kw)
+        return self.model.apply_model(x, t, self._c_in, **kw)
+
+    # ---- per-step layer-skip lists
+    _skips = None   # during a sample() call of DDIM / PLMS: one list per entry of ddim_timesteps
+
+    @staticmethod
+    def _check_skip_layers(skip_layers, count, who, what):
+        """-> None, or `count` lists of ints.  A wrong length raises here, before anything is launched; the UNet checks the ids."""
+        if skip_layers is None:
+            return None
+        lists = [[int(v) for v in sk] for sk in skip_layers]
+        if len(lists) != count:
+            raise ValueError(f"{who}: skip_layers holds {len(lists)} lists for {count} {what}")
+        return lists
+
+    def _skip_at(self, index):
+        return None if self._skips is None else self._skips[index]
 
     def _start(self, shape, x_T):
         device = self.model.betas.device
@@ -393,14 +417,22 @@ class _LatentSampler:
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, sampled_timestep=None, prompt_mask=None, **kwargs):
+               unconditional_conditioning=None, sampled_timestep=None, prompt_mask=None, skip_layers=None, **kwargs):
+        """skip_layers: one list of layer ids per timestep, ``skip_layers[i]`` belonging to ``sampled_timestep[i]`` as passed (it
+        travels with its timestep through the sampler's ordering); every UNet evaluation at a timestep bypasses that timestep's
+        layers.  None: nothing changes."""
         self._unsupported(quantize_x0=quantize_x0, noise_dropout=noise_dropout > 0., score_corrector=score_corrector is not None)
         if conditioning is not None and not isinstance(conditioning, dict) and conditioning.shape[0] != batch_size:
             print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
         C_, H, W = shape
         self._check_mask(mask, x0, (batch_size, C_, H, W))
-        sampled_timestep = self._order(sampled_timestep)
+        if skip_layers is not None and sampled_timestep is not None:
+            skip_layers = self._check_skip_layers(skip_layers, len(sampled_timestep), type(self).__name__, "timesteps")
+            sampled_timestep, skip_layers = self._order(sampled_timestep, skip_layers)
+        else:
+            sampled_timestep = self._order(sampled_timestep)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose, sampled_timestep=sampled_timestep)
+        self._skips = self._check_skip_layers(skip_layers, len(self.ddim_timesteps), type(self).__name__, "timesteps")
         self._prompt_mask = self._check_prompt_mask(prompt_mask, len(self.ddim_timesteps), unconditional_conditioning)
         self._mask = self._begin_mask(mask, x0, (batch_size, C_, H, W))
         try:
@@ -409,7 +441,7 @@ class _LatentSampler:
                               unconditional_guidance_scale=unconditional_guidance_scale,
                               unconditional_conditioning=unconditional_conditioning)
         finally:
-            self._mask = self._prompt_mask = None
+            self._mask = self._prompt_mask = self._skips = None
 
     # ---- masked sampling (ddim.py:157-160, plms.py:159-162): mask 1 keeps x0, 0 is generated
     _mask = None          # (keep, drop, x0) during a masked sample() call
@@ -457,8 +489,12 @@ class _LatentSampler:
 
 
 class DDIMSampler(_LatentSampler):
-    def _order(self, sampled_timestep):
-        return None if sampled_timestep is None else sorted(int(t) for t in sampled_timestep)  # ddim.py:93-94
+    def _order(self, sampled_timestep, skip_layers=None):
+        """ddim.py:93-94 sorts the list; with skip_layers -> (timesteps, lists), each list moving with its timestep."""
+        if skip_layers is None:
+            return None if sampled_timestep is None else sorted(int(t) for t in sampled_timestep)
+        order = sorted(range(len(sampled_timestep)), key=lambda i: int(sampled_timestep[i]))   # stable, as sorted() on the values
+        return [int(sampled_timestep[i]) for i in order], [skip_layers[i] for i in order]
 
     def _loop(self, cond, shape, x_T, callback, img_callback, log_every_t, temperature, unconditional_guidance_scale,
               unconditional_conditioning):
@@ -474,7 +510,7 @@ class DDIMSampler(_LatentSampler):
             # ddim.py:157-160.  The reference does not blend again after the last update: the kept region of the RESULT is the
             # model's last update of it, not x0; and x_inter below stays the post-step latent.
             img = self._blend(img, ts)
-            eps = self._eps(img, ts)
+            eps = self._eps(img, ts, skip=self._skip_at(index))
             sigma = self.ddim_sigmas[index]
             noise = torch.randn(shape, device=device) * temperature if sigma != 0 else None  # ddim.py:198 noise_like
             img, pred_x0, _ = sd_step(img, eps, b, unconditional_guidance_scale, (1.0,), (), self.ddim_alphas[index],
@@ -502,11 +538,14 @@ class DDIMSampler(_LatentSampler):
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False):
+               use_original_steps=False, skip_layers=None):
         """ddim.py:235-254: the DDIM updates of ``ddim_timesteps[:t_start]``, downwards, from x_latent.  With the reference's
         conventions a latent from ``stochastic_encode(x0, t)`` carries the noise level of table entry t and is decoded with
-        ``t_start = t``, whose first update is entry t - 1's: the off-by-one is the reference's and is kept."""
+        ``t_start = t``, whose first update is entry t - 1's: the off-by-one is the reference's and is kept.
+        skip_layers: one list of layer ids per entry of ``ddim_timesteps`` (the table make_schedule built), in the table's order;
+        the update of entry i bypasses list i's layers."""
         self._unsupported(use_original_steps=use_original_steps)
+        skips = self._check_skip_layers(skip_layers, len(self.ddim_timesteps), "DDIMSampler.decode", "timesteps of the schedule")
         device, img = self._start(tuple(x_latent.shape), x_latent)
         self._begin(cond, unconditional_conditioning, unconditional_guidance_scale)
         b = img.shape[0]
@@ -515,7 +554,7 @@ class DDIMSampler(_LatentSampler):
         for i, step in enumerate(np.flip(timesteps)):
             index = total - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
-            eps = self._eps(img, ts)
+            eps = self._eps(img, ts, skip=None if skips is None else skips[index])
             sigma = self.ddim_sigmas[index]
             noise = torch.randn(img.shape, device=device) if sigma != 0 else None
             img, _, _ = sd_step(img, eps, b, unconditional_guidance_scale, (1.0,), (), self.ddim_alphas[index],
@@ -529,8 +568,9 @@ class PLMSSampler(_LatentSampler):
             raise ValueError('ddim_eta must be 0 for PLMS')
         super().make_schedule(ddim_num_steps, ddim_discretize, ddim_eta, verbose, sampled_timestep)
 
-    def _order(self, sampled_timestep):
-        return sampled_timestep  # plms.py takes the list as given; search_ea.py sorts its candidates (:480)
+    def _order(self, sampled_timestep, skip_layers=None):
+        # plms.py takes the list as given; search_ea.py sorts its candidates (:480)
+        return sampled_timestep if skip_layers is None else (sampled_timestep, skip_layers)
 
     def _check_prompt_mask(self, prompt_mask, steps, uc):
         """plms.py:85,131,164: one entry per loop position i (entry 0 is the first, noisiest step)."""
@@ -576,10 +616,10 @@ class PLMSSampler(_LatentSampler):
             # unconditional conditioning (scale 1), and that eps is what the multistep history keeps
             un = self._prompt_mask is not None and self._prompt_mask[i] == 0
             scale = 1.0 if un else unconditional_guidance_scale
-            eps = self._eps(img, ts, un)
+            eps = self._eps(img, ts, un, skip=self._skip_at(index))
             if len(old_eps) == 0:    # pseudo improved Euler (2nd order): a second model call at the predicted point
                 x_mid, _, e_t = sd_step(img, eps, b, scale, (1.0,), (), a_t, a_prev, sigma, param=param)
-                eps2 = self._eps(x_mid, ts_next, un)
+                eps2 = self._eps(x_mid, ts_next, un, skip=self._skip_at(max(index - 1, 0)))   # t_next's own list
                 img, pred_x0, _ = self._plms_second(img, x_mid, eps2, b, scale, e_t, a_t, a_prev, sigma, int(ts_next[0]), param)
             else:                    # Adams-Bashforth of order 2 / 3 / 4 over the kept eps history (newest first)
                 w = {1: (3 / 2, -1 / 2), 2: (23 / 12, -16 / 12, 5 / 12), 3: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}[len(old_eps)]
@@ -662,14 +702,16 @@ class DPMSolverSampler(_LatentSampler):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, sampled_timestep=None, **kwargs):
+               unconditional_conditioning=None, sampled_timestep=None, skip_layers=None, **kwargs):
+        """skip_layers: one list of layer ids per model evaluation, in the order evaluated: K lists for K + 1 times."""
         if conditioning is not None and not isinstance(conditioning, dict) and conditioning.shape[0] != batch_size:
             print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
         C_, H, W = shape
-        device, x = self._start((batch_size, C_, H, W), x_T)
-        ns = NoiseScheduleVP('discrete', alphas_cumprod=self.alphas_cumprod)
         steps, order = int(S), 2
         assert steps >= order
+        skips = self._check_skip_layers(skip_layers, steps, "DPMSolverSampler", "model evaluations")
+        device, x = self._start((batch_size, C_, H, W), x_T)
+        ns = NoiseScheduleVP('discrete', alphas_cumprod=self.alphas_cumprod)
         if sampled_timestep is None:
             ts = [float(v) for v in np.linspace(ns.T, 1.0 / ns.total_N, steps + 1, dtype=np.float32)]
         else:
@@ -684,9 +726,9 @@ class DPMSolverSampler(_LatentSampler):
 
         self._begin(conditioning, uc, scale)
 
-        def eps_at(x_, t):  # model_wrapper: discrete-time input (t - 1/N) * 1000, guidance batch = [uncond | cond]
+        def eps_at(x_, t, skip):  # model_wrapper: discrete-time input (t - 1/N) * 1000, guidance batch = [uncond | cond]
             t_in = torch.full((batch_size,), (t - 1.0 / ns.total_N) * 1000.0, device=device, dtype=torch.float32)
-            return self._eps(x_, t_in)
+            return self._eps(x_, t_in, skip=skip)
 
         m_prev, lam_prev = None, None
         for step in range(1, steps + 1):
@@ -704,7 +746,7 @@ class DPMSolverSampler(_LatentSampler):
                 b0, b1 = -phi * (1.0 + 0.5 / r0), 0.5 * phi / r0
             else:
                 b0, b1 = -phi, 0.0
-            x, m = dpm_step(x, eps_at(x, s), batch_size, scale, m_prev if step_order == 2 else None,
+            x, m = dpm_step(x, eps_at(x, s, None if skips is None else skips[step - 1]), batch_size, scale, m_prev if step_order == 2 else None,
                             ns.marginal_std(s), ns.marginal_alpha(s), a, b0, b1, param=self._param)
             m_prev, lam_prev = m, lam_s
         return x, None
@@ -767,8 +809,10 @@ class UniPCSampler(_LatentSampler):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, sampled_timestep=None, order=None, variant=None, corrector=None, record=None,
-               **kwargs):
+               skip_layers=None, **kwargs):
+        """skip_layers: one list of layer ids per model evaluation, in the order evaluated: K lists for K + 1 times."""
         from .unipc import plan_evaluations
+        skips = self._check_skip_layers(skip_layers, int(S), "UniPCSampler", "model evaluations")
         order = self.order if order is None else int(order)
         variant = self.variant if variant is None else variant
         corrector = self.corrector if corrector is None else bool(corrector)
@@ -796,7 +840,7 @@ class UniPCSampler(_LatentSampler):
         hist, x_base = [], None      # model values, newest first; the accepted state at the previous time
         for j, e in enumerate(plan):
             t_in = torch.full((batch_size,), (ts[j] - 1.0 / ns.total_N) * 1000.0, device=device, dtype=torch.float32)
-            eps = self._eps(x, t_in)
+            eps = self._eps(x, t_in, skip=None if skips is None else skips[j])
             depth = max(e["corr"][2] if e["corr"] else 0, e["pred"][2] - 1)
             corr = None if e["corr"] is None else (e["corr"][0], *e["corr"][1])
             pred = (e["pred"][0], *e["pred"][1])

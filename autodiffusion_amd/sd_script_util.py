@@ -53,6 +53,19 @@ SD_SAMPLING_FLAGS = {
                         help="build the networks with randomize_() instead of reading --ckpt (tiny2 / v2: the SD 2.x family, v-prediction)"),
     "--use_timestep": dict(type=str, default="", help="'[t0, t1, ...]': a searched schedule of --ddim_steps timesteps"),
     "--side_multiple": dict(type=int, default=64, help="an image FILE is resized down to a multiple of this many pixels"),
+    # absent from the namespace unless given (as the flags below): the argument line of every other run stays what it was
+    "--skip_layers": dict(type=str, default=argparse.SUPPRESS,
+                          help="'[[ids], [ids], ...]': per-step layer-skip lists, list i belonging to entry i of --use_timestep as written "
+                               "(without --use_timestep: to step i of the uniform schedule, ascending)"),
+}
+# scripts/sd_search_ea.py's joint timestep / layer-skip search: scripts/search_ea.py's names and meaning
+SD_SKIP_SEARCH_FLAGS = {
+    "--use_dynamic_unet": dict(type=str2bool, default=argparse.SUPPRESS,
+                               help="search per-step layer-skip lists together with the timesteps (DDIM / PLMS)"),
+    "--max_prun": dict(type=float, default=argparse.SUPPRESS, help="largest fraction of the UNet's layers one step may skip"),
+    "--min_prun": dict(type=float, default=argparse.SUPPRESS, help="smallest fraction, from epoch 6 on"),
+    "--index_step": dict(type=str, default=argparse.SUPPRESS,
+                         help="budget of evaluated layers per candidate (default: time_step * layer_num); a number, no arithmetic"),
 }
 
 
@@ -62,6 +75,59 @@ def add_sd_sampling_flags(parser, first, last):
     names = list(SD_SAMPLING_FLAGS)
     for name in names[names.index(first):names.index(last) + 1]:
         parser.add_argument(name, **SD_SAMPLING_FLAGS[name])
+
+
+def add_skip_search_flags(parser):
+    for name, kw in SD_SKIP_SEARCH_FLAGS.items():
+        parser.add_argument(name, **kw)
+
+
+def skip_search_options(opt, prog):
+    """The joint search's (max_prun, min_prun, index_step | None), or None with --use_dynamic_unet off; its flags without it, and
+    the continuous-time samplers beside it, are refused."""
+    if not getattr(opt, "use_dynamic_unet", False):
+        given = [k for k in ("max_prun", "min_prun", "index_step") if hasattr(opt, k)]
+        if given:
+            raise SystemExit(f"{prog}: --{given[0]} needs --use_dynamic_unet True")
+        return None
+    if getattr(opt, "dpm_solver", False) or getattr(opt, "unipc", False):
+        raise SystemExit(f"{prog}: --use_dynamic_unet searches the integer timestep space (DDIM / PLMS): not with --dpm_solver / --unipc")
+    if not (hasattr(opt, "max_prun") and hasattr(opt, "min_prun")):
+        raise SystemExit(f"{prog}: --use_dynamic_unet True needs --max_prun F --min_prun F")
+    if not 0.0 <= opt.min_prun <= opt.max_prun < 1.0:
+        raise SystemExit(f"{prog}: expected 0 <= --min_prun <= --max_prun < 1, got {opt.min_prun} and {opt.max_prun}")
+    index_step = None
+    if hasattr(opt, "index_step"):
+        from .evaluate import parse_index_step
+        try:
+            index_step = parse_index_step(opt.index_step, "--index_step")
+        except ValueError as e:
+            raise SystemExit(f"{prog}: {e}") from e
+    return opt.max_prun, opt.min_prun, index_step
+
+
+def read_skip_layers(text, use_timestep, steps, prog):
+    """--skip_layers "[[ids], ...]" -> one list of ints per step in ASCENDING timestep order (read_use_timestep's order), or None when
+    the flag is empty.  List i belongs to entry i of --use_timestep as written and moves with it through the sort."""
+    if not text:
+        return None
+    try:
+        v = ast.literal_eval(text)
+    except (ValueError, SyntaxError) as e:
+        raise SystemExit(f"{prog}: --skip_layers: expected a list of lists of layer ids, got {text!r}") from e
+    ok = isinstance(v, (list, tuple)) and all(isinstance(s, (list, tuple)) and all(isinstance(i, int) and not isinstance(i, bool) for i in s)
+                                              for s in v)
+    if not ok:
+        raise SystemExit(f"{prog}: --skip_layers: expected a list of lists of layer ids, got {text!r}")
+    if len(v) != steps:
+        raise SystemExit(f"{prog}: --skip_layers holds {len(v)} lists; --ddim_steps is {steps}")
+    lists = [list(s) for s in v]
+    if use_timestep:
+        ts = [int(t) for t in ast.literal_eval(use_timestep)]
+        if len(ts) != len(lists):
+            raise SystemExit(f"{prog}: --skip_layers holds {len(lists)} lists; --use_timestep {len(ts)} entries")
+        lists = [lists[i] for i in sorted(range(len(ts)), key=lambda i: ts[i])]
+    return lists
 
 
 def read_use_timestep(text, ddim_steps, prog):

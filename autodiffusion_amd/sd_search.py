@@ -25,6 +25,9 @@ Different by design:
     ``flush_pending()`` evaluates candidate i on rank ``i % world`` (all SD candidates of one search cost the same: no cost
     model), runs ONE ``all_gather`` of the float64 FIDs and writes them back in order; ``search()`` flushes where ``search.py``
     does.  With one rank the trajectory is the sequential one.
+
+``DynamicEvolutionSearcher`` below is the joint search over timesteps AND per-step layer-skip lists in the integer
+timestep space: ``search.DynamicEvolutionSearcher``'s own operators, draws, budget and bookkeeping over this module's evaluator.
 """
 from __future__ import annotations
 
@@ -37,7 +40,8 @@ import time
 import numpy as np
 import torch
 
-from . import dist_util, logger
+from . import dist_util, logger, search as adm_search
+from .evaluate import parse_candidate
 from .sd_sampler import make_ddim_timesteps
 
 choice = lambda x: x[np.random.randint(len(x))] if isinstance(x, tuple) else choice(tuple(x))  # noqa: E731
@@ -54,11 +58,14 @@ def dpm_search_params(alphas_cumprod, time_step):
 
 def parse_sd_candidate(text, flag="candidate"):
     """A candidate as the search writes it (``str(cand)``) or as ``--evaluate`` gives it: a flat list of ints (a timestep
-    list) or of floats (DPM-Solver times).  ``ast.literal_eval`` plus a shape check: command-line text is input from outside."""
+    list) or of floats (DPM-Solver times), or the joint search's ``{'timesteps': [ints], 'skip_layers': [[ints], ...]}`` with one
+    list per timestep.  ``ast.literal_eval`` plus a shape check: command-line text is input from outside."""
     try:
         v = ast.literal_eval(text)
     except (ValueError, SyntaxError) as e:
         raise ValueError(f"{flag}: expected a list of numbers, got {text!r}") from e
+    if isinstance(v, dict):
+        return parse_candidate(text, flag)   # evaluate.py's shape check of the dict form
     if not isinstance(v, (list, tuple)) or not v or not all(isinstance(t, (int, float)) and not isinstance(t, bool) for t in v):
         raise ValueError(f"{flag}: expected a non-empty list of ints or floats, got {text!r}")
     return list(v)
@@ -319,3 +326,62 @@ class EvolutionSearcher(object):
             self.get_random(self.population_num)
             self.epoch += 1
         self.flush_pending()
+
+
+class _Steps:
+    """What search.py's operators read from the diffusion they search over."""
+
+    def __init__(self, original_num_steps):
+        self.original_num_steps = int(original_num_steps)
+
+
+class DynamicEvolutionSearcher(adm_search.DynamicEvolutionSearcher):
+    """Joint search over timesteps and per-step layer-skip lists of the latent UNet, DDIM / PLMS (integer timesteps).  The
+    operators, the order of RNG draws, the budget (``max_index_number = time_step * layer_num``, or ``index_step``), the
+    progressive ``skip_layer_range``, the bookkeeping and the log lines are ``search.DynamicEvolutionSearcher``'s, inherited; what
+    is set here is the space (``original_num_steps = sampler.ddpm_num_timesteps``, ``model_layers = unet.layer_num``) and the
+    evaluation, which goes through ``SDCandidateEvaluator``.  With ``population_parallel`` the queued dict candidates are assigned
+    by search.py's cost-aware rule (``flush_pending``: longest first to the least-loaded rank)."""
+
+    def __init__(self, opt, model, time_step, ref_mu, ref_sigma, sampler, dataloader_info, batch_size, dpm_params=None, *,
+                 evaluator=None, population_parallel=False, inception=None, features=None, allow_random_inception=False,
+                 clip_scorer=None, fitness="fid", ref_feats=None, ref_clip_feats=None, index_step=None, layer_num=None):
+        if getattr(opt, "dpm_solver", False) or getattr(opt, "unipc", False) or dpm_params is not None:
+            raise ValueError("the joint timestep / layer-skip search is built for the integer timestep space (DDIM / PLMS): "
+                             "not together with opt.dpm_solver / opt.unipc")
+        if evaluator is None:
+            from .sd_evaluate import SDCandidateEvaluator
+            evaluator = SDCandidateEvaluator(
+                model, sampler, ref_mu=np.load(ref_mu) if isinstance(ref_mu, (str, os.PathLike)) else ref_mu,
+                ref_sigma=np.load(ref_sigma) if isinstance(ref_sigma, (str, os.PathLike)) else ref_sigma, num_samples=opt.num_sample,
+                prompts=_Texts(dataloader_info['validation_loader']), features=features, inception=inception,
+                allow_random_inception=allow_random_inception, seed=int(getattr(opt, "seed", 0)), clip_scorer=clip_scorer,
+                fitness=fitness, ref_feats=ref_feats, ref_clip_feats=ref_clip_feats, image_sharded=not population_parallel)
+        if layer_num is None:
+            layer_num = getattr(getattr(model, "model", None), "layer_num", None) or getattr(evaluator, "layer_num", None)
+        if not layer_num:
+            raise ValueError("the joint search needs the UNet's layer_num (model.model.layer_num, the evaluator's, or layer_num=)")
+        args = copy.copy(opt)               # search.py's names for what it reads from the argument namespace
+        args.layer_num = int(layer_num)
+        args.time_step = time_step
+        args.use_ddim = True
+        args.fitness = "fid"                # the evaluator owns the fitness; search.py only sorts by the value
+        # model=None: search.py builds no ADM evaluator; base_diffusion: only its original_num_steps is read
+        super().__init__(args, None, _Steps(sampler.ddpm_num_timesteps), time_step, index_step=index_step,
+                         population_parallel=population_parallel)
+        self.opt, self.model, self.sampler = opt, model, sampler
+        self.dataloader_info, self.batch_size = dataloader_info, batch_size
+        self.evaluator = self._ev = evaluator      # _ev: flush_pending reads its .device for the all_gather
+        self.fid_note = getattr(evaluator, "fid_note", "")
+
+    def candidate_cost(self, cand) -> int:
+        return self.evaluator.candidate_cost(cand) if hasattr(self.evaluator, "candidate_cost") else super().candidate_cost(cand)
+
+    def get_cand_fid(self, cand=None, args=None, opt=None, device='cuda'):
+        """The candidate's steps go to the evaluator in ascending timestep order, each list with its timestep: the order in which
+        both samplers are driven on this path (search_ea.py:480 sorts before PLMS sees a list; DDIM sorts itself)."""
+        if isinstance(cand, dict):
+            order = sorted(range(len(cand['timesteps'])), key=lambda i: cand['timesteps'][i])
+            cand = {'timesteps': [_plain(cand['timesteps'][i]) for i in order],
+                    'skip_layers': [list(cand['skip_layers'][i]) for i in order]}
+        return self.evaluator.get_cand_fid(cand, opt if opt is not None else self.opt)

@@ -20,11 +20,16 @@ Engine: activations are bf16 NHWC, so a token of the SpatialTransformer IS a pix
   The reference's 40-channel heads are zero-padded to 48 by the packed projection weights (the MFMA attention kernels
   take head widths 32, 48, 64, 80, 96, 128, 160, 192, 256: 80 and 160 run as they are); the logit scale stays
   dim_head^-0.5.
+
+Layer skipping (``forward(..., skip_layer=[ids])``): the ids of ``sd_arch`` (ResBlocks and transformers in
+construction order) under the rule of guided_diffusion/dynamic_unet.py -- a skipped ResBlock is ``skip_connection(x)`` alone
+(:245-250: x itself, or the unfused 1x1 over the block input), a skipped transformer is ``x`` (:316-318).  No launch is added.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict
+from collections import OrderedDict
+from typing import Dict, Sequence
 
 import torch
 
@@ -155,13 +160,21 @@ class UNetModel(HipModule):
         pr.zero_bias = torch.zeros(max(zmax, 32), dtype=torch.float32, device=dev)  # the bias-free Linear layers
         pr.head = blocks.head_weights(P, f32, pack, "out.0", "out.2")
         pr.graphs = {}  # captured evaluations; they die with the packed weights they point into
+        pr.skip_graphs = OrderedDict()  # ... those of a non-empty layer-skip set: a bounded LRU (plan_graphs)
         pr.kv_cache = None  # (context key, k|v projections of the cross-attention layers)
         self._packed = pr
         return pr
 
     # ------------------------------------------------------------------ blocks
-    def _resblock(self, pr, s: SDResBlockSpec, x0, x1, emb):
+    def _resblock(self, pr, s: SDResBlockSpec, x0, x1, emb, skipped=False):
         d = pr.blocks[s.prefix]
+        if skipped:   # dynamic_unet.py:245-250: the body bypassed, skip_connection(x) kept
+            if not s.has_skip_conv:
+                assert x1 is None
+                return x0   # with the statistics its producer accumulated (x0._adm_stats), if it did
+            # the unfused 1x1 over (x0 | x1), never the folded 3x3 weights on zeros; its epilogue accumulates the GroupNorm
+            # statistics the next block's gn_affine reads (where the kernel does not offer them, gn_affine runs its own pass)
+            return ops.conv(x0, d["ws"], d["wsb"], s.cout, 1, x1=x1, want_stats=True)
         aff1 = ops.gn_affine(x0, d["g1"], d["b1"], x1)
         h = ops.conv(x0, d["w1"], d["c1b"], s.cout, 9, x1=x1, aff=aff1, silu=True, want_stats=True,
                      ksplit=self._ks(x0, x0.shape[3] + (0 if x1 is None else x1.shape[3])))
@@ -201,16 +214,17 @@ class UNetModel(HipModule):
             h = ops.conv(gl, L["ff2"], L["ff2b"], inner, 1, res=h, ksplit=self._ks1(x, 4 * inner, inner))
         return ops.conv(h, d["w_out"], d["b_out"], c, 1, res=x, want_stats=True, ksplit=self._ks1(x, inner, c))
 
-    def _run_seq(self, pr, seq, h, skip, emb, kvs, n_ctx, x_nchw=None):
+    def _run_seq(self, pr, seq, h, skip, emb, kvs, n_ctx, x_nchw=None, skip_ids=()):
         first = True
         for blk in seq:
             d = pr.blocks[blk.prefix]
             if isinstance(blk, SDStemSpec):
                 h = blocks.stem(d, x_nchw, blk.cout, self.compute_dtype)
             elif isinstance(blk, SDResBlockSpec):
-                h = self._resblock(pr, blk, h, skip if first else None, emb)
+                h = self._resblock(pr, blk, h, skip if first else None, emb, blk.layer_id in skip_ids)
             elif isinstance(blk, SDTransformerSpec):
-                h = self._transformer(pr, blk, h, kvs, n_ctx)
+                if blk.layer_id not in skip_ids:   # dynamic_unet.py:316-318: a skipped attention-type layer returns x
+                    h = self._transformer(pr, blk, h, kvs, n_ctx)
             elif isinstance(blk, SDDownSpec):
                 if STRIDE2_TAPS:   # the 9 taps at the output pixels only (general conv2d kernel, csrc/adm_convg.hip)
                     h = ops.conv2d(h, d["w2d"], d["b"], 3, 3, stride=2, pad=(1, 1), relu=False)
@@ -235,6 +249,7 @@ class UNetModel(HipModule):
         self.upconv_phases = bool(on)
         if self._packed is not None:
             self._packed.graphs = {}
+            self._packed.skip_graphs = OrderedDict()
         return self
 
     def enable_splitk(self, flag: bool = True):
@@ -258,9 +273,65 @@ class UNetModel(HipModule):
         self.use_graph = bool(flag)
         return self
 
+    # ------------------------------------------------------------------ layer-skip sets and their graphs
+    # A layer-skip set is another launch sequence, hence another captured graph per (shape, stream).  Graphs of the empty set
+    # stay in pr.graphs as before; those of non-empty sets live in pr.skip_graphs, an LRU bounded as unet.py's plan_graphs /
+    # _graphed bound the ADM cache: SKIP_GRAPH_CACHE graphs, raised to the announced candidate's needs up to
+    # SKIP_GRAPH_CACHE_MAX, and never more than GRAPH_POOL_FRACTION of the device's memory in private pools.
+    SKIP_GRAPH_CACHE = 12
+    SKIP_GRAPH_CACHE_MAX = 32
+    GRAPH_POOL_FRACTION = float(os.environ.get("ADM_GRAPH_POOL_FRACTION", "0.45"))
+    _graph_eager = False    # the announced candidate's skip sets do not fit: its skipped evaluations launch eagerly
+    _planned_graphs = 1
+    _pool_bytes_seen = 0    # largest private pool a capture of a skipped evaluation has needed so far
+
+    @property
+    def layer_num(self) -> int:
+        return self.plan.layer_num
+
+    def _skip_key(self, skip_layer) -> tuple:
+        """The sorted tuple of distinct ids; an id outside range(layer_num) raises before anything is launched."""
+        ids = [] if skip_layer is None else list(skip_layer)
+        for v in ids:
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < self.plan.layer_num:
+                raise ValueError(f"skip_layer: {v!r} is not a layer id of this UNet (range({self.plan.layer_num}))")
+        return tuple(sorted({int(v) for v in ids}))
+
+    def _graph_budget(self) -> int:
+        dev = self.device
+        return int(self.GRAPH_POOL_FRACTION * torch.cuda.get_device_properties(dev).total_memory) if dev.type == "cuda" else 0
+
+    def plan_graphs(self, distinct_sets: int, streams: int = 1):
+        """Called per candidate (SDCandidateEvaluator) with the number of DISTINCT non-empty layer-skip sets of its steps and the
+        number of streams each is evaluated from (2 under split guidance: a graph belongs to one launching stream).  The LRU
+        grows to hold them all, up to SKIP_GRAPH_CACHE_MAX graphs and GRAPH_POOL_FRACTION of the device's memory in pools (the
+        pool of a capture is known after the first one; forward() re-checks at every capture); beyond either bound the
+        candidate's skipped evaluations launch eagerly, with one log line -- an LRU smaller than the candidate's needs would
+        recapture at every step of every batch."""
+        from . import logger
+        sets = max(0, int(distinct_sets))
+        need = max(1, sets * max(1, int(streams)))
+        self._planned_graphs = need
+        too_many = need > self.SKIP_GRAPH_CACHE_MAX
+        too_big = self._pool_bytes_seen > 0 and need * self._pool_bytes_seen > self._graph_budget()
+        if not (too_many or too_big):
+            self.SKIP_GRAPH_CACHE = max(type(self).SKIP_GRAPH_CACHE, need)
+            self._graph_eager = False
+        else:
+            if not self._graph_eager and self.use_graph:
+                why = (f"{sets} distinct layer-skip sets x {max(1, int(streams))} stream(s) > {self.SKIP_GRAPH_CACHE_MAX} cached graphs"
+                       if too_many else f"{need} graphs x {self._pool_bytes_seen / 1e9:.2f} GB of private pool > "
+                                        f"{self._graph_budget() / 1e9:.0f} GB budget")
+                logger.log(f"hipGraph replay off for this candidate's skipped evaluations: {why} (eager launches instead of "
+                           "recapturing every step)")
+            self._graph_eager = True
+        return self
+
     def _context_kv(self, pr, context, n):
         """The k|v projections of every cross-attention layer: they depend on the conditioning only.  The tokens ride as a
-        bf16 pixel map (8x16 or 16x16, zero rows beyond S) so that the projections are 1x1 convs."""
+        bf16 pixel map (8x16 or 16x16, zero rows beyond S) so that the projections are 1x1 convs.  Transformers that a step's
+        skip list leaves out are projected too: this runs once per sample() call, whose steps may skip different layers, and the
+        graphs take the projections as a fixed list of static inputs."""
         plan: SDUNetPlan = self.plan
         if context is None or context.dim() != 3 or context.shape[2] != plan.context_dim or context.shape[0] != n:
             raise AdmError(f"context must be [N = {n}, S, {plan.context_dim}]")
@@ -300,15 +371,17 @@ class UNetModel(HipModule):
 
     accepts_context_key = True
 
-    def forward(self, x, timesteps=None, context=None, y=None, context_key=None, **kwargs):
-        """x fp32 [N, C, H, W] latents, timesteps [N], context [N, S, context_dim] -> fp32 [N, out, H, W]."""
+    def forward(self, x, timesteps=None, context=None, y=None, context_key=None, skip_layer: Sequence[int] = (), **kwargs):
+        """x fp32 [N, C, H, W] latents, timesteps [N], context [N, S, context_dim] -> fp32 [N, out, H, W].
+        skip_layer: layer ids (sd_arch: range(layer_num)) whose body this evaluation bypasses."""
+        skip = self._skip_key(skip_layer)
         pr = self._packed or self._prepare()
         if not x.is_cuda:
             raise AdmError("latent UNetModel.forward: x must be a device tensor (no CPU fallback)")
         n = x.shape[0]
         kvs, fresh = self._kv_for(pr, context, n, context_key)
-        if not self.use_graph:
-            return self._forward(x, timesteps, kvs, context.shape[1], y)
+        if not self.use_graph or (skip and self._graph_eager):
+            return self._forward(x, timesteps, kvs, context.shape[1], y, skip)
         if not timesteps.is_cuda:
             raise AdmError("latent UNetModel (graph mode): timesteps must be a device tensor")
         # one captured graph (hipGraphExec + static input / output buffers + private allocator pool) per input shape AND
@@ -319,20 +392,39 @@ class UNetModel(HipModule):
         # the launch-sequence switches are part of the key: toggling one after the first replay must not keep the old capture
         key = (tuple(x.shape), x.dtype, tuple(timesteps.shape), timesteps.dtype, tuple(context.shape),
                torch.cuda.current_stream(x.device).cuda_stream, self.small_batch_splitk, self.upconv_phases, self.fuse_geglu)
-        entry = pr.graphs.get(key)
+        if skip:   # ... and so is a non-empty layer-skip set; the empty set keeps the key and the cache it has always had
+            key += (skip,)
+        cache = pr.skip_graphs if skip else pr.graphs
+        entry = cache.get(key)
         if entry is None:   # static inputs: x, timesteps, then the k|v projections in the order of kvs
             names = list(kvs)
-            graph, static_in, so, _ = blocks.capture_graph(
-                lambda x_, t_, *kv: self._forward(x_, t_, dict(zip(names, kv)), context.shape[1], y), (x, timesteps, *kvs.values()))
-            entry = pr.graphs[key] = [graph, static_in, so, None]   # None: the k|v dict the static buffers were last filled from
+            graph, static_in, so, pool = blocks.capture_graph(
+                lambda x_, t_, *kv: self._forward(x_, t_, dict(zip(names, kv)), context.shape[1], y, skip), (x, timesteps, *kvs.values()))
+            entry = cache[key] = [graph, static_in, so, None]   # None: the k|v dict the static buffers were last filled from
             fresh = True
+            if skip:
+                entry.append(pool)
+                self._pool_bytes_seen = max(self._pool_bytes_seen, pool)
+                budget = self._graph_budget()
+                while len(cache) > 1 and (len(cache) > self.SKIP_GRAPH_CACHE or sum(e[4] for e in cache.values()) > budget):
+                    torch.cuda.synchronize(x.device)   # a graph of any stream may still be replaying out of the pool that is freed here
+                    cache.popitem(last=False)
+                if self._planned_graphs * pool > budget:
+                    # this candidate's launch sequences do not fit together: replay this one, then go eager (plan_graphs logs why)
+                    res = blocks.replay_graph(*entry[:3], (x, timesteps, *kvs.values()))
+                    torch.cuda.synchronize(x.device)   # the replay reads the pool that goes with the graph
+                    cache.pop(key, None)
+                    self.plan_graphs(self._planned_graphs)
+                    return res
+        elif skip:
+            cache.move_to_end(key)
         ins = (x, timesteps)
         if fresh or entry[3] is not kvs:  # the graph reads its own k|v buffers: refill them only when the conditioning changed
             ins += tuple(kvs.values())
             entry[3] = kvs if context_key is not None else None
         return blocks.replay_graph(*entry[:3], ins)
 
-    def _forward(self, x, timesteps, kvs, s_ctx, y=None):
+    def _forward(self, x, timesteps, kvs, s_ctx, y=None, skip_ids=()):
         assert y is None, "must specify y if and only if the model is class-conditional"
         pr = self._packed or self._prepare()
         plan: SDUNetPlan = self.plan
@@ -342,5 +434,5 @@ class UNetModel(HipModule):
             e = ops.linear_f32(e, pr.te0_w, pr.te0_b)
             e = ops.linear_f32(e, pr.te2_w, pr.te2_b, silu_in=True)
             emb = ops.linear_f32(e, pr.emb_w, pr.emb_b, silu_in=True)  # every ResBlock's emb_layers at once
-            h = blocks.u_walk(plan, lambda seq, h, skip: self._run_seq(pr, seq, h, skip, emb, kvs, s_ctx, x_nchw=x))
+            h = blocks.u_walk(plan, lambda seq, h, skip: self._run_seq(pr, seq, h, skip, emb, kvs, s_ctx, x_nchw=x, skip_ids=skip_ids))
             return blocks.head(pr.head, h, plan.out_channels)

@@ -18,6 +18,9 @@ latent granularity of the v1 first stage) or a ``.npy`` / ``.npz`` (``arr_0``) u
 
 As in the reference ``t_enc`` indexes a table of ``ddim_steps`` entries: ``strength`` must leave 1 <= t_enc <= ddim_steps - 1
 (the reference fails with an index error at strength 1.0).
+
+``--skip_layers "[[ids], ...]"`` gives per-step layer-skip lists beside ``--use_timestep``: list i belongs to entry i
+of ``--use_timestep`` as written; every UNet evaluation at that timestep bypasses those layers.
 """
 import argparse
 import os
@@ -29,7 +32,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import logger, ops  # noqa: E402
-from autodiffusion_amd.sd_script_util import (add_sd_sampling_flags, build_model, load_images, load_prompts, read_use_timestep,  # noqa: E402
+from autodiffusion_amd.sd_script_util import (add_sd_sampling_flags, build_model, load_images, load_prompts, read_skip_layers, read_use_timestep,  # noqa: E402
                                               require_gpu, save_samples, seed_everything)
 
 
@@ -44,6 +47,7 @@ def create_argparser():
     p.add_argument("--strength", type=float, default=0.75,
                    help="strength for noising/unnoising. 1.0 corresponds to full destruction of information in init image")
     add_sd_sampling_flags(p, "--config", "--side_multiple")   # from --tokenizer_dir on: additions (scripts/sd_search_ea.py)
+    add_sd_sampling_flags(p, "--skip_layers", "--skip_layers")
     return p
 
 
@@ -60,6 +64,7 @@ def main(argv=None):
         raise SystemExit(f"sd_img2img.py: --strength {opt.strength} of --ddim_steps {opt.ddim_steps} gives t_enc = {t_enc}; "
                          f"the DDIM table has entries 1 .. {opt.ddim_steps - 1} to encode at")
     sched = read_use_timestep(opt.use_timestep, opt.ddim_steps, "sd_img2img.py")
+    skips = read_skip_layers(getattr(opt, "skip_layers", ""), opt.use_timestep, opt.ddim_steps, "sd_img2img.py")
     seed_everything(opt.seed)
     logger.configure(opt.outdir)
     device = require_gpu("sd_img2img.py")
@@ -75,7 +80,8 @@ def main(argv=None):
         uc = model.get_learned_conditioning(empty) if opt.scale != 1.0 else None
         c = model.get_learned_conditioning(prompts)
         z_enc = sampler.stochastic_encode(init_latent, torch.tensor([t_enc] * opt.n_samples))   # encode (scaled latent)
-        samples = sampler.decode(z_enc, c, t_enc, unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc)
+        samples = sampler.decode(z_enc, c, t_enc, unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc,
+                                 skip_layers=skips)
         _, u8 = ops.vae_image_out(model.decode_first_stage(samples), want_unit=False, want_u8=True)
         out.append(u8.cpu().numpy())
     return save_samples(opt.outdir, np.concatenate(out, axis=0))

@@ -15,7 +15,7 @@ first stage's, image side / latent side).
 noisiest first; a step whose entry is 0 runs one unguided evaluation on the empty prompt instead of the guided pair
 (plms.py:164-171, scripts/txt2img_prompt_mask.py).  Everything else -- ``--init-img --ckpt --config --prompt --prompt_ids
 --tokenizer_dir --scale --ddim_steps --ddim_eta --n_samples --n_iter --seed --torso --synthetic --use_timestep --outdir
---side_multiple`` -- is scripts/sd_img2img.py's; what the two share is autodiffusion_amd/sd_script_util.py's.  Output:
+--side_multiple --skip_layers`` -- is scripts/sd_img2img.py's; what the two share is autodiffusion_amd/sd_script_util.py's.  Output:
 ``OUTDIR/samples_{N}x{H}x{W}x3.npz`` with ``arr_0`` = uint8 NHWC images.
 """
 import argparse
@@ -29,7 +29,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from autodiffusion_amd import logger, ops  # noqa: E402
-from autodiffusion_amd.sd_script_util import (add_sd_sampling_flags, build_model, load_images, load_prompts, read_use_timestep,  # noqa: E402
+from autodiffusion_amd.sd_script_util import (add_sd_sampling_flags, build_model, load_images, load_prompts, read_skip_layers, read_use_timestep,  # noqa: E402
                                               require_gpu, save_samples, seed_everything)
 
 F8 = 8   # pixels per latent of the KL-f8 first stage (--synthetic tiny's has two downsamplings: 4)
@@ -47,7 +47,7 @@ def create_argparser():
     p.add_argument("--prompt_mask", type=str, default="", help="'[1,1,0,...]', --plms only: one entry per step, noisiest first; 0 = that "
                                                                "step runs unguided on the empty prompt")
     p.add_argument("--no_composite", action="store_true", help="write the decoded images as they are: do not restore the kept pixels")
-    add_sd_sampling_flags(p, "--ddim_eta", "--side_multiple")
+    add_sd_sampling_flags(p, "--ddim_eta", "--skip_layers")
     return p
 
 
@@ -95,6 +95,7 @@ def main(argv=None):
         if opt.scale == 1.0 and 0 in prompt_mask:
             raise SystemExit("sd_inpaint.py: --prompt_mask with a 0 entry needs --scale != 1 (the empty prompt is encoded only then)")
     sched = read_use_timestep(opt.use_timestep, opt.ddim_steps, "sd_inpaint.py")
+    skips = read_skip_layers(getattr(opt, "skip_layers", ""), opt.use_timestep, opt.ddim_steps, "sd_inpaint.py")
     seed_everything(opt.seed)
     logger.configure(opt.outdir)
     device = require_gpu("sd_inpaint.py")
@@ -111,6 +112,8 @@ def main(argv=None):
         raise SystemExit(f"sd_inpaint.py: the image is {height} x {width}, its latent {x0.shape[2]} x {x0.shape[3]}: no whole factor")
     keep = torch.from_numpy(latent_keep_mask(repaint, f)).to(device)
     extra = {} if prompt_mask is None else {"prompt_mask": prompt_mask}
+    if skips is not None:
+        extra["skip_layers"] = skips   # in ascending timestep order, as sched is
     out = []
     for _ in range(opt.n_iter):
         uc = model.get_learned_conditioning(empty) if opt.scale != 1.0 else None

@@ -18,7 +18,11 @@ peak on the plan's algorithmic FLOPs and on the executed ones, which run the thr
 resize entry alone.
 --prompt-mask "[1,1,1,0,0,0]" times the K-step PLMS loop at the search's 6-latent call with that `prompt_mask` against all ones, and
 --masked the K-step DDIM loop with `mask=, x0=` against the unmasked one and the per-step blend alone: both on a captured hipGraph
-(GRAPH=0: eager), alternating windows of REPS (default 3) batches in one process, median of 5."""
+(GRAPH=0: eager), alternating windows of REPS (default 3) batches in one process, median of 5.
+--skip_layers "[ids]" (may be given several times; `transformers` and `level0` name the 16 transformers and the layers of the
+first, 64 x 64, level) times one UNet evaluation of BATCH latents with each layer-skip set beside the full network: alternating
+windows of REPS (default 5) evaluations between device events, median of 5, on a captured hipGraph (GRAPH=0: eager), one line per
+set with its launches per evaluation.  --synthetic {v1,tiny} picks the network (default v1)."""
 import os
 import sys
 import time
@@ -349,8 +353,77 @@ def masked_bench():
           f"{us / 4:.1f} us per launch")
 
 
+def named_skip_set(plan, text):
+    """--skip_layers' value -> sorted layer ids: a list literal, `transformers`, or `level0` (every layer at the input resolution)."""
+    import ast
+    from autodiffusion_amd.sd_arch import SDDownSpec, SDTransformerSpec, SDUpSpec
+    if text == "transformers":
+        return sorted(b.layer_id for b in plan.all_blocks() if isinstance(b, SDTransformerSpec))
+    if text == "level0":
+        ids, depth = [], 0
+        for seq in plan.input_blocks + [plan.middle_block] + plan.output_blocks:
+            for b in seq:
+                if getattr(b, "layer_id", -1) >= 0 and depth == 0:
+                    ids.append(b.layer_id)
+                depth += isinstance(b, SDDownSpec) - isinstance(b, SDUpSpec)
+        return sorted(ids)
+    ids = ast.literal_eval(text)
+    if not isinstance(ids, (list, tuple)) or not all(isinstance(i, int) and not isinstance(i, bool) for i in ids):
+        raise SystemExit(f"sd_bench.py: --skip_layers: a list of layer ids, `transformers` or `level0`, got {text!r}")
+    return sorted(ids)
+
+
+def skip_bench(texts, synthetic="v1"):
+    import statistics
+    from autodiffusion_amd.sd_script_util import TINY_UNET
+    cfg, hw, s_ctx = (SD_V1, 64, 77) if synthetic == "v1" else (TINY_UNET, 16, 77)
+    b, reps = int(os.environ.get("BATCH", "12")), int(os.environ.get("REPS", "5"))
+    m = UNetModel(image_size=32, use_spatial_transformer=True, **cfg).to(DEV)
+    m.randomize_(1234)
+    graph = os.environ.get("GRAPH", "1") == "1"
+    m.enable_graph(graph)
+    sets = [("none", ())] + [(t, tuple(named_skip_set(m.plan, t))) for t in texts]
+    m.plan_graphs(len({s_ for _, s_ in sets if s_}))
+    x = torch.randn(b, 4, hw, hw, device=DEV)
+    t = torch.full((b,), 500, device=DEV, dtype=torch.int64)
+    ctx = torch.randn(b, s_ctx, m.plan.context_dim, device=DEV)
+    launches = {}
+    names = ("conv", "conv2d", "gn_affine", "layernorm", "attention_cross", "geglu", "resample", "linear_f32", "timestep_embedding",
+             "nchw_to_nhwc_pad")
+    for name, ids in sets:     # launches per evaluation: counted on an eager pass through the ops entry points
+        count = [0]
+        saved = {k: getattr(ops, k) for k in names}
+        for k, fn in saved.items():
+            setattr(ops, k, (lambda fn: lambda *a_, **kw: count.__setitem__(0, count[0] + 1) or fn(*a_, **kw))(fn))
+        try:
+            m.enable_graph(False)(x, t, ctx, skip_layer=ids)
+        finally:
+            for k, fn in saved.items():
+                setattr(ops, k, fn)
+            m.enable_graph(graph)
+        launches[name] = count[0]
+        for _ in range(2):
+            out = m(x, t, ctx, context_key="bench", skip_layer=ids)
+        torch.cuda.synchronize()
+        assert torch.isfinite(out).all()
+    ms = {name: [] for name, _ in sets}
+    for _ in range(5):
+        for name, ids in sets:
+            ms[name].append(_timed(lambda: m(x, t, ctx, context_key="bench", skip_layer=ids), reps))
+    base = statistics.median(ms["none"])
+    for name, ids in sets:
+        med = statistics.median(ms[name])
+        print(f"SD {synthetic} UNet batch {b} ({'hipGraph' if graph else 'eager'}), skip_layers {name} ({len(ids)} of {m.layer_num} layers, "
+              f"{launches[name]} op calls): {med:.2f} ms / evaluation ({min(ms[name]):.2f} .. {max(ms[name]):.2f} over 5 windows of {reps}), "
+              f"{med / base:.3f} x the full network")
+
+
 if __name__ == "__main__":
-    if "--prompt-mask" in sys.argv[1:]:
+    if "--skip_layers" in sys.argv[1:]:
+        argv = sys.argv[1:]
+        skip_bench([argv[i + 1] for i, a in enumerate(argv) if a == "--skip_layers"],
+                   argv[argv.index("--synthetic") + 1] if "--synthetic" in argv else "v1")
+    elif "--prompt-mask" in sys.argv[1:]:
         import ast
         prompt_mask_bench([int(v) for v in ast.literal_eval(sys.argv[sys.argv.index("--prompt-mask") + 1])])
     elif "--masked" in sys.argv[1:]:
