@@ -256,6 +256,42 @@ def test_population_parallel_two_ranks_gloo(tmp_path):
             np.testing.assert_array_equal(z[r]["fid"], g[f"{tag}_top50_fid_e2"])
 
 
+# ------------------------------------------------------------------ 5b. one driver under both packages' searchers
+def test_equal_costs_are_assigned_round_robin():
+    """What lets the SD searchers use the cost-aware flush: with one cost for all, longest-first is exactly i % world."""
+    for world in range(1, 9):
+        for n in range(41):
+            assert EvolutionSearcher.assign_candidates([5] * n, world) == [i % world for i in range(n)], (n, world)
+
+
+def test_the_loops_and_the_joint_operators_exist_once():
+    from autodiffusion_amd import ea, sd_search, search
+    for name in ("search", "flush_pending", "_collect", "_fill_random", "update_top_k", "_visit", "is_legal", "is_legal_before_search",
+                 "get_random", "get_random_before_search", "get_cross", "get_mutation", "mutate_init_x", "_mutate", "_cross",
+                 "sample_active_subnet", "assign_candidates", "candidate_cost"):
+        assert getattr(search.EvolutionSearcher, name) is getattr(sd_search.EvolutionSearcher, name), name
+        assert getattr(search.EvolutionSearcher, name) is getattr(ea.EvolutionDriver, name), name
+    for name in ("_mutate", "_cross", "sample_active_subnet", "_after_selection", "_mutate_timesteps", "_touch_skips", "_draw_skips",
+                 "mutate_init_x", "_initial_candidate", "cand2gen", "_init_joint"):
+        assert getattr(search.DynamicEvolutionSearcher, name) is getattr(sd_search.DynamicEvolutionSearcher, name), name
+        assert getattr(search.DynamicEvolutionSearcher, name) is getattr(ea.JointSearch, name), name
+    for name in ("search", "flush_pending", "_collect", "_fill_random", "update_top_k", "_visit"):   # the loops stay the driver's
+        assert getattr(sd_search.DynamicEvolutionSearcher, name) is getattr(ea.EvolutionDriver, name), name
+    assert not hasattr(sd_search, "_Steps")
+
+
+def test_last_flush_of_flat_candidates_is_a_superset(monkeypatch):
+    monkeypatch.setattr(logger, "log", lambda *a: None)
+    s, ev = _searcher(population_parallel=True)
+    cands = [[1, 2, 3, 4], [8, 7, 6, 5], [9, 10, 11, 12], [13, 14, 15, 16]]
+    assert all(s.is_legal(str(c)) for c in cands) and ev.evaluated == []
+    s.flush_pending()
+    f = s.last_flush
+    assert f["owner"] == [0, 0, 0, 0] and f["costs"] == [4, 4, 4, 4] and f["assigned_cost"] == 16
+    assert f["candidates"] == 4 and f["assigned"] == 4 and f["evaluate_s"] >= 0 and f["collective"] is None
+    assert ev.evaluated == [sorted(c) for c in cands] and [s.vis_dict[str(sorted(c))]["fid"] for c in cands] == [fitness_of(c) for c in cands]
+
+
 # ------------------------------------------------------------------ 6. the command line
 def _cli():
     spec = importlib.util.spec_from_file_location("sd_search_ea", os.path.join(ROOT, "scripts", "sd_search_ea.py"))

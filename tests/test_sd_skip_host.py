@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from autodiffusion_amd import logger, sd_script_util, sd_search, search
+from autodiffusion_amd import ea, logger, sd_script_util, sd_search, search
 from autodiffusion_amd.sd_arch import (SD_V1, SD_V2, SDDownSpec, SDResBlockSpec, SDStemSpec, SDTransformerSpec, SDUpSpec,
                                        sd_unet_plan)
 from oracle import sd_nets
@@ -131,7 +131,7 @@ def test_joint_searcher_reproduces_search_py_value_for_value(monkeypatch, init, 
             s = search.DynamicEvolutionSearcher(args, model=None, base_diffusion=SimpleNamespace(original_num_steps=1000), time_step=4)
         else:
             s = _sd_joint(_opt(max_epochs=epochs, use_ddim_init_x=init))
-            assert isinstance(s, search.DynamicEvolutionSearcher) and s.model_layers == 14 and s.max_index_number == 4 * 14
+            assert isinstance(s, ea.JointSearch) and s.model_layers == 14 and s.max_index_number == 4 * 14
         evaluated, ranges = [], []
 
         def fitness(cand=None, args=None, s=s, evaluated=evaluated, ranges=ranges):
